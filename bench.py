@@ -13,6 +13,12 @@ bytes: neighbor models owned by other GPUs by RCCL send/recv over xGMI, overlapp
 interior rows (halo), or every model's column blocks by two RCCL all-to-alls around the local
 round (transpose; random expanders at 4+ GPUs) — topology_aware_learning_amd/transposed.py.
 
+A plain run sets up (pool placement, plan tuning), warms up, times --steps rounds and prints
+the result line.  --full adds what that figure does not need: the whole-round parity checks,
+the CPU baseline and the per-call side measurements.  --dump-outputs DIR writes the models the
+last timed round produced (dump_outputs); the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
 Prints ONE JSON line (rank 0).  See DESIGN.md for the byte accounting.
 """
 from __future__ import annotations
@@ -91,7 +97,52 @@ def parse():
     p.add_argument("--link-probe-mb", type=int, default=1024,
                    help="N > 1: bytes each rank sends to (and receives from) every other rank in the "
                         "link probe before the round is built (gloo rehearsals: at most 8 MiB)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the whole-round parity checks "
+                        "(K1 on every row, the reference's digests, the bf16 tolerance), the CPU baseline, "
+                        "the per-call K1 side measurement and --host-path; a plain run sets up, warms up, "
+                        "times the steps and prints the result line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (the output pool's "
+                        "segments, see dump_outputs) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.host_path and not args.full:
+        p.error("--host-path is a side measurement: it needs --full")
+    return args
+
+
+DUMP_SAMPLE_BYTES = 48 << 20  # the float segments of a dump; with the int64 counters it stays under 64 MB
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir, pool, n_rows: int, suffix: str = "", writers: int = 1) -> dict:
+    """--dump-outputs: rows [0, n_rows) of `pool` (the models the last timed step wrote), one
+    file per non-empty segment of the layout: f32.npy (float32), b16.npy (the bf16 values
+    widened to float32, exact) and i64.npy (float64: the counters stay far below 2^53), each
+    [n_rows, columns].  Float segments larger than DUMP_SAMPLE_BYTES together are cut to a fixed
+    sample of their columns, the same for every row: a sorted draw without replacement from
+    np.random.default_rng(DUMP_SAMPLE_SEED), so two builds run with the same arguments write
+    the same elements.  With `writers` ranks dumping their own rows (N > 1: files named by
+    `suffix`) each takes an equal share of that size.  Returns {file name: [shape, columns of
+    the segment]}."""
+    import torch
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written = {}
+    share = DUMP_SAMPLE_BYTES // writers // max(1, sum(g != "i64" for g, _, _ in pool.segments()))
+    for g, t, n in pool.segments():
+        k = n if g == "i64" else min(n, max(1, share // (4 * max(n_rows, 1))))
+        if k < n:
+            cols = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+            a = t[:n_rows].index_select(1, torch.from_numpy(cols).to(t.device))
+        else:
+            a = t[:n_rows, :n]
+        a = a.to(torch.float64 if g == "i64" else torch.float32).cpu().numpy()
+        name = f"{g}{suffix}.npy"
+        np.save(out_dir / name, np.ascontiguousarray(a))
+        written[name] = [list(a.shape), n]
+    return written
 
 
 def make_graph(kind: str, n_devices: int, degree: int, seed: int = 0):
@@ -408,33 +459,36 @@ def main():
             round_fn(seg(a), seg(b), plan, n=n_float, mode=mode)
             _ops.round_i64(a.i64, b.i64, plan, n=layout.n_i64)
 
-        # correctness check at full size: EVERY output row of the round (both segments) == K1
-        # on the same operands, bitwise (K1 itself is pinned to the reference's sha256 of
-        # ResNet-50 M = 9 calls; tests/test_gpu_fullsize.py pins whole rounds)
-        log(f"plan {plan.spec}; checking every row against K1")
-        step(pin, pout)
-        chk = torch.empty(n_float, dtype=seg(pin).dtype, device=dev)
-        chk_i = torch.empty(layout.n_i64, dtype=torch.int64, device=dev)
-        iv = torch.int16 if bf16 else torch.int32
-        bad_rows = []
-        for r in range(rows):
-            agg_fn([row(pin, j) for j in orders[r]], weights[r], chk, mode=mode)
-            same = torch.equal(chk.view(iv), row(pout, r).view(iv))
-            if layout.n_i64:
-                _ops.agg_i64([pin.row_i64(j) for j in orders[r]], weights[r], chk_i)
-                same = same and torch.equal(chk_i, pout.row_i64(r))
-            if not same:
-                bad_rows.append(r)
-        parity_ok = not bad_rows
-        del chk, chk_i
-        ref_check = None
-        if reference is not None:  # the round's outputs against the reference's own digests
-            ref_check = rowcheck.check_round(pout, range(rows), lay, orders, weights, seed_base, mode,
-                                             reference=reference)
-            parity_ok = parity_ok and ref_check["rows_differing"] == 0
-        tol = bf16_tolerance(pin, pout, orders[0], weights[0], n_float, dev) if bf16 else None
+        parity_ok = parity_k1 = ref_check = tol = None
+        if args.full:
+            # correctness check at full size: EVERY output row of the round (both segments) == K1
+            # on the same operands, bitwise (K1 itself is pinned to the reference's sha256 of
+            # ResNet-50 M = 9 calls; tests/test_gpu_fullsize.py pins whole rounds)
+            log(f"plan {plan.spec}; checking every row against K1")
+            step(pin, pout)
+            chk = torch.empty(n_float, dtype=seg(pin).dtype, device=dev)
+            chk_i = torch.empty(layout.n_i64, dtype=torch.int64, device=dev)
+            iv = torch.int16 if bf16 else torch.int32
+            bad_rows = []
+            for r in range(rows):
+                agg_fn([row(pin, j) for j in orders[r]], weights[r], chk, mode=mode)
+                same = torch.equal(chk.view(iv), row(pout, r).view(iv))
+                if layout.n_i64:
+                    _ops.agg_i64([pin.row_i64(j) for j in orders[r]], weights[r], chk_i)
+                    same = same and torch.equal(chk_i, pout.row_i64(r))
+                if not same:
+                    bad_rows.append(r)
+            parity_ok = not bad_rows
+            parity_k1 = dict(rows_checked=rows, rows_differing=len(bad_rows), first_bad=bad_rows[:8])
+            del chk, chk_i
+            if reference is not None:  # the round's outputs against the reference's own digests
+                ref_check = rowcheck.check_round(pout, range(rows), lay, orders, weights, seed_base, mode,
+                                                 reference=reference)
+                parity_ok = parity_ok and ref_check["rows_differing"] == 0
+            tol = bf16_tolerance(pin, pout, orders[0], weights[0], n_float, dev) if bf16 else None
+            log(f"parity {parity_ok} ({len(bad_rows)} rows differ)")
 
-        log(f"parity {parity_ok} ({len(bad_rows)} rows differ); timing {args.steps} steps")
+        log(f"plan {plan.spec}; timing {args.steps} steps")
         pools = [pin, pin] if in_place else [pin, pout]
         for i in range(args.warmup):
             step(pools[i % 2], pools[(i + 1) % 2])
@@ -461,7 +515,7 @@ def main():
                                                   tuned_ms=plan.tuned_ms, candidates=plan.candidates,
                                                   spec=plan.spec),
             per_call_equivalent_GBps=per_call_bytes / (k_ms * 1e-3) / 1e9,
-            parity_k3_vs_k1=dict(rows_checked=rows, rows_differing=len(bad_rows), first_bad=bad_rows[:8]),
+            parity_k3_vs_k1=parity_k1,
             parity_vs_reference=ref_check,
             valu=valu_floor(len(col), rows, n_float, k_ms, mode, bf16=bool(layout.n_b16)))
         if tol is not None:
@@ -470,8 +524,11 @@ def main():
         result_extra["in_place"] = in_place
         steps_done = args.steps
         units = rows * n_params * steps_done
+        dumped = None
+        if args.dump_outputs:  # the pool the last timed step wrote, before anything else touches it
+            dumped = dump_outputs(args.dump_outputs, pools[args.steps % 2], rows)
         k1 = None
-        if not args.no_k1 and not bf16:
+        if args.full and not args.no_k1 and not bf16:
             k1 = bench_k1(layout, pin, orders, weights, mode, dev)
         hostp = bench_host_path(lay, M, dev) if args.host_path else None
     else:
@@ -488,24 +545,27 @@ def main():
                         link_gbps=probe["GBps"] if world > 1 else None)
         rlog(f"{sr.exchange_kind} exchange over {sr.transport}, {len(sr.own_ids)} own devices; first round")
         rowcheck.fill_owned(sr.pool_a, lay, sr.own_ids, seed_base)
-        sr.step()
-        torch.cuda.synchronize(dev)
-        rlog("first round done; checking every owned row")
-        # every output row this rank owns, against the reference's digests or K1 on operands
-        # regenerated from their seeds - never on what the exchange delivered (rowcheck)
-        chk = rowcheck.check_round(sr.own_rows(), sr.own_ids, lay, orders, weights, seed_base, mode,
-                                   reference=reference)
         cdev = dev if args.dist_backend == "nccl" else torch.device("cpu")  # collectives' scalars
-        cnt = torch.tensor([chk["rows_checked"], chk["rows_differing"]], dtype=torch.int64, device=cdev)
-        dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-        bad_all = [None] * world
-        dist.all_gather_object(bad_all, chk["first_bad"])
-        rows_checked, rows_differing = int(cnt[0].item()), int(cnt[1].item())
-        parity_dist = rows_differing == 0 and rows_checked == n_dev_total
-        parity_rows = dict(rows_checked=rows_checked, rows_differing=rows_differing,
-                           first_bad=sorted(j for b in bad_all for j in b)[:8], reference=chk["reference"],
-                           devices=n_dev_total)
-        rlog(f"rows checked {rows_checked}, differing {rows_differing}; {args.warmup} warm-up + {args.steps} timed rounds")
+        parity_dist = parity_rows = None
+        if args.full:
+            sr.step()
+            torch.cuda.synchronize(dev)
+            rlog("first round done; checking every owned row")
+            # every output row this rank owns, against the reference's digests or K1 on operands
+            # regenerated from their seeds - never on what the exchange delivered (rowcheck)
+            chk = rowcheck.check_round(sr.own_rows(), sr.own_ids, lay, orders, weights, seed_base, mode,
+                                       reference=reference)
+            cnt = torch.tensor([chk["rows_checked"], chk["rows_differing"]], dtype=torch.int64, device=cdev)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+            bad_all = [None] * world
+            dist.all_gather_object(bad_all, chk["first_bad"])
+            rows_checked, rows_differing = int(cnt[0].item()), int(cnt[1].item())
+            parity_dist = rows_differing == 0 and rows_checked == n_dev_total
+            parity_rows = dict(rows_checked=rows_checked, rows_differing=rows_differing,
+                               first_bad=sorted(j for b in bad_all for j in b)[:8], reference=chk["reference"],
+                               devices=n_dev_total)
+            rlog(f"rows checked {rows_checked}, differing {rows_differing}")
+        rlog(f"{args.warmup} warm-up + {args.steps} timed rounds")
         for _ in range(args.warmup):
             sr.step()
         torch.cuda.synchronize(dev)
@@ -543,6 +603,10 @@ def main():
                                              kernel_share_of_step=round(k_ms / ms_step, 3)))
         units = n_dev_total * n_params * args.steps
         parity_ok = parity_dist
+        dumped = None
+        if args.dump_outputs:  # every rank its own rows, in the order of its own_ids
+            dumped = dump_outputs(args.dump_outputs, sr.own_rows(), sr.local_rows,
+                                  suffix=f"_rank{rank}" if world > 1 else "", writers=world)
         k1 = None
         hostp = None
 
@@ -558,7 +622,7 @@ def main():
         traffic = load_traffic(traffic_key(result_extra["kernel"], result_extra["plan"]["spec"],
                                            workload_key(args.graph, n_dev_total, args.model, args.dtype, args.weights)))
     cpu = None
-    if not args.no_cpu_baseline and not sharded:
+    if args.full and not args.no_cpu_baseline and not sharded:
         log("CPU baseline")
         cpu = cpu_baseline(lay, M, args.cpu_seconds)  # bf16 layouts: the reference's loop on bf16 tensors
     value = units / el
@@ -592,9 +656,12 @@ def main():
                                          / HBM_PEAK_GBPS) if not sharded and "first_pair_ms" in result_extra.get(
                                              "placement", {}) else None},
         "cpu_baseline": cpu,
-        "parity": parity_ok,
+        "parity": parity_ok,  # None without --full: nothing was checked
+        "full": args.full,
         **result_extra,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if k1 is not None:
         out["k1_per_call"] = k1
     if hostp is not None:

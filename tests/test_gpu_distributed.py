@@ -176,7 +176,7 @@ def test_bench_multi_rank_rehearsal(cuda, tmp_path, exchange, world, tune):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={port}", str(ROOT / "bench.py"), "--gpus", str(world),
            "--dist-backend", "gloo", "--exchange", exchange, "--model", "cifar10", "--devices-per-gpu", "16",
-           "--degree", "4", "--steps", "2", "--warmup", "1"] + ([] if tune else ["--no-tune"])
+           "--degree", "4", "--steps", "2", "--warmup", "1", "--full"] + ([] if tune else ["--no-tune"])
     out = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -210,7 +210,7 @@ def test_bench_world8_rehearsal(cuda, tmp_path, graph, model, dtype, exchange):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
            "--master-addr", "127.0.0.1", f"--master-port={port}", str(ROOT / "bench.py"), "--gpus", "8",
            "--dist-backend", "gloo", "--graph", graph, "--model", model, "--dtype", dtype, *devices,
-           "--exchange", exchange, "--max-params", "131072", "--steps", "2", "--warmup", "1"] + \
+           "--exchange", exchange, "--max-params", "131072", "--steps", "2", "--warmup", "1", "--full"] + \
         ([] if graph == "random" else ["--no-tune"])
     out = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -254,7 +254,7 @@ def test_bench_sharded_one_rank_rccl(cuda, tmp_path, exchange, tune, model, tran
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", f"--master-port={port}", str(ROOT / "bench.py"), "--gpus", "1",
            "--sharded", "--dist-backend", "nccl", "--exchange", exchange, "--model", model, *shape,
-           "--transport", transport, "--steps", "2", "--warmup", "1"] + ([] if tune else ["--no-tune"])
+           "--transport", transport, "--steps", "2", "--warmup", "1", "--full"] + ([] if tune else ["--no-tune"])
     out = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
