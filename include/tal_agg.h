@@ -335,6 +335,66 @@ int32_t tal_cosine_params(const float* const* a_ptrs_host, const float* const* b
                           int32_t n_pairs, const int64_t* plan_dev, const int64_t* plan_host,
                           int32_t n_chunks, void* scratch, float* out_dev, void* stream);
 
+/* ---- K2r: K2 over a whole round's pair list (ABI 26) --------------------------------------
+ * The `*_sim` strategies need the cosine of every client with every neighbor.  In a batched
+ * round all models are rows of one pool segment (row r at pool + r ld), and the pairs of a round
+ * share work that a per-client call cannot: a clamped norm belongs to a model, not to a pair, and
+ * the value of a pair is bitwise symmetric (fl(x/n1) fl(y/n2) commutes and every sum runs in the
+ * same order), so an undirected topology needs each edge once.  The round form computes every
+ * norm once per model, every unique unordered pair once, and writes out_dev[j] for each of the
+ * caller's ordered pairs, in the caller's order.  Every fp32 operation and its order are K2's
+ * (the kernels share K2's device code), so out_dev[j] is bit for bit what tal_cosine_params
+ * gives for (pool + row_a[j] ld, pool + row_b[j] ld) under the same plan, thread word included;
+ * a NaN result is NaN for both orders (payload unspecified).
+ *
+ * The table (int32 words; built on the host by tal_cosine_round_build into a buffer of at least
+ * tal_cosine_round_words(n_pairs) words, or exactly info->words, and copied to the device by the
+ * caller, the host copy passed too):
+ *   {n_pairs, n_unique, n_models, n_groups, max_group, pool_rows, words, 0}
+ *   models[n_models]     the distinct rows referenced, ascending; a model's slot is its index here
+ *   unique[n_unique][2]  the distinct unordered pairs as model slots {a, b}, a the row its
+ *                        group shares (a == b, the self pair, is allowed), group after group
+ *   groups[n_groups][3]  {slot a, first unique pair, count}: consecutive unique pairs that share
+ *                        row a, at most 8 to a group (one streamed product workgroup holds a
+ *                        and 8 others in LDS).  Each pair is given to one of its two rows so
+ *                        that groups fill: the row with the most pairs still to place (8 or
+ *                        more count alike, ties to the smaller row) takes up to 8 of them, until
+ *                        none is left; a row with more partners than 8 gets several groups
+ *   map[n_pairs]         the unique pair of each ordered pair
+ * tal_cosine_round_build: TAL_ERR_INVALID for n_pairs <= 0, a null row array or a row outside
+ * [0, pool_rows); TAL_ERR_CAPACITY, with the need in info->words, when table_host is null or
+ * capacity_words is too small.  info carries the counts.
+ *
+ * Scratch (device, from the caller): 4 n_outputs per model (the norm table), 4 (n_outputs +
+ * n_seg) per unique pair of a batch, 4 per unique pair.  tal_cosine_round_scratch_bytes picks
+ * the largest batch of whole groups under budget_bytes (at most 32768 pairs), stores it in
+ * info->batch_pairs with the number of batches in info->n_batches, and returns the bytes needed
+ * (<= budget_bytes); -1 for bad arguments or when not even the largest group fits.
+ * tal_cosine_round walks the groups in those batches.  It allocates nothing, runs every launch on
+ * `stream`, and never synchronises.  plan_dev / plan_host / n_chunks: a plan of
+ * tal_cosine_plan_build, as for tal_cosine_params; ld (elements) must cover the plan's tensors. */
+typedef struct tal_cosine_round_info {
+  int32_t n_pairs;     /* ordered pairs given */
+  int32_t n_unique;    /* distinct unordered pairs */
+  int32_t n_models;    /* distinct rows */
+  int32_t n_groups;
+  int32_t max_group;   /* pairs of the largest group (<= 8) */
+  int32_t pool_rows;
+  int32_t batch_pairs; /* set by tal_cosine_round_scratch_bytes: unique pairs per batch */
+  int32_t n_batches;   /* set by tal_cosine_round_scratch_bytes */
+  int64_t words;       /* table words */
+} tal_cosine_round_info;
+int64_t tal_cosine_round_words(int32_t n_pairs);
+int32_t tal_cosine_round_build(const int32_t* row_a_host, const int32_t* row_b_host, int32_t n_pairs,
+                               int32_t pool_rows, int32_t* table_host, int64_t capacity_words,
+                               tal_cosine_round_info* info);
+int64_t tal_cosine_round_scratch_bytes(const int64_t* plan_host, const int32_t* table_host,
+                                       tal_cosine_round_info* info, int64_t budget_bytes);
+int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
+                         int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
+                         const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
+                         float* out_dev, void* stream);
+
 /* ---- FedProx proximal term ------------------------------------------------
  * Reference: local_train, tasks.py:277-286: loss += (prox_coeff / 2) * sum_t sum_p
  * ||w_p - wt_p||_2 over the neighbors t and the parameter tensors p.  Here the parameters are
@@ -383,6 +443,10 @@ int32_t tal_host_agg_bf16(const uint16_t* const* x_host, const double* w_host, i
  * as tal_cosine_params, i.e. torch's CPU order, bit for bit.  Up to 16 host threads. */
 int32_t tal_host_cosine(const float* const* a_host, const float* const* b_host, int32_t n_pairs,
                         const int64_t* plan_host, float* out);
+/* tal_cosine_round on a HOST pool (no GPU visible): every unique pair of the table once through
+ * tal_host_cosine's arithmetic, out[j] for each ordered pair. */
+int32_t tal_host_cosine_round(const float* pool_host, int64_t ld, const int64_t* plan_host,
+                              const int32_t* table_host, const tal_cosine_round_info* info, float* out);
 
 /* ---- Synthetic pool rows (test / benchmark inputs) --------------------------
  * Not a reference interface: the reference trains its models; the benchmark and the full-size

@@ -314,7 +314,8 @@ class DecentrallearnApp:
         same fp32 weights).  batch: (future position, client, its training future, drawn
         operand ids with self last, kwargs) per aggregation; nxt: the round's
         {client: {"train": future}}.  Returns each entry's aggregated (results, client) tuple,
-        in order."""
+        in order.  The `*_sim` strategies' similarities for the whole round come from one
+        similarity.cosine_round call before the launch (_round_similarities)."""
         from topology_aware_learning_amd import arena
         from topology_aware_learning_amd.arena import bound_row
         from topology_aware_learning_amd.multipool import MultiPool
@@ -357,14 +358,19 @@ class DecentrallearnApp:
             row_of[id(m)] = b[1]
             return b[1]
 
+        round_sims = None
+        if rule is not None and rule.__name__ == "_sim_centrality_weights":
+            round_sims = self._round_similarities(batch, nxt, memo, pool_row)
         orders, weights, out_rows, done = [], [], [], []
         text = io.StringIO()
         with contextlib.redirect_stdout(text) if key is not None else contextlib.nullcontext():
-            for _, _, agg_client, idxs, kwargs in batch:
+            for pos, (_, _, agg_client, idxs, kwargs) in enumerate(batch):
                 me = memo[id(agg_client)]
                 done.append(me)
                 if rule is None:
                     continue
+                if round_sims is not None:
+                    kwargs = dict(kwargs, sims=round_sims[pos])
                 got = rule(me, [memo[id(nxt[i]["train"])] for i in idxs], **kwargs)
                 orders.append([row_of[id(m)] if id(m) in row_of else pool_row(m) for m in got[0]])
                 weights.append(list(map(float, got[1])))
@@ -386,6 +392,26 @@ class DecentrallearnApp:
                 self._round_cache[key] = dict(orders=orders, weights=weights, out_rows=out_rows, plan=plan,
                                               text=text.getvalue(), gen=arena._GEN[0], rows=sorted(rows.items()))
         return done
+
+    def _round_similarities(self, batch, nxt, memo, pool_row) -> list:
+        """The `*_sim` strategies' cosine similarities for a whole batched round in ONE call
+        (similarity.cosine_round: every model's norms once, every edge once, one copy to the
+        host) on the pool as it is after training, before the round's K3 launch: per batch
+        entry {neighbor idx: similarity with the entry's client}, self excluded - what
+        _sim_centrality_weights otherwise gets from one K2 launch and one synchronisation per
+        client, bit for bit."""
+        from topology_aware_learning_amd.similarity import cosine_round
+
+        pairs, spans = [], []
+        for _, _, agg_client, idxs, _ in batch:
+            me = memo[id(agg_client)][1]
+            others = [memo[id(nxt[i]["train"])][1] for i in idxs]
+            others = [c for c in others if c.idx != me.idx]
+            r = pool_row(me.model)
+            spans.append((len(pairs), [c.idx for c in others]))
+            pairs.extend((r, pool_row(c.model)) for c in others)
+        vals = cosine_round(self.pool, pairs, memo[id(batch[0][2])][1].model) if pairs else []
+        return [dict(zip(ids, vals[p0: p0 + len(ids)])) for p0, ids in spans]
 
     def _round_key(self, batch, rule):
         """A round's operand rows and weights are a function of its drawn neighbor sets and the
@@ -416,7 +442,9 @@ class DecentrallearnApp:
         the whole halo moves first (every GPU's ghost rows from their owners: RCCL sends /
         receives between this process's per-device communicators), then each GPU's share of the
         round runs as one K3 launch on its pool (own and ghost rows in, own rows out in place),
-        each on its device's stream behind that device's messages."""
+        each on its device's stream behind that device's messages.  The `*_sim` strategies keep
+        the per-client cosine here (cosine_pairs over the ghost rows, one K2 launch per client):
+        the round form (similarity.cosine_round) reads rows of one pool."""
         from topology_aware_learning_amd.arena import bound_row
         from topology_aware_learning_amd.round import RoundExecutor
 

@@ -194,7 +194,10 @@ def _unweighted_weights(client_future, neighbor_futures, **kwargs):
     return _models(neighbor_futures), _w.unweighted(len(neighbor_futures))
 
 
-def _sim_centrality_weights(client_future, neighbor_futures, **kwargs):
+def _sim_centrality_weights(client_future, neighbor_futures, sims=None, **kwargs):
+    """sims: {neighbor idx: cosine similarity with this client} when the caller already has them
+    (the batched round computes a whole round's in one call, similarity.cosine_round); None: one
+    K2 launch for this client (cosine_pairs)."""
     cent_dict = kwargs["centrality_dict"]
     metric = kwargs["centrality_metric"]
     softmax = kwargs["softmax"]
@@ -202,8 +205,11 @@ def _sim_centrality_weights(client_future, neighbor_futures, **kwargs):
     print(f"{metric} aggregate round w/ {softmax=}")
     me = client_future[1]
     others = [f[1] for f in neighbor_futures if f[1].idx != me.idx]
-    sims_list = cosine_pairs(me.model, [c.model for c in others])
-    sims = {c.idx: s for c, s in zip(others, sims_list)}
+    if sims is None:
+        sims_list = cosine_pairs(me.model, [c.model for c in others])
+        sims = {c.idx: s for c, s in zip(others, sims_list)}
+    else:
+        sims = {c.idx: sims[c.idx] for c in others}
     order = [f[1].idx for f in neighbor_futures]
     w, coeff = _w.sim_centrality(order, me.idx, cent_dict[metric], sims, softmax, coeff)
     if softmax:

@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 EXPORTED = (
     "tal_last_error",
@@ -51,6 +51,10 @@ EXPORTED = (
     "tal_cosine_plan_set_threads",
     "tal_cosine_scratch_bytes",
     "tal_cosine_params",
+    "tal_cosine_round_words",
+    "tal_cosine_round_build",
+    "tal_cosine_round_scratch_bytes",
+    "tal_cosine_round",
     "tal_prox_plan_words",
     "tal_prox_plan_build",
     "tal_prox_scratch_bytes",
@@ -68,6 +72,7 @@ EXPORTED = (
     "tal_host_agg_i64",
     "tal_host_agg_bf16",
     "tal_host_cosine",
+    "tal_host_cosine_round",
 )
 
 
@@ -124,6 +129,22 @@ class RoundPlanInfo(ctypes.Structure):
     ]
 
 
+class CosineRoundInfo(ctypes.Structure):
+    """tal_cosine_round_info (tal_agg.h K2r)."""
+
+    _fields_ = [
+        ("n_pairs", ctypes.c_int32),
+        ("n_unique", ctypes.c_int32),
+        ("n_models", ctypes.c_int32),
+        ("n_groups", ctypes.c_int32),
+        ("max_group", ctypes.c_int32),
+        ("pool_rows", ctypes.c_int32),
+        ("batch_pairs", ctypes.c_int32),
+        ("n_batches", ctypes.c_int32),
+        ("words", ctypes.c_int64),
+    ]
+
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -163,6 +184,13 @@ _SIGS = {
     "tal_cosine_plan_set_threads": (_I32, [_PI64, _I32]),
     "tal_cosine_scratch_bytes": (_I64, [_PI64, _I32]),
     "tal_cosine_params": (_I32, [_PP, _PP, _I32, _P, _PI64, _I32, _P, _P, _P]),
+    "tal_cosine_round_words": (_I64, [_I32]),
+    "tal_cosine_round_build": (_I32, [_PI32, _PI32, _I32, _I32, _PI32, _I64, ctypes.POINTER(CosineRoundInfo)]),
+    "tal_cosine_round_scratch_bytes": (_I64, [_PI64, _PI32, ctypes.POINTER(CosineRoundInfo), _I64]),
+    "tal_cosine_round": (
+        _I32,
+        [_P, _I64, _P, _PI64, _I32, _P, _PI32, ctypes.POINTER(CosineRoundInfo), _P, _I64, _P, _P],
+    ),
     "tal_prox_plan_words": (_I64, [_PI64, _I32]),
     "tal_prox_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),
     "tal_prox_scratch_bytes": (_I64, [_I32, _I32]),
@@ -180,6 +208,7 @@ _SIGS = {
     "tal_host_agg_i64": (_I32, [_PP, _PD, _I32, _P, _I64]),
     "tal_host_agg_bf16": (_I32, [_PP, _PD, _I32, _P, _I64, _I32]),
     "tal_host_cosine": (_I32, [_PP, _PP, _I32, _PI64, _P]),
+    "tal_host_cosine_round": (_I32, [_P, _I64, _PI64, _PI32, ctypes.POINTER(CosineRoundInfo), _P]),
 }
 
 _lock = threading.Lock()

@@ -45,7 +45,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 25;
+constexpr int kAbiVersion = 26;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -3062,9 +3062,11 @@ __device__ __forceinline__ int64_t cos_ceil_log2(int64_t x) {
 }
 
 // torch multi_row_sum: NR interleaved streams load(i, k), a 4-level cascade whose level
-// boundaries depend only on i (so one column of a 32-column chunk is the NR = 1 case)
-template <int NR, class Load>
-__device__ __forceinline__ void cos_multi_row(Load load, int64_t size, float* out) {
+// boundaries depend only on i (so one column of a 32-column chunk is the NR = 1 case).  The NR
+// values of index i come from one load_all(i, v) call, so streams that share an operand (the
+// round form's pairs with one `a`) compute it once; kU: the load batch, see below.
+template <int NR, int kU = 8, class LoadAll>
+__device__ __forceinline__ void cos_multi_row_v(LoadAll load_all, int64_t size, float* out) {
   constexpr int kL = 4;
   const int64_t lp = cos_ceil_log2(size) / kL > 4 ? cos_ceil_log2(size) / kL : 4;
   const int64_t step = int64_t{1} << lp;
@@ -3079,14 +3081,12 @@ __device__ __forceinline__ void cos_multi_row(Load load, int64_t size, float* ou
   // loads are issued together, then added in order (each stream k keeps torch's order), so a
   // serial chain waits on one memory latency per batch, not per element (8 ran 0.62-0.63 ms
   // for 8 ResNet-50 pairs, 4 0.68, one element at a time 0.94)
-  constexpr int kU = 8;
+  static_assert(kU == 8 || kU == 4 || kU == 2, "kU divides the level-0 run (>= 16)");
   while (i + step <= size) {
     for (int64_t j = 0; j < step; j += kU, i += kU) {
       float v[kU][NR];
 #pragma unroll
-      for (int u = 0; u < kU; ++u)
-#pragma unroll
-        for (int k = 0; k < NR; ++k) v[u][k] = load(i + u, k);
+      for (int u = 0; u < kU; ++u) load_all(i + u, v[u]);
 #pragma unroll
       for (int u = 0; u < kU; ++u)
 #pragma unroll
@@ -3102,15 +3102,26 @@ __device__ __forceinline__ void cos_multi_row(Load load, int64_t size, float* ou
       if ((i & (mask0 << (j * lp))) != 0) break;
     }
   }
-  for (; i < size; ++i)
+  for (; i < size; ++i) {
+    float v[NR];
+    load_all(i, v);
 #pragma unroll
-    for (int k = 0; k < NR; ++k) acc[0][k] = __fadd_rn(acc[0][k], load(i, k));
+    for (int k = 0; k < NR; ++k) acc[0][k] = __fadd_rn(acc[0][k], v[k]);
+  }
 #pragma unroll
   for (int j = 1; j < kL; ++j)
 #pragma unroll
     for (int k = 0; k < NR; ++k) acc[0][k] = __fadd_rn(acc[0][k], acc[j][k]);
 #pragma unroll
   for (int k = 0; k < NR; ++k) out[k] = acc[0][k];
+}
+
+template <int NR, class Load>
+__device__ __forceinline__ void cos_multi_row(Load load, int64_t size, float* out) {
+  cos_multi_row_v<NR>([&](int64_t i, float* v) {
+#pragma unroll
+    for (int k = 0; k < NR; ++k) v[k] = load(i, k);
+  }, size, out);
 }
 
 // torch row_sum: 4 interleaved partial sums (element 4 i + k), the remainder into partial 0,
@@ -3123,6 +3134,34 @@ __device__ __forceinline__ float cos_row_sum(Load load, int64_t size) {
   for (int64_t i = si * 4; i < size; ++i) ps[0] = __fadd_rn(ps[0], load(i));
   for (int k = 1; k < 4; ++k) ps[0] = __fadd_rn(ps[0], ps[k]);
   return ps[0];
+}
+
+// row_sum of the P product rows qa(i) qb(i, p) that share the factor qa: stream 4 p + k of the
+// cascade is row_sum's partial k of pair p, and qa(i) is computed once for the P pairs.  Each
+// out[p] is bit for bit cos_row_sum of pair p's own products (the streams do not interact).
+template <int P, int kU, class QA, class QB>
+__device__ __forceinline__ void cos_row_sum_pairs(QA qa, QB qb, int64_t size, float* out) {
+  float ps[4 * P];
+  const int64_t si = size / 4;
+  cos_multi_row_v<4 * P, kU>([&](int64_t i, float* v) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float a = qa(i * 4 + k);
+#pragma unroll
+      for (int p = 0; p < P; ++p) v[4 * p + k] = __fmul_rn(a, qb(i * 4 + k, p));
+    }
+  }, si, ps);
+  for (int64_t i = si * 4; i < size; ++i) {
+    const float a = qa(i);
+#pragma unroll
+    for (int p = 0; p < P; ++p) ps[4 * p] = __fadd_rn(ps[4 * p], __fmul_rn(a, qb(i, p)));
+  }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+#pragma unroll
+    for (int k = 1; k < 4; ++k) ps[4 * p] = __fadd_rn(ps[4 * p], ps[4 * p + k]);
+    out[p] = ps[4 * p];
+  }
 }
 
 // correctly rounded sqrt (llvm.sqrt.f32 under HIP's default correctly-rounded divide/sqrt);
@@ -3394,27 +3433,13 @@ __device__ __forceinline__ void col_stream(const ColLoads& L, int I, int B, floa
   }
 }
 
-// Norms: one workgroup per (streamed chunk, group of model slots); thread (g, c): model slot
-// m0 + g, output c of the chunk: |x| = sqrt(fma chain over i in index order), clamped (torch's
-// NormTwoOps over dim 1, cosine_similarity's clamp_min), into nrm[slot n_out + output].
-__global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, const int64_t* __restrict__ plan, int n_seg,
-                                                              int cnt, int same_a, float* __restrict__ nrm) {
-  __shared__ float lds[kColModels * kColMS];
-  const ColChunk k = col_chunk(plan, n_seg, blockIdx.x);
-  const int n_models = same_a ? 1 + cnt : 2 * cnt;
-  const int nmw = min(kColModels, kColThreads / k.Cf);
-  const int m0 = static_cast<int>(blockIdx.y) * nmw;
-  if (m0 >= n_models) return;
-  const int nmod = min(nmw, n_models - m0);
-  const float* gm[kColModels];
-#pragma unroll
-  for (int m = 0; m < kColModels; ++m) {
-    // model slot s: one a shared by all pairs (slot 0 = a, 1 + p = b_p) or one per pair (2 p = a_p,
-    // 2 p + 1 = b_p); the kernel argument is indexed in place (a reference to it would copy it
-    // to scratch)
-    const int sl = m0 + min(m, nmod - 1);
-    gm[m] = same_a ? (sl == 0 ? pr.a[0] : pr.b[sl - 1]) : ((sl & 1) ? pr.b[sl >> 1] : pr.a[sl >> 1]);
-  }
+// The norm chains of one workgroup over the chunk's steps: thread (g, c) is model gm[g], output c
+// of the chunk: |x| = sqrt(fma chain over i in index order), clamped (torch's NormTwoOps over dim
+// 1, cosine_similarity's clamp_min), into nrm[(slot0 + g) n_out + output].  Shared by K2
+// (k_cos_col_norms) and its round form (k_cosr_col_norms), which differ only in where the model
+// pointers come from.
+__device__ __forceinline__ void cos_col_norms_body(const ColChunk& k, const float* const* gm, int nmod, int slot0,
+                                                   int64_t n_out, float* lds, float* __restrict__ nrm) {
   ColLoads L;
   col_loads_init(L, gm, nmod, k);
   const int t = threadIdx.x, g = t / k.Cf, c = t - g * k.Cf;
@@ -3445,7 +3470,29 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, cons
   // the norm, negated when the chain has an element outside cos_rdiv's range (the products then
   // check element by element); a NaN norm stays NaN either way
   const float nv = cos_clamp(cos_sqrt_rn(acc));
-  if (live) nrm[static_cast<int64_t>(m0 + g) * plan[1] + k.out0 + c] = in_range ? nv : -nv;
+  if (live) nrm[static_cast<int64_t>(slot0 + g) * n_out + k.out0 + c] = in_range ? nv : -nv;
+}
+
+// Norms: one workgroup per (streamed chunk, group of model slots); see cos_col_norms_body.
+__global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, const int64_t* __restrict__ plan, int n_seg,
+                                                              int cnt, int same_a, float* __restrict__ nrm) {
+  __shared__ float lds[kColModels * kColMS];
+  const ColChunk k = col_chunk(plan, n_seg, blockIdx.x);
+  const int n_models = same_a ? 1 + cnt : 2 * cnt;
+  const int nmw = min(kColModels, kColThreads / k.Cf);
+  const int m0 = static_cast<int>(blockIdx.y) * nmw;
+  if (m0 >= n_models) return;
+  const int nmod = min(nmw, n_models - m0);
+  const float* gm[kColModels];
+#pragma unroll
+  for (int m = 0; m < kColModels; ++m) {
+    // model slot s: one a shared by all pairs (slot 0 = a, 1 + p = b_p) or one per pair (2 p = a_p,
+    // 2 p + 1 = b_p); the kernel argument is indexed in place (a reference to it would copy it
+    // to scratch)
+    const int sl = m0 + min(m, nmod - 1);
+    gm[m] = same_a ? (sl == 0 ? pr.a[0] : pr.b[sl - 1]) : ((sl & 1) ? pr.b[sl >> 1] : pr.a[sl >> 1]);
+  }
+  cos_col_norms_body(k, gm, nmod, m0, plan[1], lds, nrm);
 }
 
 // Products: one workgroup per (streamed chunk, group of pairs); thread (g, c): pair p0 + g, output
@@ -3455,37 +3502,15 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, cons
 // counts at width 2^4), the partial last run at the end, the I mod 4 remainder into stream 0,
 // then the streams in order; s = 0 + that.  Divisions: cos_rdiv where both norms and the element
 // are in its range (equal to the IEEE quotient there), else __fdiv_rn.
-__global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs pr, const int64_t* __restrict__ plan, int n_seg,
-                                                              int cnt, int same_a, const float* __restrict__ nrm,
-                                                              float* __restrict__ s_all) {
-  __shared__ float lds[kColModels * kColMS];
-  // chunks in the reverse of the norms' order: the first workgroups read what the norms kernel
-  // read last, still in the 256 MiB last-level cache
-  const ColChunk k = col_chunk(plan, n_seg, gridDim.x - 1 - blockIdx.x);
-  const int ppw = same_a ? kColPairs : kColPairs / 2;
-  const int p0 = static_cast<int>(blockIdx.y) * ppw;
-  if (p0 >= cnt) return;
-  const int np = min(ppw, cnt - p0);
-  const int nmod = same_a ? 1 + np : 2 * np;
-  const float* gm[kColModels];
-#pragma unroll
-  for (int m = 0; m < kColModels; ++m) {
-    const int mm = min(m, nmod - 1);
-    gm[m] = same_a ? (mm == 0 ? pr.a[p0] : pr.b[p0 + mm - 1]) : ((mm & 1) ? pr.b[p0 + (mm >> 1)] : pr.a[p0 + (mm >> 1)]);
-  }
+// The product chains of one workgroup over the chunk's steps (the arithmetic described at
+// k_cos_col_prods): this thread's pair reads models ma and mb of gm[] (LDS slots), whose norms as
+// k_cos_col_norms stored them are na and nb, for output c of the chunk; the sum goes to *dst.
+// Shared by K2 (k_cos_col_prods) and its round form (k_cosr_col_prods).
+__device__ __forceinline__ void cos_col_prods_body(const ColChunk& k, const float* const* gm, int nmod, bool live, int c,
+                                                   int ma, int mb, float na, float nb, float* lds, float* dst) {
   ColLoads L;
   col_loads_init(L, gm, nmod, k);
-  const int t = threadIdx.x, g = t / k.Cf, c = t - g * k.Cf;
-  const bool live = g < np && c < k.C;
   const int o = c / k.B, kk = c - o * k.B;
-  const int ma = same_a ? 0 : 2 * g, mb = same_a ? 1 + g : 2 * g + 1;
-  const int64_t n_out = plan[1];
-  float na = 1.f, nb = 1.f;
-  if (live) {
-    const int sa = same_a ? 0 : 2 * (p0 + g), sb = same_a ? 1 + p0 + g : 2 * (p0 + g) + 1;
-    na = nrm[sa * n_out + k.out0 + c];
-    nb = nrm[sb * n_out + k.out0 + c];
-  }
   // a negative norm: its chain has an element outside cos_rdiv's range (k_cos_col_norms)
   const bool checked = __float_as_uint(na) >> 31 || __float_as_uint(nb) >> 31;
   na = fabsf(na);
@@ -3565,7 +3590,39 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs pr, cons
   const int last = (k.I - 1) / kColIc * kColIc;
   for (int gi = e4; gi < k.I; ++gi) ps[0] = __fadd_rn(ps[0], prod(xa[(gi - last) * B], xb[(gi - last) * B]));
   const float v = __fadd_rn(__fadd_rn(__fadd_rn(ps[0], ps[1]), ps[2]), ps[3]);
-  s_all[static_cast<int64_t>(p0 + g) * n_out + k.out0 + c] = __fadd_rn(0.f, v);
+  *dst = __fadd_rn(0.f, v);
+}
+
+// Products of K2: one workgroup per (streamed chunk, group of pairs), see above.
+__global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs pr, const int64_t* __restrict__ plan, int n_seg,
+                                                              int cnt, int same_a, const float* __restrict__ nrm,
+                                                              float* __restrict__ s_all) {
+  __shared__ float lds[kColModels * kColMS];
+  // chunks in the reverse of the norms' order: the first workgroups read what the norms kernel
+  // read last, still in the 256 MiB last-level cache
+  const ColChunk k = col_chunk(plan, n_seg, gridDim.x - 1 - blockIdx.x);
+  const int ppw = same_a ? kColPairs : kColPairs / 2;
+  const int p0 = static_cast<int>(blockIdx.y) * ppw;
+  if (p0 >= cnt) return;
+  const int np = min(ppw, cnt - p0);
+  const int nmod = same_a ? 1 + np : 2 * np;
+  const float* gm[kColModels];
+#pragma unroll
+  for (int m = 0; m < kColModels; ++m) {
+    const int mm = min(m, nmod - 1);
+    gm[m] = same_a ? (mm == 0 ? pr.a[p0] : pr.b[p0 + mm - 1]) : ((mm & 1) ? pr.b[p0 + (mm >> 1)] : pr.a[p0 + (mm >> 1)]);
+  }
+  const int t = threadIdx.x, g = t / k.Cf, c = t - g * k.Cf;
+  const bool live = g < np && c < k.C;
+  const int ma = same_a ? 0 : 2 * g, mb = same_a ? 1 + g : 2 * g + 1;
+  const int64_t n_out = plan[1];
+  float na = 1.f, nb = 1.f;
+  if (live) {
+    const int sa = same_a ? 0 : 2 * (p0 + g), sb = same_a ? 1 + p0 + g : 2 * (p0 + g) + 1;
+    na = nrm[sa * n_out + k.out0 + c];
+    nb = nrm[sb * n_out + k.out0 + c];
+  }
+  cos_col_prods_body(k, gm, nmod, live, c, ma, mb, na, nb, lds, s_all + static_cast<int64_t>(p0 + g) * n_out + k.out0 + c);
 }
 
 // torch's serial full sum of s[0 .. n) (scalar_inner_sum below 8 elements, else
@@ -3623,6 +3680,325 @@ __global__ void k_cosine_finish(int n_seg, const float* __restrict__ means, floa
   float avg = __fadd_rn(0.f, m[0]);
   for (int t = 1; t < n_seg; ++t) avg = __fadd_rn(avg, m[t]);
   out[pair0 + pair] = __fdiv_rn(avg, static_cast<float>(n_seg));
+}
+
+// ------------------------------------------------------------------------------------------
+// K2r: K2 over a round's pair list (tal_cosine_round; table format in tal_agg.h).  The models
+// are rows of one pool segment.  Every clamped norm is computed once per model into
+// nrm[model slot][output] (streamed column chunks: cos_col_norms_body as K2 runs it; the direct
+// kinds: k_cosr_norms, the norm halves of k_cosine_outputs), then every unique unordered pair's
+// products once (streamed: cos_col_prods_body, one workgroup per (chunk, pair group), the group's
+// shared row in LDS slot 0; direct: k_cosr_prods, the product halves of k_cosine_outputs with the
+// norms read from the table), then k_cosine_means / k_cosine_finish over the batch's unique pairs
+// and one gather into the caller's ordered pairs.  No fp32 operation differs from K2's: the value
+// of a pair is symmetric (fl(x/n1) fl(y/n2) commutes, the sums run in the same order), so the
+// unordered pair's value serves both orders.
+// ------------------------------------------------------------------------------------------
+constexpr int kCosrHdr = 8;     // table words: {n_pairs, n_unique, n_models, n_groups, max_group, pool_rows, words, 0}
+constexpr int kCosrGroup = 8;   // pairs per group: kColPairs, the 9-model LDS area of kColModels
+static_assert(kCosrGroup == kColPairs && kCosrGroup + 1 <= kColModels, "a group is one streamed product workgroup");
+
+struct CosrTable {
+  const int32_t* models;  // [n_models] pool rows, ascending
+  const int32_t* uniq;    // [n_unique][2] model slots {a, b}: a = the shared row of the pair's group
+  const int32_t* groups;  // [n_groups][3] {slot of the shared row a, first unique pair, count <= 8}
+  const int32_t* map;     // [n_pairs] unique pair of each ordered pair
+};
+
+__host__ __device__ inline CosrTable cosr_table(const int32_t* t) {
+  CosrTable r;
+  r.models = t + kCosrHdr;
+  r.uniq = r.models + t[2];
+  r.groups = r.uniq + 2 * static_cast<int64_t>(t[1]);
+  r.map = r.groups + 3 * static_cast<int64_t>(t[3]);
+  return r;
+}
+
+// streamed column chunks: every model's norms, model slots = the table's models
+__global__ __launch_bounds__(kColThreads) void k_cosr_col_norms(const float* __restrict__ pool, int64_t ld,
+                                                               const int32_t* __restrict__ table,
+                                                               const int64_t* __restrict__ plan, int n_seg,
+                                                               float* __restrict__ nrm) {
+  __shared__ float lds[kColModels * kColMS];
+  const ColChunk k = col_chunk(plan, n_seg, blockIdx.x);
+  const CosrTable tb = cosr_table(table);
+  const int n_models = table[2];
+  const int nmw = min(kColModels, kColThreads / k.Cf);
+  const int m0 = static_cast<int>(blockIdx.y) * nmw;
+  if (m0 >= n_models) return;
+  const int nmod = min(nmw, n_models - m0);
+  const float* gm[kColModels];
+#pragma unroll
+  for (int m = 0; m < kColModels; ++m) gm[m] = pool + tb.models[m0 + min(m, nmod - 1)] * ld;
+  cos_col_norms_body(k, gm, nmod, m0, plan[1], lds, nrm);
+}
+
+// streamed column chunks: one workgroup per (chunk, pair group g0 + blockIdx.y); LDS slot 0 = the
+// group's shared row, slot 1 + j = the other row of its pair j; pair u's outputs at s_all[u - u0]
+__global__ __launch_bounds__(kColThreads) void k_cosr_col_prods(const float* __restrict__ pool, int64_t ld,
+                                                               const int32_t* __restrict__ table,
+                                                               const int64_t* __restrict__ plan, int n_seg, int g0,
+                                                               int u0, const float* __restrict__ nrm,
+                                                               float* __restrict__ s_all) {
+  __shared__ float lds[kColModels * kColMS];
+  // chunks in the reverse of the norms' order, as k_cos_col_prods takes them
+  const ColChunk k = col_chunk(plan, n_seg, gridDim.x - 1 - blockIdx.x);
+  const CosrTable tb = cosr_table(table);
+  const int32_t* grp = tb.groups + 3 * (g0 + static_cast<int>(blockIdx.y));
+  const int slot_a = grp[0], first = grp[1], np = grp[2];
+  const int nmod = 1 + np;
+  const float* gm[kColModels];
+#pragma unroll
+  for (int m = 0; m < kColModels; ++m) {
+    const int mm = min(m, nmod - 1);
+    gm[m] = pool + tb.models[mm == 0 ? slot_a : tb.uniq[2 * (first + mm - 1) + 1]] * ld;
+  }
+  const int t = threadIdx.x, g = t / k.Cf, c = t - g * k.Cf;
+  const bool live = g < np && c < k.C;
+  const int64_t n_out = plan[1];
+  float na = 1.f, nb = 1.f;
+  if (live) {
+    na = nrm[slot_a * n_out + k.out0 + c];
+    nb = nrm[tb.uniq[2 * (first + g) + 1] * n_out + k.out0 + c];
+  }
+  cos_col_prods_body(k, gm, nmod, live, c, 0, 1 + g, na, nb, lds,
+                     s_all + static_cast<int64_t>(first - u0 + g) * n_out + k.out0 + c);
+}
+
+// XCD-aware order of a (direct chunk, item) grid, as k_cosine_outputs: workgroup 8 k + x takes
+// item k % cnt of direct chunk 8 (k / cnt) + x, so a chunk's items (models, or pair groups, which
+// share rows) run one after another on XCD x and meet in its L2
+__device__ __forceinline__ bool cosr_direct_chunk(const int64_t* __restrict__ plan, int n_seg, int cnt, int64_t n_direct,
+                                                  int* item, const int64_t** ch, const int64_t** sg) {
+  const int64_t kq = blockIdx.x >> 3;
+  *item = static_cast<int>(kq % cnt);
+  const int64_t c = kq / cnt * 8 + (blockIdx.x & 7);
+  if (c >= n_direct) return false;
+  *ch = plan + kCosHdr + kCosSegWords * static_cast<int64_t>(n_seg) + kCosChunkWords * (plan[3] + c);
+  *sg = plan + kCosHdr + kCosSegWords * (*ch)[0];
+  return true;
+}
+
+// direct chunks: one workgroup per (chunk, model): the clamped norms of the chunk's outputs, the
+// norm halves of k_cosine_outputs for one model
+__global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const float* __restrict__ pool, int64_t ld,
+                                                         const int32_t* __restrict__ table,
+                                                         const int64_t* __restrict__ plan, int n_seg,
+                                                         int64_t n_direct, float* __restrict__ nrm) {
+  int slot;
+  const int64_t *ch, *sg;
+  if (!cosr_direct_chunk(plan, n_seg, table[2], n_direct, &slot, &ch, &sg)) return;
+  const int64_t first = ch[1], count = ch[2];
+  const int64_t I = sg[2], B = sg[3];
+  const int kind = static_cast<int>(sg[5]);
+  const float* a = pool + cosr_table(table).models[slot] * ld + sg[0];
+  float* nm = nrm + static_cast<int64_t>(slot) * plan[1] + sg[4];
+  const int tid = threadIdx.x;
+  if (kind == kCosElem) {
+    const int64_t q = first + tid;
+    if (q < first + count) nm[q] = cos_clamp(cos_sqrt_rn(__fmaf_rn(a[q], a[q], 0.f)));
+    return;
+  }
+  if (kind == kCosCol) {  // torch NormTwoOps: fma in index order (loads in batches of 8)
+    const int64_t q = first + tid;
+    if (q >= first + count) return;
+    const int64_t o = q / B, k = q % B;
+    const float* x1 = a + o * I * B + k;
+    float m1 = 0.f;
+    int64_t i0 = 0;
+    for (; i0 + 8 <= I; i0 += 8) {
+      float u1[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) u1[u] = x1[(i0 + u) * B];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) m1 = __fmaf_rn(u1[u], u1[u], m1);
+    }
+    for (int64_t i = i0; i < I; ++i) m1 = __fmaf_rn(x1[i * B], x1[i * B], m1);
+    nm[q] = cos_clamp(cos_sqrt_rn(m1));
+    return;
+  }
+  // kCosRow: 8 threads per row, vector_norm's lane accumulators over whole vectors, the lane
+  // fold in lane order, the tail (groups of 4 as square-then-add, the rest fused)
+  const int lane = tid & 63;
+  const int l = lane & (kCosVw - 1);
+  const int gbase = lane & ~(kCosVw - 1);
+  const int64_t q = first + tid / kCosVw;
+  const bool live = q < first + count;
+  const float* x1 = a + (live ? q : first) * I;
+  const int64_t vec_end = I - I % kCosVw;
+  float m1 = 0.f;
+  if (live) {
+    int64_t d = l;
+    for (; d + 7 * kCosVw < vec_end; d += 8 * kCosVw) {
+      float u1[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) u1[u] = x1[d + u * kCosVw];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) m1 = __fmaf_rn(u1[u], u1[u], m1);
+    }
+    for (; d < vec_end; d += kCosVw) m1 = __fmaf_rn(x1[d], x1[d], m1);
+  }
+  float t1 = __shfl(m1, gbase, 64);  // lane 0 starts the fold
+  for (int j = 1; j < kCosVw; ++j) t1 = __fadd_rn(t1, __shfl(m1, gbase + j, 64));
+  if (l == 0 && live) {
+    int64_t d = vec_end;
+    const int64_t sep = (I - vec_end) / 4 * 4;
+    for (int64_t e = 0; e < sep; ++e, ++d) t1 = __fadd_rn(t1, __fmul_rn(x1[d], x1[d]));
+    for (; d < I; ++d) t1 = __fmaf_rn(x1[d], x1[d], t1);
+    nm[q] = cos_clamp(cos_sqrt_rn(t1));
+  }
+}
+
+// One workgroup's view of a direct chunk and a pair group (k_cosr_prods)
+struct CosrGroup {
+  const float* pool;
+  int64_t ld, n_out, seg_off, out_off;  // the tensor's offset in a row and its first output
+  const int32_t* models;
+  const int32_t* uniq;   // the group's first unique pair
+  const float* nrm;
+  float* s_all;          // the group's first pair's outputs
+};
+__device__ __forceinline__ int cosr_slot_b(const CosrGroup& g, int j) { return g.uniq[2 * j + 1]; }
+__device__ __forceinline__ const float* cosr_b(const CosrGroup& g, int j) {
+  return g.pool + g.models[cosr_slot_b(g, j)] * g.ld + g.seg_off;
+}
+__device__ __forceinline__ const float* cosr_nrm_b(const CosrGroup& g, int j) {
+  return g.nrm + static_cast<int64_t>(cosr_slot_b(g, j)) * g.n_out + g.out_off;
+}
+__device__ __forceinline__ float* cosr_s(const CosrGroup& g, int j) { return g.s_all + j * g.n_out + g.out_off; }
+
+// Row kind, pairs j0 .. j0 + P of the group at once: torch's inner sum of each pair's products (x1
+// / n1) (x2 / n2) as in k_cosine_outputs - scalar_inner_sum below 8 elements, else
+// vectorized_inner_sum: lane l sums elements 8 i + l by row_sum, then the scalar tail from 0, then
+// the lanes in order - with the shared row's quotient x1 / n1 divided once per element for the P
+// pairs (cos_row_sum_pairs).  x1: the shared row's row q, n1 its norm.
+template <int P, int kU>
+__device__ __forceinline__ void cosr_row_pairs(const CosrGroup& g, int j0, const float* x1, float n1, int64_t q,
+                                               int64_t rowoff, int64_t I, bool live, int l, int gbase) {
+  const float* x2[P];
+  float n2[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    x2[p] = cosr_b(g, j0 + p) + rowoff;
+    n2[p] = live ? cosr_nrm_b(g, j0 + p)[q] : 1.f;
+  }
+  auto qa = [&](int64_t i) { return __fdiv_rn(x1[i], n1); };
+  auto qb = [&](int64_t i, int p) { return __fdiv_rn(x2[p][i], n2[p]); };
+  if (I < kCosVw) {  // scalar_inner_sum
+    if (l == 0 && live) {
+      float r[P];
+      cos_row_sum_pairs<P, kU>(qa, qb, I, r);
+#pragma unroll
+      for (int p = 0; p < P; ++p) cosr_s(g, j0 + p)[q] = __fadd_rn(0.f, r[p]);
+    }
+    return;
+  }
+  const int64_t nv = I / kCosVw;
+  float lane_sum[P], tail[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) lane_sum[p] = tail[p] = 0.f;
+  if (live)
+    cos_row_sum_pairs<P, kU>([&](int64_t i) { return qa(i * kCosVw + l); },
+                             [&](int64_t i, int p) { return qb(i * kCosVw + l, p); }, nv, lane_sum);
+  if (l == 0 && live)
+    for (int64_t k2 = nv * kCosVw; k2 < I; ++k2) {
+      const float a = qa(k2);
+#pragma unroll
+      for (int p = 0; p < P; ++p) tail[p] = __fadd_rn(tail[p], __fmul_rn(a, qb(k2, p)));
+    }
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const float fin = cos_group_fold(tail[p], lane_sum[p], gbase);
+    if (l == 0 && live) cosr_s(g, j0 + p)[q] = __fadd_rn(0.f, fin);
+  }
+}
+
+// direct chunks: one workgroup per (chunk, pair group): the product halves of k_cosine_outputs
+// with both norms read from the table.  Row tensors take the group's pairs four (then two, then
+// one) at a time, the shared row's loads and quotients once for them; the element and column
+// kinds (1-D parameters, B >= 32: few and small) take them one after another.
+__global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const float* __restrict__ pool, int64_t ld,
+                                                         const int32_t* __restrict__ table,
+                                                         const int64_t* __restrict__ plan, int n_seg,
+                                                         int64_t n_direct, int g0, int ng, int u0,
+                                                         const float* __restrict__ nrm, float* __restrict__ s_all) {
+  int gi;
+  const int64_t *ch, *sg;
+  if (!cosr_direct_chunk(plan, n_seg, ng, n_direct, &gi, &ch, &sg)) return;
+  const CosrTable tb = cosr_table(table);
+  const int32_t* grp = tb.groups + 3 * (g0 + gi);
+  const int slot_a = grp[0], np = grp[2];
+  CosrGroup g;
+  g.pool = pool;
+  g.ld = ld;
+  g.n_out = plan[1];
+  g.seg_off = sg[0];
+  g.out_off = sg[4];
+  g.models = tb.models;
+  g.uniq = tb.uniq + 2 * grp[1];
+  g.nrm = nrm;
+  g.s_all = s_all + static_cast<int64_t>(grp[1] - u0) * g.n_out;
+  const int64_t first = ch[1], count = ch[2];
+  const int64_t I = sg[2], B = sg[3];
+  const int kind = static_cast<int>(sg[5]);
+  const float* a = pool + tb.models[slot_a] * ld + sg[0];
+  const float* nma = nrm + static_cast<int64_t>(slot_a) * g.n_out + sg[4];
+  const int tid = threadIdx.x;
+  if (kind == kCosElem) {
+    const int64_t q = first + tid;
+    if (q >= first + count) return;
+    const float qa = __fdiv_rn(a[q], nma[q]);
+    for (int j = 0; j < np; ++j)
+      cosr_s(g, j)[q] = __fadd_rn(0.f, __fmul_rn(qa, __fdiv_rn(cosr_b(g, j)[q], cosr_nrm_b(g, j)[q])));
+    return;
+  }
+  if (kind == kCosCol) {
+    const int64_t q = first + tid;
+    if (q >= first + count) return;
+    const int64_t o = q / B, k = q % B;
+    const float* x1 = a + o * I * B + k;
+    const float n1 = nma[q];
+#pragma nounroll
+    for (int j = 0; j < np; ++j) {
+      const float* x2 = cosr_b(g, j) + o * I * B + k;
+      const float n2 = cosr_nrm_b(g, j)[q];
+      auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(x1[i * B], n1), __fdiv_rn(x2[i * B], n2)); };
+      float r;
+      if (B >= kCosVw && k < B / 32 * 32) {  // columns in chunks of 32 share one cascade
+        float c[1];
+        cos_multi_row<1>([&](int64_t i, int) { return prod(i); }, I, c);
+        r = c[0];
+      } else {  // chunks of 8 and single columns: row_sum per column
+        r = cos_row_sum(prod, I);
+      }
+      cosr_s(g, j)[q] = __fadd_rn(0.f, r);
+    }
+    return;
+  }
+  // kCosRow: 8 threads per row (torch's vector lanes)
+  const int lane = tid & 63;
+  const int l = lane & (kCosVw - 1);
+  const int gbase = lane & ~(kCosVw - 1);
+  const int64_t q = first + tid / kCosVw;
+  const bool live = q < first + count;
+  const int64_t rowoff = (live ? q : first) * I;
+  const float* x1 = a + rowoff;
+  const float n1 = live ? nma[q] : 1.f;
+  int j = 0;
+#pragma nounroll
+  for (; j + 4 <= np; j += 4) cosr_row_pairs<4, 2>(g, j, x1, n1, q, rowoff, I, live, l, gbase);
+  if (j + 2 <= np) {
+    cosr_row_pairs<2, 4>(g, j, x1, n1, q, rowoff, I, live, l, gbase);
+    j += 2;
+  }
+  if (j < np) cosr_row_pairs<1, 8>(g, j, x1, n1, q, rowoff, I, live, l, gbase);
+}
+
+// every ordered pair's result from its unique pair
+__global__ void k_cosr_gather(const int32_t* __restrict__ table, const float* __restrict__ res,
+                              float* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < table[0]) out[j] = res[cosr_table(table).map[j]];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4851,6 +5227,215 @@ int32_t tal_cosine_params(const float* const* a_ptrs_host, const float* const* b
   return check_launch("tal_cosine_params");
 }
 
+// ---- K2r: the round form (table format in tal_agg.h) ------------------------------------------
+int64_t tal_cosine_round_words(int32_t n_pairs) {
+  if (n_pairs <= 0) return -1;
+  // at most 2 n models, n unique pairs (2 words), n groups (3 words) and the n-word map
+  return kCosrHdr + 8 * static_cast<int64_t>(n_pairs);
+}
+
+int32_t tal_cosine_round_build(const int32_t* row_a_host, const int32_t* row_b_host, int32_t n_pairs,
+                               int32_t pool_rows, int32_t* table_host, int64_t capacity_words,
+                               tal_cosine_round_info* info) {
+  if (!info) return fail(TAL_ERR_INVALID, "tal_cosine_round_build: null info");
+  memset(info, 0, sizeof(*info));
+  if (n_pairs <= 0) return fail(TAL_ERR_INVALID, "tal_cosine_round_build: n_pairs must be positive");
+  if (!row_a_host || !row_b_host) return fail(TAL_ERR_INVALID, "tal_cosine_round_build: null row array");
+  if (pool_rows <= 0) return fail(TAL_ERR_INVALID, "tal_cosine_round_build: pool_rows must be positive");
+  std::vector<int32_t> models;
+  std::vector<std::pair<int32_t, int32_t>> uniq;
+  models.reserve(2 * static_cast<size_t>(n_pairs));
+  uniq.reserve(static_cast<size_t>(n_pairs));
+  for (int32_t j = 0; j < n_pairs; ++j) {
+    const int32_t a = row_a_host[j], b = row_b_host[j];
+    if (a < 0 || a >= pool_rows || b < 0 || b >= pool_rows)
+      return fail(TAL_ERR_INVALID, "tal_cosine_round_build: pair " + std::to_string(j) + " has a row outside [0, " +
+                                       std::to_string(pool_rows) + ")");
+    models.push_back(a);
+    models.push_back(b);
+    uniq.emplace_back(std::min(a, b), std::max(a, b));
+  }
+  std::sort(models.begin(), models.end());
+  models.erase(std::unique(models.begin(), models.end()), models.end());
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  auto slot = [&](int32_t row) {
+    return static_cast<int32_t>(std::lower_bound(models.begin(), models.end(), row) - models.begin());
+  };
+  // Groups: every unique pair is given to one of its two rows, the group's shared row.  Greedy:
+  // the row with the most pairs still to place (8 or more all count as 8: they fill a group; ties
+  // go to the smaller row) takes up to kCosrGroup of them, in ascending order of the pair.  A
+  // regular graph's pairs then sit in fuller groups (config 3: 256 pairs in 49 groups; with
+  // the smaller row always the shared one, 59).  order[]: the unique pairs in table order.
+  const size_t nu = uniq.size(), nm = models.size();
+  std::vector<std::vector<int32_t>> inc(nm);  // a model's unique pairs
+  for (size_t u = 0; u < nu; ++u) {
+    inc[static_cast<size_t>(slot(uniq[u].first))].push_back(static_cast<int32_t>(u));
+    if (uniq[u].second != uniq[u].first) inc[static_cast<size_t>(slot(uniq[u].second))].push_back(static_cast<int32_t>(u));
+  }
+  std::vector<int32_t> left(nm), pos(nm, 0), order, index(nu, -1), groups;
+  for (size_t m = 0; m < nm; ++m) left[m] = static_cast<int32_t>(inc[m].size());
+  order.reserve(nu);
+  int32_t max_group = 0;
+  while (order.size() < nu) {
+    size_t best = nm;
+    for (size_t m = 0; m < nm; ++m)
+      if (left[m] > 0 && (best == nm || std::min(left[m], kCosrGroup) > std::min(left[best], kCosrGroup))) best = m;
+    const int32_t first = static_cast<int32_t>(order.size());
+    int32_t cnt = 0;
+    for (int32_t& k = pos[best]; k < static_cast<int32_t>(inc[best].size()) && cnt < kCosrGroup; ++k) {
+      const int32_t u = inc[best][static_cast<size_t>(k)];
+      if (index[static_cast<size_t>(u)] >= 0) continue;  // placed by its other row
+      index[static_cast<size_t>(u)] = static_cast<int32_t>(order.size());
+      order.push_back(u);
+      ++cnt;
+      --left[static_cast<size_t>(slot(uniq[static_cast<size_t>(u)].first))];
+      if (uniq[static_cast<size_t>(u)].second != uniq[static_cast<size_t>(u)].first)
+        --left[static_cast<size_t>(slot(uniq[static_cast<size_t>(u)].second))];
+    }
+    groups.push_back(static_cast<int32_t>(best));
+    groups.push_back(first);
+    groups.push_back(cnt);
+    max_group = std::max(max_group, cnt);
+  }
+  const int64_t words = kCosrHdr + static_cast<int64_t>(models.size()) + 2 * static_cast<int64_t>(uniq.size()) +
+                        static_cast<int64_t>(groups.size()) + n_pairs;
+  info->n_pairs = n_pairs;
+  info->n_unique = static_cast<int32_t>(uniq.size());
+  info->n_models = static_cast<int32_t>(models.size());
+  info->n_groups = static_cast<int32_t>(groups.size() / 3);
+  info->max_group = max_group;
+  info->pool_rows = pool_rows;
+  info->words = words;
+  if (!table_host || capacity_words < words)
+    return fail(TAL_ERR_CAPACITY, "tal_cosine_round_build: the table needs " + std::to_string(words) + " words");
+  int32_t* t = table_host;
+  t[0] = n_pairs;
+  t[1] = info->n_unique;
+  t[2] = info->n_models;
+  t[3] = info->n_groups;
+  t[4] = max_group;
+  t[5] = pool_rows;
+  t[6] = static_cast<int32_t>(words);
+  t[7] = 0;
+  int32_t* w = t + kCosrHdr;
+  for (int32_t m : models) *w++ = m;
+  {
+    size_t k = 0;  // the pairs of group g are order[k ..], its shared row first
+    for (size_t g = 0; g < groups.size(); g += 3)
+      for (int32_t e = 0; e < groups[g + 2]; ++e, ++k) {
+        const auto& p = uniq[static_cast<size_t>(order[k])];
+        const int32_t sa = slot(p.first), sb = slot(p.second);
+        *w++ = groups[g];
+        *w++ = sa == groups[g] ? sb : sa;
+      }
+  }
+  for (int32_t g : groups) *w++ = g;
+  for (int32_t j = 0; j < n_pairs; ++j) {
+    const std::pair<int32_t, int32_t> key(std::min(row_a_host[j], row_b_host[j]), std::max(row_a_host[j], row_b_host[j]));
+    *w++ = index[static_cast<size_t>(std::lower_bound(uniq.begin(), uniq.end(), key) - uniq.begin())];
+  }
+  g_err.clear();
+  return TAL_OK;
+}
+
+// does info describe table_host?
+static bool cosr_info_matches(const int32_t* t, const tal_cosine_round_info* info) {
+  return t && info && info->n_pairs > 0 && t[0] == info->n_pairs && t[1] == info->n_unique && t[2] == info->n_models &&
+         t[3] == info->n_groups && t[4] == info->max_group && t[5] == info->pool_rows && t[6] == info->words &&
+         info->n_unique > 0 && info->n_models > 0 && info->n_groups > 0 && info->max_group > 0 &&
+         info->max_group <= kCosrGroup;
+}
+
+// batches of whole groups holding at most batch_pairs unique pairs, in group order: the groups
+// [g, *ge) of the batch that starts at group g, and its pairs
+static int32_t cosr_batch(const int32_t* groups, int32_t n_groups, int32_t batch_pairs, int32_t g, int32_t* ge) {
+  int32_t cnt = 0, e = g;
+  while (e < n_groups && cnt + groups[3 * e + 2] <= batch_pairs) cnt += groups[3 * e++ + 2];
+  *ge = e;
+  return cnt;
+}
+
+constexpr int32_t kCosrMaxBatch = 32768;  // unique pairs per batch: k_cosine_means' grid.y
+
+static int64_t cosr_scratch_need(const int64_t* plan_host, const tal_cosine_round_info* info, int64_t batch_pairs) {
+  // norms per model, per batch pair its outputs and per-tensor means, a result per unique pair
+  return static_cast<int64_t>(sizeof(float)) *
+         (static_cast<int64_t>(info->n_models) * plan_host[1] + batch_pairs * (plan_host[1] + plan_host[0]) + info->n_unique);
+}
+
+int64_t tal_cosine_round_scratch_bytes(const int64_t* plan_host, const int32_t* table_host,
+                                       tal_cosine_round_info* info, int64_t budget_bytes) {
+  if (!plan_host || plan_host[0] <= 0 || plan_host[1] <= 0 || !cosr_info_matches(table_host, info)) return -1;
+  const int64_t fixed = cosr_scratch_need(plan_host, info, 0);
+  const int64_t per = static_cast<int64_t>(sizeof(float)) * (plan_host[1] + plan_host[0]);
+  if (budget_bytes < fixed) return -1;
+  int64_t batch = std::min<int64_t>(std::min<int64_t>(info->n_unique, kCosrMaxBatch), (budget_bytes - fixed) / per);
+  if (batch < info->max_group) return -1;  // not even one (largest) group fits
+  const int32_t* groups = cosr_table(table_host).groups;
+  int32_t n_batches = 0, largest = 0;
+  for (int32_t g = 0, ge = 0; g < info->n_groups; g = ge, ++n_batches)
+    largest = std::max(largest, cosr_batch(groups, info->n_groups, static_cast<int32_t>(batch), g, &ge));
+  info->batch_pairs = largest;  // the same walk with the largest batch's size gives the same batches
+  info->n_batches = n_batches;
+  return cosr_scratch_need(plan_host, info, largest);
+}
+
+int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
+                         int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
+                         const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
+                         float* out_dev, void* stream) {
+  if (!pool || !plan_dev || !plan_host || !table_dev || !table_host || !info || !scratch || !out_dev || n_chunks <= 0 ||
+      plan_host[0] <= 0 || plan_host[1] <= 0 || plan_host[3] < 0 || plan_host[3] > n_chunks)
+    return fail(TAL_ERR_INVALID, "tal_cosine_round: bad arguments");
+  if (!cosr_info_matches(table_host, info))
+    return fail(TAL_ERR_INVALID, "tal_cosine_round: info does not describe the table");
+  if (info->batch_pairs < info->max_group || info->batch_pairs > kCosrMaxBatch)
+    return fail(TAL_ERR_INVALID, "tal_cosine_round: no batch size (call tal_cosine_round_scratch_bytes first)");
+  if (scratch_bytes < cosr_scratch_need(plan_host, info, info->batch_pairs))
+    return fail(TAL_ERR_INVALID, "tal_cosine_round: scratch too small");
+  const int n_seg = static_cast<int>(plan_host[0]);
+  const int64_t n_out = plan_host[1];
+  int64_t extent = 0;  // a row's elements the plan reads
+  for (int t = 0; t < n_seg; ++t) {
+    const int64_t* sg = plan_host + kCosHdr + kCosSegWords * static_cast<int64_t>(t);
+    extent = std::max(extent, sg[0] + sg[1] * sg[2] * sg[3]);
+  }
+  if (ld < extent) return fail(TAL_ERR_INVALID, "tal_cosine_round: row pitch shorter than the plan's parameters");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int32_t* groups = cosr_table(table_host).groups;
+  float* nrm = static_cast<float*>(scratch);
+  float* s_all = nrm + static_cast<int64_t>(info->n_models) * n_out;
+  float* means = s_all + static_cast<int64_t>(info->batch_pairs) * n_out;
+  float* res = means + static_cast<int64_t>(info->batch_pairs) * n_seg;
+  const int64_t n_staged = plan_host[3], n_direct = n_chunks - n_staged;
+  const int64_t direct8 = (n_direct + 7) / 8 * 8;
+  if (direct8 * std::max(info->n_models, info->n_groups) > 0x7fffffff)
+    return fail(TAL_ERR_INVALID, "tal_cosine_round: too many workgroups");
+  // every launch on the caller's stream: a whole round fills the GPU without a side stream
+  if (n_staged > 0)
+    k_cosr_col_norms<<<dim3(static_cast<unsigned>(n_staged), (info->n_models + 7) / 8), kColThreads, 0, s>>>(
+        pool, ld, table_dev, plan_dev, n_seg, nrm);
+  if (n_direct > 0)
+    k_cosr_norms<<<static_cast<unsigned>(direct8 * info->n_models), kCosBlock, 0, s>>>(pool, ld, table_dev, plan_dev,
+                                                                                      n_seg, n_direct, nrm);
+  for (int32_t g = 0, ge = 0; g < info->n_groups; g = ge) {
+    const int32_t cnt = cosr_batch(groups, info->n_groups, info->batch_pairs, g, &ge);
+    if (cnt <= 0) return fail(TAL_ERR_INVALID, "tal_cosine_round: a group exceeds the batch");
+    const int32_t ng = ge - g, u0 = groups[3 * g + 1];
+    if (n_staged > 0)
+      k_cosr_col_prods<<<dim3(static_cast<unsigned>(n_staged), ng), kColThreads, 0, s>>>(pool, ld, table_dev, plan_dev,
+                                                                                        n_seg, g, u0, nrm, s_all);
+    if (n_direct > 0)
+      k_cosr_prods<<<static_cast<unsigned>(direct8 * ng), kCosBlock, 0, s>>>(pool, ld, table_dev, plan_dev, n_seg,
+                                                                            n_direct, g, ng, u0, nrm, s_all);
+    k_cosine_means<<<dim3(n_seg, cnt), 64, 0, s>>>(plan_dev, n_seg, s_all, means);
+    k_cosine_finish<<<cnt, 64, 0, s>>>(n_seg, means, res, u0);
+  }
+  k_cosr_gather<<<(info->n_pairs + 255) / 256, 256, 0, s>>>(table_dev, res, out_dev);
+  return check_launch("tal_cosine_round");
+}
+
 
 int64_t tal_prox_plan_words(const int64_t* seg_host, int32_t n_seg) {
   if (!seg_host || n_seg <= 0) return -1;
@@ -5591,6 +6176,31 @@ int32_t tal_host_cosine(const float* const* a_host, const float* const* b_host, 
     out[j] = avg / static_cast<float>(n_seg);
   }
   g_err.clear();
+  return TAL_OK;
+}
+
+int32_t tal_host_cosine_round(const float* pool_host, int64_t ld, const int64_t* plan_host,
+                              const int32_t* table_host, const tal_cosine_round_info* info, float* out) {
+  if (!pool_host || !plan_host || !out || ld <= 0 || plan_host[0] <= 0)
+    return fail(TAL_ERR_INVALID, "tal_host_cosine_round: bad arguments");
+  if (!cosr_info_matches(table_host, info))
+    return fail(TAL_ERR_INVALID, "tal_host_cosine_round: info does not describe the table");
+  for (int64_t t = 0; t < plan_host[0]; ++t) {
+    const int64_t* sg = plan_host + kCosHdr + kCosSegWords * t;
+    if (ld < sg[0] + sg[1] * sg[2] * sg[3])
+      return fail(TAL_ERR_INVALID, "tal_host_cosine_round: row pitch shorter than the plan's parameters");
+  }
+  // every unique pair once through tal_host_cosine, then each ordered pair from its unique pair
+  const CosrTable tb = cosr_table(table_host);
+  std::vector<const float*> a(static_cast<size_t>(info->n_unique)), b(a.size());
+  for (int32_t u = 0; u < info->n_unique; ++u) {
+    a[static_cast<size_t>(u)] = pool_host + tb.models[tb.uniq[2 * u]] * ld;
+    b[static_cast<size_t>(u)] = pool_host + tb.models[tb.uniq[2 * u + 1]] * ld;
+  }
+  std::vector<float> res(a.size());
+  const int32_t rc = tal_host_cosine(a.data(), b.data(), info->n_unique, plan_host, res.data());
+  if (rc != TAL_OK) return rc;
+  for (int32_t j = 0; j < info->n_pairs; ++j) out[j] = res[static_cast<size_t>(tb.map[j])];
   return TAL_OK;
 }
 

@@ -1131,6 +1131,109 @@ def host_cosine(a_list: Sequence[torch.Tensor], b_list: Sequence[torch.Tensor], 
     return out
 
 
+# K2r: the cosine similarities of a whole round in one call (tal_agg.h K2r)
+COSINE_ROUND_BUDGET = 256 << 20  # default scratch budget in bytes: config 3's round takes 141 MB, one batch
+
+
+@dataclass
+class CosineRound:
+    """A round's ordered pairs of pool rows as tal_cosine_round_build's table."""
+    n_pairs: int
+    pool_rows: int
+    host: np.ndarray
+    info: "_lib.CosineRoundInfo"
+    device: Optional[torch.Tensor] = None
+
+
+def build_cosine_round(pairs: Sequence[Sequence[int]], pool_rows: int) -> CosineRound:
+    """pairs: (row_a, row_b) per ordered pair, rows of a pool of `pool_rows` rows.  The table holds
+    the distinct rows, the distinct unordered pairs in groups that share a row, and the map from
+    each ordered pair to its unordered pair."""
+    arr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(arr) == 0:
+        raise ValueError("cosine round: no pairs")
+    if arr.min() < 0 or arr.max() >= int(pool_rows):
+        raise ValueError(f"cosine round: a row outside [0, {int(pool_rows)})")
+    ra = np.ascontiguousarray(arr[:, 0], dtype=np.int32)
+    rb = np.ascontiguousarray(arr[:, 1], dtype=np.int32)
+    L = _lib.load()
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    words = L.tal_cosine_round_words(len(arr))
+    blob = np.zeros(words, dtype=np.int32)
+    info = _lib.CosineRoundInfo()
+    check(L.tal_cosine_round_build(ra.ctypes.data_as(P32), rb.ctypes.data_as(P32), len(arr), int(pool_rows),
+                                   blob.ctypes.data_as(P32), words, ctypes.byref(info)))
+    return CosineRound(n_pairs=len(arr), pool_rows=int(pool_rows), host=np.ascontiguousarray(blob[: info.words]),
+                       info=info)
+
+
+def _cosine_round_args(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan, what: str):
+    if not isinstance(pool_f32, torch.Tensor):
+        raise TypeError(f"{what}: the pool must be a torch.Tensor")
+    if pool_f32.dtype != torch.float32 or pool_f32.dim() != 2 or pool_f32.shape[0] < 1 or (
+            pool_f32.shape[1] > 1 and pool_f32.stride(1) != 1):
+        raise ValueError(f"{what}: the pool must be a 2-D float32 tensor with unit column stride")
+    ld = int(pool_f32.stride(0)) if pool_f32.shape[0] > 1 else int(pool_f32.shape[1])
+    seg = plan.host[4: 4 + 7 * plan.n_seg].reshape(-1, 7)
+    extent = int((seg[:, 0] + seg[:, 1] * seg[:, 2] * seg[:, 3]).max())
+    if pool_f32.shape[1] < extent or ld < pool_f32.shape[1]:
+        raise ValueError(f"{what}: the pool's rows ({pool_f32.shape[1]} floats, pitch {ld}) are shorter than the "
+                         f"plan's parameters ({extent})")
+    table = pairs_or_table if isinstance(pairs_or_table, CosineRound) else build_cosine_round(
+        pairs_or_table, pool_f32.shape[0])
+    if table.pool_rows > pool_f32.shape[0]:
+        raise ValueError(f"{what}: the table was built for {table.pool_rows} rows, the pool has {pool_f32.shape[0]}")
+    return ld, table
+
+
+def cosine_round(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan, budget_bytes: int = COSINE_ROUND_BUDGET,
+                 stream=None) -> torch.Tensor:
+    """K2r: cosine_similarity(pool[a_j], pool[b_j]) for every ordered pair of a round, rows of one
+    device pool f32[rows, ld]: every norm once per model, every unordered pair once, one launch
+    sequence on the current (or given) stream.  Bit for bit `cosine` on the same pairs.
+    pairs_or_table: (row_a, row_b) pairs, or a CosineRound of build_cosine_round.  budget_bytes
+    bounds the scratch (the unique pairs run in batches under it)."""
+    if pool_f32.device.type != "cuda":
+        raise ValueError(f"cosine_round: the pool must be a GPU tensor (got {pool_f32.device}); "
+                         "host_cosine_round is the host form")
+    ld, table = _cosine_round_args(pool_f32, pairs_or_table, plan, "cosine_round")
+    dev = pool_f32.device
+    if plan.device is None or plan.device.device != dev:
+        plan.device = torch.from_numpy(plan.host).to(dev)
+    if table.device is None or table.device.device != dev:
+        table.device = torch.from_numpy(table.host).to(dev)
+    L = _lib.load()
+    hp = plan.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    ht = table.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    need = int(L.tal_cosine_round_scratch_bytes(hp, ht, ctypes.byref(table.info), int(budget_bytes)))
+    if need < 0:
+        raise ValueError(f"cosine_round: budget_bytes={int(budget_bytes)} does not hold the norm table and one pair group")
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(table.n_pairs, dtype=torch.float32, device=dev)
+    check(L.tal_cosine_round(ctypes.c_void_p(pool_f32.data_ptr()), ld, ctypes.c_void_p(plan.device.data_ptr()), hp,
+                             plan.n_chunks, ctypes.c_void_p(table.device.data_ptr()), ht, ctypes.byref(table.info),
+                             ctypes.c_void_p(scratch.data_ptr()), need, ctypes.c_void_p(out.data_ptr()),
+                             _stream(dev, stream)))
+    if stream is not None:  # the scratch is released to the current stream's allocator pool
+        scratch.record_stream(stream)
+    return out
+
+
+def host_cosine_round(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan) -> torch.Tensor:
+    """cosine_round on a CPU pool (tal_host_cosine_round: tal_host_cosine's arithmetic, every
+    unordered pair once), for a process that sees no GPU."""
+    if pool_f32.device.type != "cpu":
+        raise ValueError("host_cosine_round: the pool must be a CPU tensor")
+    ld, table = _cosine_round_args(pool_f32, pairs_or_table, plan, "host_cosine_round")
+    out = torch.empty(table.n_pairs, dtype=torch.float32)
+    L = _lib.load()
+    check(L.tal_host_cosine_round(ctypes.c_void_p(pool_f32.data_ptr()), ld,
+                                  plan.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                  table.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(table.info),
+                                  ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # Synthetic pool rows (benchmark / full-size test inputs)
 # ------------------------------------------------------------------------------------------

@@ -46,12 +46,7 @@ def _flat(models: Sequence[nn.Module], layout, device) -> List[torch.Tensor]:
     return out
 
 
-def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
-    """[cosine_similarity(model, o) for o in others] in one kernel launch."""
-    if not others:
-        return []
-    layout = layout_of_module(model)
-    names = _param_names(model)
+def _plan_for(layout, names: Sequence[str]) -> ops.CosinePlan:
     # a tensor mean over >= 32768 outputs follows torch's parallel order for this process's
     # intra-op thread count, as the reference's own call would (tal_agg.h K2).  The plan holds
     # at most 1024 (tal_cosine_plan_set_threads); a process with more intra-op threads gets
@@ -63,6 +58,33 @@ def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
     if plan is None:
         plan = ops.build_cosine_plan(layout.param_segments(names), threads=threads)
         _plans[key] = plan
+    return plan
+
+
+def cosine_round(pool, pairs: Sequence[Tuple[int, int]], model: nn.Module) -> List[float]:
+    """[cosine_similarity(row a, row b) for (a, b) in pairs] over the rows of one ModelPool, a
+    whole round's pairs in one launch sequence and one copy to the host (K2r, tal_agg.h): every
+    model's norms once, every unordered pair once, the values bit for bit cosine_pairs'.
+    model: any model of the pool's layout (its named_parameters say which entries count).  With
+    no GPU visible the pool is a host pool and the library's host form runs."""
+    if not len(pairs):
+        return []
+    layout = pool.layout
+    if layout_of_module(model) != layout:
+        raise ValueError("cosine_round: the model does not have the pool's layout")
+    plan = _plan_for(layout, _param_names(model))
+    if not torch.cuda.is_available():
+        return [float(x) for x in ops.host_cosine_round(pool.f32, pairs, plan).tolist()]
+    with torch.cuda.device(pool.device):
+        return [float(x) for x in ops.cosine_round(pool.f32, pairs, plan).cpu().tolist()]
+
+
+def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
+    """[cosine_similarity(model, o) for o in others] in one kernel launch."""
+    if not others:
+        return []
+    layout = layout_of_module(model)
+    plan = _plan_for(layout, _param_names(model))
     if not torch.cuda.is_available():  # no GPU (config 1's setting): the library's host K2
         flats = _host_flat([model, *others], layout)
         return [float(x) for x in ops.host_cosine([flats[0]] * len(others), flats[1:], plan).tolist()]
