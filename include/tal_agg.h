@@ -335,6 +335,28 @@ int32_t tal_cosine_params(const float* const* a_ptrs_host, const float* const* b
                           int32_t n_pairs, const int64_t* plan_dev, const int64_t* plan_host,
                           int32_t n_chunks, void* scratch, float* out_dev, void* stream);
 
+/* ---- K2 on bf16 models (ABI 27) -------------------------------------------------------------
+ * The reference has no bf16 path for cosine_similarity, so the definition is this project's:
+ *
+ *   the cosine similarity of two bf16 models is K2's fp32 result for the two models with every
+ *   parameter widened exactly to fp32 - bit for bit what the reference's
+ *   cosine_similarity(m1.float(), m2.float()) returns, for the plan's thread word.
+ *
+ * Only the loads differ: a bf16 bit pattern u becomes the fp32 value with bits u << 16.  Every
+ * fp32 operation and its order stay K2's (vector_norm's FMA chains, the 1e-6 clamp, the two
+ * quotients, the cascade sums, the per-tensor mean under the plan's thread word, the in-order
+ * average over tensors), and the result is fp32.  It is not an op-by-op emulation of torch's bf16
+ * CPU kernels: a result with 8 mantissa bits would make sim_centrality_module_avg's
+ * least-similar-neighbor choice (decentralized_client.py:511-516) tie-prone, and those kernels'
+ * reduction orders are not the fp32 ones K2 pins.
+ *
+ * The *_bf16 entry points (here, K2r's and the host forms' below) are their fp32 twins with
+ * `const uint16_t*` models / pool (bf16 bit patterns; offsets and ld in elements, rows 2-byte
+ * aligned): plans, round tables, scratch sizes, results and error codes are shared. */
+int32_t tal_cosine_params_bf16(const uint16_t* const* a_ptrs_host, const uint16_t* const* b_ptrs_host,
+                               int32_t n_pairs, const int64_t* plan_dev, const int64_t* plan_host,
+                               int32_t n_chunks, void* scratch, float* out_dev, void* stream);
+
 /* ---- K2r: K2 over a whole round's pair list (ABI 26) --------------------------------------
  * The `*_sim` strategies need the cosine of every client with every neighbor.  In a batched
  * round all models are rows of one pool segment (row r at pool + r ld), and the pairs of a round
@@ -394,6 +416,11 @@ int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev,
                          int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
                          const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
                          float* out_dev, void* stream);
+/* K2r over a bf16 pool segment (ABI 27; semantics: "K2 on bf16 models" above). */
+int32_t tal_cosine_round_bf16(const uint16_t* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
+                              int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
+                              const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
+                              float* out_dev, void* stream);
 
 /* ---- FedProx proximal term ------------------------------------------------
  * Reference: local_train, tasks.py:277-286: loss += (prox_coeff / 2) * sum_t sum_p
@@ -447,6 +474,12 @@ int32_t tal_host_cosine(const float* const* a_host, const float* const* b_host, 
  * tal_host_cosine's arithmetic, out[j] for each ordered pair. */
 int32_t tal_host_cosine_round(const float* pool_host, int64_t ld, const int64_t* plan_host,
                               const int32_t* table_host, const tal_cosine_round_info* info, float* out);
+/* The two host forms on bf16 rows / a bf16 host pool (ABI 27; "K2 on bf16 models" above): bit for
+ * bit tal_cosine_params_bf16 / tal_cosine_round_bf16. */
+int32_t tal_host_cosine_bf16(const uint16_t* const* a_host, const uint16_t* const* b_host, int32_t n_pairs,
+                             const int64_t* plan_host, float* out);
+int32_t tal_host_cosine_round_bf16(const uint16_t* pool_host, int64_t ld, const int64_t* plan_host,
+                                   const int32_t* table_host, const tal_cosine_round_info* info, float* out);
 
 /* ---- Synthetic pool rows (test / benchmark inputs) --------------------------
  * Not a reference interface: the reference trains its models; the benchmark and the full-size

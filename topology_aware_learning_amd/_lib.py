@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 EXPORTED = (
     "tal_last_error",
@@ -51,10 +51,12 @@ EXPORTED = (
     "tal_cosine_plan_set_threads",
     "tal_cosine_scratch_bytes",
     "tal_cosine_params",
+    "tal_cosine_params_bf16",
     "tal_cosine_round_words",
     "tal_cosine_round_build",
     "tal_cosine_round_scratch_bytes",
     "tal_cosine_round",
+    "tal_cosine_round_bf16",
     "tal_prox_plan_words",
     "tal_prox_plan_build",
     "tal_prox_scratch_bytes",
@@ -72,7 +74,9 @@ EXPORTED = (
     "tal_host_agg_i64",
     "tal_host_agg_bf16",
     "tal_host_cosine",
+    "tal_host_cosine_bf16",
     "tal_host_cosine_round",
+    "tal_host_cosine_round_bf16",
 )
 
 
@@ -184,10 +188,15 @@ _SIGS = {
     "tal_cosine_plan_set_threads": (_I32, [_PI64, _I32]),
     "tal_cosine_scratch_bytes": (_I64, [_PI64, _I32]),
     "tal_cosine_params": (_I32, [_PP, _PP, _I32, _P, _PI64, _I32, _P, _P, _P]),
+    "tal_cosine_params_bf16": (_I32, [_PP, _PP, _I32, _P, _PI64, _I32, _P, _P, _P]),
     "tal_cosine_round_words": (_I64, [_I32]),
     "tal_cosine_round_build": (_I32, [_PI32, _PI32, _I32, _I32, _PI32, _I64, ctypes.POINTER(CosineRoundInfo)]),
     "tal_cosine_round_scratch_bytes": (_I64, [_PI64, _PI32, ctypes.POINTER(CosineRoundInfo), _I64]),
     "tal_cosine_round": (
+        _I32,
+        [_P, _I64, _P, _PI64, _I32, _P, _PI32, ctypes.POINTER(CosineRoundInfo), _P, _I64, _P, _P],
+    ),
+    "tal_cosine_round_bf16": (
         _I32,
         [_P, _I64, _P, _PI64, _I32, _P, _PI32, ctypes.POINTER(CosineRoundInfo), _P, _I64, _P, _P],
     ),
@@ -209,6 +218,8 @@ _SIGS = {
     "tal_host_agg_bf16": (_I32, [_PP, _PD, _I32, _P, _I64, _I32]),
     "tal_host_cosine": (_I32, [_PP, _PP, _I32, _PI64, _P]),
     "tal_host_cosine_round": (_I32, [_P, _I64, _PI64, _PI32, ctypes.POINTER(CosineRoundInfo), _P]),
+    "tal_host_cosine_bf16": (_I32, [_PP, _PP, _I32, _PI64, _P]),
+    "tal_host_cosine_round_bf16": (_I32, [_P, _I64, _PI64, _PI32, ctypes.POINTER(CosineRoundInfo), _P]),
 }
 
 _lock = threading.Lock()

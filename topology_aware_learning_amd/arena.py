@@ -125,14 +125,34 @@ class StateLayout:
     def flatten_cat(self, sd: Mapping[str, torch.Tensor], seg: str) -> List[torch.Tensor]:
         return [sd[e.name].reshape(-1) for e in self.entries if e.seg == seg and e.alias_of is None]
 
+    def param_segment_kind(self, param_names: Sequence[str]) -> str:
+        """"f32" or "b16": the segment every one of the parameters lies in (the cosine kernels
+        read one segment of a row).  A model with parameters in both - or in neither - raises
+        NotImplementedError; `model.to(torch.bfloat16)` converts every floating parameter, so a
+        bf16 model is all "b16"."""
+        first: Dict[str, str] = {}
+        for name in param_names:
+            first.setdefault(self.by_name[name].seg, name)
+        for seg in first:
+            if seg not in ("f32", "b16"):
+                raise NotImplementedError(f"parameter {first[seg]} is neither fp32 nor bf16")
+        if len(first) > 1:
+            raise NotImplementedError(
+                f"cosine similarity needs parameters of one dtype: {first['f32']} is fp32, {first['b16']} is bf16")
+        if not first:
+            raise ValueError("no parameters")
+        return next(iter(first))
+
     def param_segments(self, param_names: Sequence[str]) -> List[Tuple[int, int, int, int]]:
         """(offset, A, I, B) of each parameter for the cosine kernel: nn.CosineSimilarity(dim=1)
-        on the tensor, 1-D tensors unsqueezed to [n, 1] (decentralized_client.py:674-678)."""
+        on the tensor, 1-D tensors unsqueezed to [n, 1] (decentralized_client.py:674-678).  The
+        offsets are elements into the one segment all the parameters lie in, fp32 or bf16
+        (param_segment_kind)."""
+        if len(param_names):
+            self.param_segment_kind(param_names)
         segs = []
         for name in param_names:
             e = self.by_name[name]
-            if e.seg != "f32":
-                raise NotImplementedError(f"parameter {name} is not fp32")
             s = e.shape
             if len(s) < 2:
                 A, I, B = max(e.numel, 1), 1, 1

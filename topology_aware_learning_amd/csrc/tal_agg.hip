@@ -45,7 +45,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 26;
+constexpr int kAbiVersion = 27;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -3050,9 +3050,22 @@ inline bool cos_col_streamed(int kind, int64_t I, int64_t B) {
   return kind == kCosCol && B < 32 && cos_lp(I / 4) == 4 && cos_col_ob(B) * cos_col_pitch(B) <= kColMS;
 }
 
+// Element types (ABI 27): the kernels and helpers that hold model pointers take T = float, or
+// bf16 carried as its bit pattern (uint16_t, as the aggregation kernels' T).  The cosine
+// similarity of two bf16 models is defined as K2's fp32 result for the two models with every
+// parameter widened exactly to fp32 (tal_agg.h): only the loads differ.  Every load of a model
+// element goes through cos_ld - a bf16 pattern u is the fp32 value with bits u << 16 - and every
+// fp32 operation after it, the register ring, the LDS tiles, the plan and the scratch are the
+// fp32 form's.  The loads are scalar, so a bf16 row needs only 2-byte alignment.
+__host__ __device__ __forceinline__ float cos_ld(const float* p, int64_t i) { return p[i]; }
+__host__ __device__ __forceinline__ float cos_ld(const uint16_t* p, int64_t i) {
+  return __builtin_bit_cast(float, static_cast<uint32_t>(p[i]) << 16);
+}
+
+template <class T>
 struct CosPairs {
-  const float* a[kCosMaxPairs];
-  const float* b[kCosMaxPairs];
+  const T* a[kCosMaxPairs];
+  const T* b[kCosMaxPairs];
 };
 
 __device__ __forceinline__ int64_t cos_ceil_log2(int64_t x) {
@@ -3196,7 +3209,8 @@ __device__ __forceinline__ float cos_group_fold(float first, float v, int gbase)
   return r;
 }
 
-__global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const int64_t* __restrict__ plan,
+template <class T>
+__global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs<T> pr, const int64_t* __restrict__ plan,
                                                               int n_seg, int cnt, int64_t n_direct,
                                                               float* __restrict__ s_all) {
   // XCD-aware order: dispatch deals workgroups round-robin over the 8 XCDs, so workgroup 8 k + x
@@ -3213,14 +3227,14 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
   const int64_t first = ch[1], count = ch[2];
   const int64_t I = sg[2], B = sg[3];
   const int kind = static_cast<int>(sg[5]);
-  const float* a = pr.a[pair] + sg[0];
-  const float* b = pr.b[pair] + sg[0];
+  const T* a = pr.a[pair] + sg[0];
+  const T* b = pr.b[pair] + sg[0];
   float* s = s_all + static_cast<int64_t>(pair) * n_out + sg[4];
   const int tid = threadIdx.x;
   if (kind == kCosElem) {  // 1-D parameter unsqueezed to [n, 1]: norm |x|, one product
     const int64_t q = first + tid;
     if (q < first + count) {
-      const float x = a[q], y = b[q];
+      const float x = cos_ld(a, q), y = cos_ld(b, q);
       const float n1 = cos_clamp(cos_sqrt_rn(__fmaf_rn(x, x, 0.f)));
       const float n2 = cos_clamp(cos_sqrt_rn(__fmaf_rn(y, y, 0.f)));
       s[q] = __fadd_rn(0.f, __fmul_rn(__fdiv_rn(x, n1), __fdiv_rn(y, n2)));
@@ -3231,16 +3245,16 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
     const int64_t q = first + tid;
     if (q >= first + count) return;
     const int64_t o = q / B, k = q % B;
-    const float* x1 = a + o * I * B + k;
-    const float* x2 = b + o * I * B + k;
+    const T* x1 = a + o * I * B + k;
+    const T* x2 = b + o * I * B + k;
     float m1 = 0.f, m2 = 0.f;  // torch NormTwoOps: fma in index order (loads in batches of 8)
     int64_t i0 = 0;
     for (; i0 + 8 <= I; i0 += 8) {
       float u1[8], u2[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        u1[u] = x1[(i0 + u) * B];
-        u2[u] = x2[(i0 + u) * B];
+        u1[u] = cos_ld(x1, (i0 + u) * B);
+        u2[u] = cos_ld(x2, (i0 + u) * B);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -3249,11 +3263,11 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
       }
     }
     for (int64_t i = i0; i < I; ++i) {
-      m1 = __fmaf_rn(x1[i * B], x1[i * B], m1);
-      m2 = __fmaf_rn(x2[i * B], x2[i * B], m2);
+      m1 = __fmaf_rn(cos_ld(x1, i * B), cos_ld(x1, i * B), m1);
+      m2 = __fmaf_rn(cos_ld(x2, i * B), cos_ld(x2, i * B), m2);
     }
     const float n1 = cos_clamp(cos_sqrt_rn(m1)), n2 = cos_clamp(cos_sqrt_rn(m2));
-    auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(x1[i * B], n1), __fdiv_rn(x2[i * B], n2)); };
+    auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i * B), n1), __fdiv_rn(cos_ld(x2, i * B), n2)); };
     float r;
     if (B >= kCosVw && k < B / 32 * 32) {  // columns in chunks of 32 share one cascade
       float c[1];
@@ -3271,8 +3285,8 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
   const int gbase = lane & ~(kCosVw - 1);
   const int64_t q = first + tid / kCosVw;
   const bool live = q < first + count;
-  const float* x1 = a + (live ? q : first) * I;
-  const float* x2 = b + (live ? q : first) * I;
+  const T* x1 = a + (live ? q : first) * I;
+  const T* x2 = b + (live ? q : first) * I;
   const int64_t vec_end = I - I % kCosVw;
   // vector_norm (reduce-lastdim kernel): lane accumulators fma over whole vectors
   float m1 = 0.f, m2 = 0.f;
@@ -3282,8 +3296,8 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
       float u1[8], u2[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        u1[u] = x1[d + u * kCosVw];
-        u2[u] = x2[d + u * kCosVw];
+        u1[u] = cos_ld(x1, d + u * kCosVw);
+        u2[u] = cos_ld(x2, d + u * kCosVw);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -3292,8 +3306,8 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
       }
     }
     for (; d < vec_end; d += kCosVw) {
-      m1 = __fmaf_rn(x1[d], x1[d], m1);
-      m2 = __fmaf_rn(x2[d], x2[d], m2);
+      m1 = __fmaf_rn(cos_ld(x1, d), cos_ld(x1, d), m1);
+      m2 = __fmaf_rn(cos_ld(x2, d), cos_ld(x2, d), m2);
     }
   }
   float t1 = __shfl(m1, gbase, 64), t2 = __shfl(m2, gbase, 64);  // lane 0 starts the fold
@@ -3306,12 +3320,12 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
     int64_t d = vec_end;
     const int64_t sep = (I - vec_end) / 4 * 4;
     for (int64_t e = 0; e < sep; ++e, ++d) {
-      t1 = __fadd_rn(t1, __fmul_rn(x1[d], x1[d]));
-      t2 = __fadd_rn(t2, __fmul_rn(x2[d], x2[d]));
+      t1 = __fadd_rn(t1, __fmul_rn(cos_ld(x1, d), cos_ld(x1, d)));
+      t2 = __fadd_rn(t2, __fmul_rn(cos_ld(x2, d), cos_ld(x2, d)));
     }
     for (; d < I; ++d) {
-      t1 = __fmaf_rn(x1[d], x1[d], t1);
-      t2 = __fmaf_rn(x2[d], x2[d], t2);
+      t1 = __fmaf_rn(cos_ld(x1, d), cos_ld(x1, d), t1);
+      t2 = __fmaf_rn(cos_ld(x2, d), cos_ld(x2, d), t2);
     }
     n1 = cos_clamp(cos_sqrt_rn(t1));
     n2 = cos_clamp(cos_sqrt_rn(t2));
@@ -3322,7 +3336,7 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs pr, const
   // range checks the row tensors ran 0.255 -> 0.335 ms for ResNet-50's, with one check per row
   // (bounds of |x| gathered in the norm loop, a templated product phase) 0.259 ms; the row kind
   // is bound by its loads, not its divisions; profiles/r06/r06k/r06k14, r06k17)
-  auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(x1[i], n1), __fdiv_rn(x2[i], n2)); };
+  auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i), n1), __fdiv_rn(cos_ld(x2, i), n2)); };
   if (I < kCosVw) {  // scalar_inner_sum
     if (l == 0 && live) s[q] = __fadd_rn(0.f, cos_row_sum(prod, I));
     return;
@@ -3365,15 +3379,17 @@ __device__ __forceinline__ ColChunk col_chunk(const int64_t* __restrict__ plan, 
 // One thread's share of a step.  A model's part of a step is Ob blocks x kColIc B floats <= 2
 // kColThreads (Ob B <= 31), so thread t moves elements t and t + kColThreads of every model: one
 // per-thread offset pair serves all the models, whose base pointers are uniform (SGPRs).
+template <class T>
 struct ColLoads {
-  const float* gm[kColModels];  // model m's first element of the chunk
+  const T* gm[kColModels];      // model m's first element of the chunk
   int64_t go[2];                // offset of element h kColThreads + t in a model (without i0 B)
   int lo[2];                    // its LDS index in model 0's area (+ m MS)
   int r[2];                     // its position inside its block's kColIc B run; INT_MAX: none
   int nmod, MS;
 };
 
-__device__ __forceinline__ void col_loads_init(ColLoads& L, const float* const* gm, int nmod, const ColChunk& k) {
+template <class T>
+__device__ __forceinline__ void col_loads_init(ColLoads<T>& L, const T* const* gm, int nmod, const ColChunk& k) {
   const int run = kColIc * k.B;
   const int per_m = k.Ob * run;
 #pragma unroll
@@ -3395,9 +3411,10 @@ __device__ __forceinline__ void col_loads_init(ColLoads& L, const float* const* 
 // advances over the step's n <= kColIc elements (step(i0, n)).  The loads are unconditional
 // (a load outside the chunk re-reads the model's first chunk element and is not stored) and
 // the steps run in whole groups of kColDepth, so the loop body is straight-line code and each
-// step waits only for its own loads.
-template <class Step>
-__device__ __forceinline__ void col_stream(const ColLoads& L, int I, int B, float* lds, Step step) {
+// step waits only for its own loads.  The ring and the LDS hold fp32: a bf16 element is widened
+// as it is loaded (cos_ld), before the LDS store.
+template <class T, class Step>
+__device__ __forceinline__ void col_stream(const ColLoads<T>& L, int I, int B, float* lds, Step step) {
   const int nsteps = (I + kColIc - 1) / kColIc;
   float ring[kColDepth][2 * kColModels];
   int64_t go[2];
@@ -3410,7 +3427,7 @@ __device__ __forceinline__ void col_stream(const ColLoads& L, int I, int B, floa
     for (int h = 0; h < 2; ++h) {
       const int64_t a = L.r[h] < lim ? go[h] + static_cast<int64_t>(i0) * B : 0;
 #pragma unroll
-      for (int m = 0; m < kColModels; ++m) v[2 * m + h] = L.gm[m][a];  // m >= nmod: the last model again
+      for (int m = 0; m < kColModels; ++m) v[2 * m + h] = cos_ld(L.gm[m], a);  // m >= nmod: the last model again
     }
   };
 #pragma unroll
@@ -3438,9 +3455,10 @@ __device__ __forceinline__ void col_stream(const ColLoads& L, int I, int B, floa
 // 1, cosine_similarity's clamp_min), into nrm[(slot0 + g) n_out + output].  Shared by K2
 // (k_cos_col_norms) and its round form (k_cosr_col_norms), which differ only in where the model
 // pointers come from.
-__device__ __forceinline__ void cos_col_norms_body(const ColChunk& k, const float* const* gm, int nmod, int slot0,
+template <class T>
+__device__ __forceinline__ void cos_col_norms_body(const ColChunk& k, const T* const* gm, int nmod, int slot0,
                                                    int64_t n_out, float* lds, float* __restrict__ nrm) {
-  ColLoads L;
+  ColLoads<T> L;
   col_loads_init(L, gm, nmod, k);
   const int t = threadIdx.x, g = t / k.Cf, c = t - g * k.Cf;
   const bool live = g < nmod && c < k.C;
@@ -3474,7 +3492,8 @@ __device__ __forceinline__ void cos_col_norms_body(const ColChunk& k, const floa
 }
 
 // Norms: one workgroup per (streamed chunk, group of model slots); see cos_col_norms_body.
-__global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, const int64_t* __restrict__ plan, int n_seg,
+template <class T>
+__global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs<T> pr, const int64_t* __restrict__ plan, int n_seg,
                                                               int cnt, int same_a, float* __restrict__ nrm) {
   __shared__ float lds[kColModels * kColMS];
   const ColChunk k = col_chunk(plan, n_seg, blockIdx.x);
@@ -3483,7 +3502,7 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, cons
   const int m0 = static_cast<int>(blockIdx.y) * nmw;
   if (m0 >= n_models) return;
   const int nmod = min(nmw, n_models - m0);
-  const float* gm[kColModels];
+  const T* gm[kColModels];
 #pragma unroll
   for (int m = 0; m < kColModels; ++m) {
     // model slot s: one a shared by all pairs (slot 0 = a, 1 + p = b_p) or one per pair (2 p = a_p,
@@ -3506,9 +3525,10 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs pr, cons
 // k_cos_col_prods): this thread's pair reads models ma and mb of gm[] (LDS slots), whose norms as
 // k_cos_col_norms stored them are na and nb, for output c of the chunk; the sum goes to *dst.
 // Shared by K2 (k_cos_col_prods) and its round form (k_cosr_col_prods).
-__device__ __forceinline__ void cos_col_prods_body(const ColChunk& k, const float* const* gm, int nmod, bool live, int c,
+template <class T>
+__device__ __forceinline__ void cos_col_prods_body(const ColChunk& k, const T* const* gm, int nmod, bool live, int c,
                                                    int ma, int mb, float na, float nb, float* lds, float* dst) {
-  ColLoads L;
+  ColLoads<T> L;
   col_loads_init(L, gm, nmod, k);
   const int o = c / k.B, kk = c - o * k.B;
   // a negative norm: its chain has an element outside cos_rdiv's range (k_cos_col_norms)
@@ -3594,7 +3614,8 @@ __device__ __forceinline__ void cos_col_prods_body(const ColChunk& k, const floa
 }
 
 // Products of K2: one workgroup per (streamed chunk, group of pairs), see above.
-__global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs pr, const int64_t* __restrict__ plan, int n_seg,
+template <class T>
+__global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs<T> pr, const int64_t* __restrict__ plan, int n_seg,
                                                               int cnt, int same_a, const float* __restrict__ nrm,
                                                               float* __restrict__ s_all) {
   __shared__ float lds[kColModels * kColMS];
@@ -3606,7 +3627,7 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs pr, cons
   if (p0 >= cnt) return;
   const int np = min(ppw, cnt - p0);
   const int nmod = same_a ? 1 + np : 2 * np;
-  const float* gm[kColModels];
+  const T* gm[kColModels];
 #pragma unroll
   for (int m = 0; m < kColModels; ++m) {
     const int mm = min(m, nmod - 1);
@@ -3715,7 +3736,8 @@ __host__ __device__ inline CosrTable cosr_table(const int32_t* t) {
 }
 
 // streamed column chunks: every model's norms, model slots = the table's models
-__global__ __launch_bounds__(kColThreads) void k_cosr_col_norms(const float* __restrict__ pool, int64_t ld,
+template <class T>
+__global__ __launch_bounds__(kColThreads) void k_cosr_col_norms(const T* __restrict__ pool, int64_t ld,
                                                                const int32_t* __restrict__ table,
                                                                const int64_t* __restrict__ plan, int n_seg,
                                                                float* __restrict__ nrm) {
@@ -3727,7 +3749,7 @@ __global__ __launch_bounds__(kColThreads) void k_cosr_col_norms(const float* __r
   const int m0 = static_cast<int>(blockIdx.y) * nmw;
   if (m0 >= n_models) return;
   const int nmod = min(nmw, n_models - m0);
-  const float* gm[kColModels];
+  const T* gm[kColModels];
 #pragma unroll
   for (int m = 0; m < kColModels; ++m) gm[m] = pool + tb.models[m0 + min(m, nmod - 1)] * ld;
   cos_col_norms_body(k, gm, nmod, m0, plan[1], lds, nrm);
@@ -3735,7 +3757,8 @@ __global__ __launch_bounds__(kColThreads) void k_cosr_col_norms(const float* __r
 
 // streamed column chunks: one workgroup per (chunk, pair group g0 + blockIdx.y); LDS slot 0 = the
 // group's shared row, slot 1 + j = the other row of its pair j; pair u's outputs at s_all[u - u0]
-__global__ __launch_bounds__(kColThreads) void k_cosr_col_prods(const float* __restrict__ pool, int64_t ld,
+template <class T>
+__global__ __launch_bounds__(kColThreads) void k_cosr_col_prods(const T* __restrict__ pool, int64_t ld,
                                                                const int32_t* __restrict__ table,
                                                                const int64_t* __restrict__ plan, int n_seg, int g0,
                                                                int u0, const float* __restrict__ nrm,
@@ -3747,7 +3770,7 @@ __global__ __launch_bounds__(kColThreads) void k_cosr_col_prods(const float* __r
   const int32_t* grp = tb.groups + 3 * (g0 + static_cast<int>(blockIdx.y));
   const int slot_a = grp[0], first = grp[1], np = grp[2];
   const int nmod = 1 + np;
-  const float* gm[kColModels];
+  const T* gm[kColModels];
 #pragma unroll
   for (int m = 0; m < kColModels; ++m) {
     const int mm = min(m, nmod - 1);
@@ -3781,7 +3804,8 @@ __device__ __forceinline__ bool cosr_direct_chunk(const int64_t* __restrict__ pl
 
 // direct chunks: one workgroup per (chunk, model): the clamped norms of the chunk's outputs, the
 // norm halves of k_cosine_outputs for one model
-__global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const float* __restrict__ pool, int64_t ld,
+template <class T>
+__global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const T* __restrict__ pool, int64_t ld,
                                                          const int32_t* __restrict__ table,
                                                          const int64_t* __restrict__ plan, int n_seg,
                                                          int64_t n_direct, float* __restrict__ nrm) {
@@ -3791,29 +3815,29 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const float* __restric
   const int64_t first = ch[1], count = ch[2];
   const int64_t I = sg[2], B = sg[3];
   const int kind = static_cast<int>(sg[5]);
-  const float* a = pool + cosr_table(table).models[slot] * ld + sg[0];
+  const T* a = pool + cosr_table(table).models[slot] * ld + sg[0];
   float* nm = nrm + static_cast<int64_t>(slot) * plan[1] + sg[4];
   const int tid = threadIdx.x;
   if (kind == kCosElem) {
     const int64_t q = first + tid;
-    if (q < first + count) nm[q] = cos_clamp(cos_sqrt_rn(__fmaf_rn(a[q], a[q], 0.f)));
+    if (q < first + count) nm[q] = cos_clamp(cos_sqrt_rn(__fmaf_rn(cos_ld(a, q), cos_ld(a, q), 0.f)));
     return;
   }
   if (kind == kCosCol) {  // torch NormTwoOps: fma in index order (loads in batches of 8)
     const int64_t q = first + tid;
     if (q >= first + count) return;
     const int64_t o = q / B, k = q % B;
-    const float* x1 = a + o * I * B + k;
+    const T* x1 = a + o * I * B + k;
     float m1 = 0.f;
     int64_t i0 = 0;
     for (; i0 + 8 <= I; i0 += 8) {
       float u1[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) u1[u] = x1[(i0 + u) * B];
+      for (int u = 0; u < 8; ++u) u1[u] = cos_ld(x1, (i0 + u) * B);
 #pragma unroll
       for (int u = 0; u < 8; ++u) m1 = __fmaf_rn(u1[u], u1[u], m1);
     }
-    for (int64_t i = i0; i < I; ++i) m1 = __fmaf_rn(x1[i * B], x1[i * B], m1);
+    for (int64_t i = i0; i < I; ++i) m1 = __fmaf_rn(cos_ld(x1, i * B), cos_ld(x1, i * B), m1);
     nm[q] = cos_clamp(cos_sqrt_rn(m1));
     return;
   }
@@ -3824,7 +3848,7 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const float* __restric
   const int gbase = lane & ~(kCosVw - 1);
   const int64_t q = first + tid / kCosVw;
   const bool live = q < first + count;
-  const float* x1 = a + (live ? q : first) * I;
+  const T* x1 = a + (live ? q : first) * I;
   const int64_t vec_end = I - I % kCosVw;
   float m1 = 0.f;
   if (live) {
@@ -3832,58 +3856,63 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const float* __restric
     for (; d + 7 * kCosVw < vec_end; d += 8 * kCosVw) {
       float u1[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) u1[u] = x1[d + u * kCosVw];
+      for (int u = 0; u < 8; ++u) u1[u] = cos_ld(x1, d + u * kCosVw);
 #pragma unroll
       for (int u = 0; u < 8; ++u) m1 = __fmaf_rn(u1[u], u1[u], m1);
     }
-    for (; d < vec_end; d += kCosVw) m1 = __fmaf_rn(x1[d], x1[d], m1);
+    for (; d < vec_end; d += kCosVw) m1 = __fmaf_rn(cos_ld(x1, d), cos_ld(x1, d), m1);
   }
   float t1 = __shfl(m1, gbase, 64);  // lane 0 starts the fold
   for (int j = 1; j < kCosVw; ++j) t1 = __fadd_rn(t1, __shfl(m1, gbase + j, 64));
   if (l == 0 && live) {
     int64_t d = vec_end;
     const int64_t sep = (I - vec_end) / 4 * 4;
-    for (int64_t e = 0; e < sep; ++e, ++d) t1 = __fadd_rn(t1, __fmul_rn(x1[d], x1[d]));
-    for (; d < I; ++d) t1 = __fmaf_rn(x1[d], x1[d], t1);
+    for (int64_t e = 0; e < sep; ++e, ++d) t1 = __fadd_rn(t1, __fmul_rn(cos_ld(x1, d), cos_ld(x1, d)));
+    for (; d < I; ++d) t1 = __fmaf_rn(cos_ld(x1, d), cos_ld(x1, d), t1);
     nm[q] = cos_clamp(cos_sqrt_rn(t1));
   }
 }
 
 // One workgroup's view of a direct chunk and a pair group (k_cosr_prods)
+template <class T>
 struct CosrGroup {
-  const float* pool;
+  const T* pool;
   int64_t ld, n_out, seg_off, out_off;  // the tensor's offset in a row and its first output
   const int32_t* models;
   const int32_t* uniq;   // the group's first unique pair
   const float* nrm;
   float* s_all;          // the group's first pair's outputs
 };
-__device__ __forceinline__ int cosr_slot_b(const CosrGroup& g, int j) { return g.uniq[2 * j + 1]; }
-__device__ __forceinline__ const float* cosr_b(const CosrGroup& g, int j) {
+template <class T>
+__device__ __forceinline__ int cosr_slot_b(const CosrGroup<T>& g, int j) { return g.uniq[2 * j + 1]; }
+template <class T>
+__device__ __forceinline__ const T* cosr_b(const CosrGroup<T>& g, int j) {
   return g.pool + g.models[cosr_slot_b(g, j)] * g.ld + g.seg_off;
 }
-__device__ __forceinline__ const float* cosr_nrm_b(const CosrGroup& g, int j) {
+template <class T>
+__device__ __forceinline__ const float* cosr_nrm_b(const CosrGroup<T>& g, int j) {
   return g.nrm + static_cast<int64_t>(cosr_slot_b(g, j)) * g.n_out + g.out_off;
 }
-__device__ __forceinline__ float* cosr_s(const CosrGroup& g, int j) { return g.s_all + j * g.n_out + g.out_off; }
+template <class T>
+__device__ __forceinline__ float* cosr_s(const CosrGroup<T>& g, int j) { return g.s_all + j * g.n_out + g.out_off; }
 
 // Row kind, pairs j0 .. j0 + P of the group at once: torch's inner sum of each pair's products (x1
 // / n1) (x2 / n2) as in k_cosine_outputs - scalar_inner_sum below 8 elements, else
 // vectorized_inner_sum: lane l sums elements 8 i + l by row_sum, then the scalar tail from 0, then
 // the lanes in order - with the shared row's quotient x1 / n1 divided once per element for the P
 // pairs (cos_row_sum_pairs).  x1: the shared row's row q, n1 its norm.
-template <int P, int kU>
-__device__ __forceinline__ void cosr_row_pairs(const CosrGroup& g, int j0, const float* x1, float n1, int64_t q,
+template <int P, int kU, class T>
+__device__ __forceinline__ void cosr_row_pairs(const CosrGroup<T>& g, int j0, const T* x1, float n1, int64_t q,
                                                int64_t rowoff, int64_t I, bool live, int l, int gbase) {
-  const float* x2[P];
+  const T* x2[P];
   float n2[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     x2[p] = cosr_b(g, j0 + p) + rowoff;
     n2[p] = live ? cosr_nrm_b(g, j0 + p)[q] : 1.f;
   }
-  auto qa = [&](int64_t i) { return __fdiv_rn(x1[i], n1); };
-  auto qb = [&](int64_t i, int p) { return __fdiv_rn(x2[p][i], n2[p]); };
+  auto qa = [&](int64_t i) { return __fdiv_rn(cos_ld(x1, i), n1); };
+  auto qb = [&](int64_t i, int p) { return __fdiv_rn(cos_ld(x2[p], i), n2[p]); };
   if (I < kCosVw) {  // scalar_inner_sum
     if (l == 0 && live) {
       float r[P];
@@ -3917,7 +3946,8 @@ __device__ __forceinline__ void cosr_row_pairs(const CosrGroup& g, int j0, const
 // with both norms read from the table.  Row tensors take the group's pairs four (then two, then
 // one) at a time, the shared row's loads and quotients once for them; the element and column
 // kinds (1-D parameters, B >= 32: few and small) take them one after another.
-__global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const float* __restrict__ pool, int64_t ld,
+template <class T>
+__global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const T* __restrict__ pool, int64_t ld,
                                                          const int32_t* __restrict__ table,
                                                          const int64_t* __restrict__ plan, int n_seg,
                                                          int64_t n_direct, int g0, int ng, int u0,
@@ -3928,7 +3958,7 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const float* __restric
   const CosrTable tb = cosr_table(table);
   const int32_t* grp = tb.groups + 3 * (g0 + gi);
   const int slot_a = grp[0], np = grp[2];
-  CosrGroup g;
+  CosrGroup<T> g;
   g.pool = pool;
   g.ld = ld;
   g.n_out = plan[1];
@@ -3941,28 +3971,28 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const float* __restric
   const int64_t first = ch[1], count = ch[2];
   const int64_t I = sg[2], B = sg[3];
   const int kind = static_cast<int>(sg[5]);
-  const float* a = pool + tb.models[slot_a] * ld + sg[0];
+  const T* a = pool + tb.models[slot_a] * ld + sg[0];
   const float* nma = nrm + static_cast<int64_t>(slot_a) * g.n_out + sg[4];
   const int tid = threadIdx.x;
   if (kind == kCosElem) {
     const int64_t q = first + tid;
     if (q >= first + count) return;
-    const float qa = __fdiv_rn(a[q], nma[q]);
+    const float qa = __fdiv_rn(cos_ld(a, q), nma[q]);
     for (int j = 0; j < np; ++j)
-      cosr_s(g, j)[q] = __fadd_rn(0.f, __fmul_rn(qa, __fdiv_rn(cosr_b(g, j)[q], cosr_nrm_b(g, j)[q])));
+      cosr_s(g, j)[q] = __fadd_rn(0.f, __fmul_rn(qa, __fdiv_rn(cos_ld(cosr_b(g, j), q), cosr_nrm_b(g, j)[q])));
     return;
   }
   if (kind == kCosCol) {
     const int64_t q = first + tid;
     if (q >= first + count) return;
     const int64_t o = q / B, k = q % B;
-    const float* x1 = a + o * I * B + k;
+    const T* x1 = a + o * I * B + k;
     const float n1 = nma[q];
 #pragma nounroll
     for (int j = 0; j < np; ++j) {
-      const float* x2 = cosr_b(g, j) + o * I * B + k;
+      const T* x2 = cosr_b(g, j) + o * I * B + k;
       const float n2 = cosr_nrm_b(g, j)[q];
-      auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(x1[i * B], n1), __fdiv_rn(x2[i * B], n2)); };
+      auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i * B), n1), __fdiv_rn(cos_ld(x2, i * B), n2)); };
       float r;
       if (B >= kCosVw && k < B / 32 * 32) {  // columns in chunks of 32 share one cascade
         float c[1];
@@ -3982,7 +4012,7 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const float* __restric
   const int64_t q = first + tid / kCosVw;
   const bool live = q < first + count;
   const int64_t rowoff = (live ? q : first) * I;
-  const float* x1 = a + rowoff;
+  const T* x1 = a + rowoff;
   const float n1 = live ? nma[q] : 1.f;
   int j = 0;
 #pragma nounroll
@@ -5171,60 +5201,107 @@ static bool cos_stream_wait(hipStream_t to, hipStream_t from) {
   return ok;
 }
 
-int32_t tal_cosine_params(const float* const* a_ptrs_host, const float* const* b_ptrs_host,
-                          int32_t n_pairs, const int64_t* plan_dev, const int64_t* plan_host, int32_t n_chunks,
-                          void* scratch, float* out_dev, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// The device of the caller's stream made current for a call's side-stream work (the side stream
+// and the fork / join events belong to the current device; a caller may pass a stream of another
+// one), the caller's current device restored on return.
+struct CosStreamDevice {
+  int prev = -1;
+  bool ok = true;
+  CosStreamDevice(hipStream_t s, bool needed) {  // !needed: nothing is queried or changed
+    if (!needed) return;
+    int cur = 0, dev = 0;
+    ok = hipGetDevice(&cur) == hipSuccess && hipStreamGetDevice(s, &dev) == hipSuccess;
+    if (ok && dev != cur) {
+      ok = hipSetDevice(dev) == hipSuccess;
+      if (ok) prev = cur;
+    }
+  }
+  ~CosStreamDevice() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// K2 for either element type (fn: the entry point's name in messages)
+template <class T>
+int32_t cosine_params(const char* fn, const T* const* a_ptrs_host, const T* const* b_ptrs_host, int32_t n_pairs,
+                      const int64_t* plan_dev, const int64_t* plan_host, int32_t n_chunks, void* scratch,
+                      float* out_dev, void* stream) {
   if (!a_ptrs_host || !b_ptrs_host || !plan_dev || !plan_host || !scratch || !out_dev || n_pairs <= 0 ||
       n_chunks <= 0 || plan_host[0] <= 0 || plan_host[1] <= 0)
-    return fail(TAL_ERR_INVALID, "tal_cosine_params: bad arguments");
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
   const int n_seg = static_cast<int>(plan_host[0]);
   const int64_t n_out = plan_host[1];
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t n_staged = plan_host[3];
+  // the direct chunks do not depend on the streamed ones: with both present they run on the
+  // device's side stream, forked from and joined back into `s`, so they fill the GPU beside the
+  // streamed kernels' workgroups.  The side stream is that of the device `s` runs on, made
+  // current for the call.
+  const bool fork = n_staged > 0 && n_chunks > n_staged;
+  const CosStreamDevice on(s, fork);
+  if (!on.ok) return fail(TAL_ERR_HIP, std::string(fn) + ": the stream's device");
   for (int base = 0; base < n_pairs; base += kCosMaxPairs) {
     const int cnt = std::min(kCosMaxPairs, n_pairs - base);
-    CosPairs pr;
+    CosPairs<T> pr;
     for (int j = 0; j < kCosMaxPairs; ++j) {
       pr.a[j] = j < cnt ? a_ptrs_host[base + j] : nullptr;
       pr.b[j] = j < cnt ? b_ptrs_host[base + j] : nullptr;
       if (j < cnt && (!pr.a[j] || !pr.b[j]))
-        return fail(TAL_ERR_INVALID, "tal_cosine_params: null model pointer");
+        return fail(TAL_ERR_INVALID, std::string(fn) + ": null model pointer");
     }
     float* s_all = static_cast<float*>(scratch);
     float* means = s_all + n_out * cnt;
-    const int64_t n_staged = plan_host[3];
     // pairs sharing one `a` (sim_centrality_module_avg: the client against each neighbor): its
     // norms once, and up to kColPairs pairs per product workgroup read its chunk once
     bool same_a = true;
     for (int j = 1; j < cnt; ++j) same_a = same_a && pr.a[j] == pr.a[0];
-    // the direct chunks do not depend on the streamed ones: with both present they run on the
-    // device's side stream, forked from and joined back into `s`, so they fill the GPU beside the
-    // streamed kernels' workgroups
-    const bool fork = n_staged > 0 && n_chunks > n_staged;
     hipStream_t so = s;
     if (fork) {
       so = cos_side_stream();
-      if (!so) return fail(TAL_ERR_HIP, "tal_cosine_params: side stream");
-      if (!cos_stream_wait(so, s)) return fail(TAL_ERR_HIP, "tal_cosine_params: fork");
+      if (!so) return fail(TAL_ERR_HIP, std::string(fn) + ": side stream");
+      if (!cos_stream_wait(so, s)) return fail(TAL_ERR_HIP, std::string(fn) + ": fork");
     }
     if (n_chunks > n_staged) {
       const int64_t n_direct = n_chunks - n_staged;
-      k_cosine_outputs<<<static_cast<unsigned>((n_direct + 7) / 8 * 8 * cnt), kCosBlock, 0, so>>>(pr, plan_dev, n_seg,
-                                                                                                 cnt, n_direct, s_all);
+      k_cosine_outputs<T><<<static_cast<unsigned>((n_direct + 7) / 8 * 8 * cnt), kCosBlock, 0, so>>>(
+          pr, plan_dev, n_seg, cnt, n_direct, s_all);
     }
     if (n_staged > 0) {
       float* nrm = means + static_cast<int64_t>(n_seg) * cnt;  // model slots x n_out
       const int n_models = same_a ? 1 + cnt : 2 * cnt;
       const int ppw = same_a ? kColPairs : kColPairs / 2;
-      k_cos_col_norms<<<dim3(static_cast<unsigned>(n_staged), (n_models + 7) / 8), kColThreads, 0, s>>>(
+      k_cos_col_norms<T><<<dim3(static_cast<unsigned>(n_staged), (n_models + 7) / 8), kColThreads, 0, s>>>(
           pr, plan_dev, n_seg, cnt, same_a ? 1 : 0, nrm);
-      k_cos_col_prods<<<dim3(static_cast<unsigned>(n_staged), (cnt + ppw - 1) / ppw), kColThreads, 0, s>>>(
+      k_cos_col_prods<T><<<dim3(static_cast<unsigned>(n_staged), (cnt + ppw - 1) / ppw), kColThreads, 0, s>>>(
           pr, plan_dev, n_seg, cnt, same_a ? 1 : 0, nrm, s_all);
     }
-    if (fork && !cos_stream_wait(s, so)) return fail(TAL_ERR_HIP, "tal_cosine_params: join");
+    if (fork && !cos_stream_wait(s, so)) return fail(TAL_ERR_HIP, std::string(fn) + ": join");
     k_cosine_means<<<dim3(n_seg, cnt), 64, 0, s>>>(plan_dev, n_seg, s_all, means);
     k_cosine_finish<<<cnt, 64, 0, s>>>(n_seg, means, out_dev, base);
   }
-  return check_launch("tal_cosine_params");
+  return check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t tal_cosine_params(const float* const* a_ptrs_host, const float* const* b_ptrs_host,
+                          int32_t n_pairs, const int64_t* plan_dev, const int64_t* plan_host, int32_t n_chunks,
+                          void* scratch, float* out_dev, void* stream) {
+  return cosine_params<float>("tal_cosine_params", a_ptrs_host, b_ptrs_host, n_pairs, plan_dev, plan_host, n_chunks,
+                              scratch, out_dev, stream);
+}
+
+int32_t tal_cosine_params_bf16(const uint16_t* const* a_ptrs_host, const uint16_t* const* b_ptrs_host,
+                               int32_t n_pairs, const int64_t* plan_dev, const int64_t* plan_host, int32_t n_chunks,
+                               void* scratch, float* out_dev, void* stream) {
+  return cosine_params<uint16_t>("tal_cosine_params_bf16", a_ptrs_host, b_ptrs_host, n_pairs, plan_dev, plan_host,
+                                 n_chunks, scratch, out_dev, stream);
 }
 
 // ---- K2r: the round form (table format in tal_agg.h) ------------------------------------------
@@ -5381,19 +5458,25 @@ int64_t tal_cosine_round_scratch_bytes(const int64_t* plan_host, const int32_t* 
   return cosr_scratch_need(plan_host, info, largest);
 }
 
-int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
-                         int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
-                         const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
-                         float* out_dev, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// K2r for either element type (fn: the entry point's name in messages)
+template <class T>
+int32_t cosine_round(const char* fn, const T* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
+                     int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
+                     const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes, float* out_dev,
+                     void* stream) {
   if (!pool || !plan_dev || !plan_host || !table_dev || !table_host || !info || !scratch || !out_dev || n_chunks <= 0 ||
       plan_host[0] <= 0 || plan_host[1] <= 0 || plan_host[3] < 0 || plan_host[3] > n_chunks)
-    return fail(TAL_ERR_INVALID, "tal_cosine_round: bad arguments");
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
   if (!cosr_info_matches(table_host, info))
-    return fail(TAL_ERR_INVALID, "tal_cosine_round: info does not describe the table");
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": info does not describe the table");
   if (info->batch_pairs < info->max_group || info->batch_pairs > kCosrMaxBatch)
-    return fail(TAL_ERR_INVALID, "tal_cosine_round: no batch size (call tal_cosine_round_scratch_bytes first)");
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": no batch size (call tal_cosine_round_scratch_bytes first)");
   if (scratch_bytes < cosr_scratch_need(plan_host, info, info->batch_pairs))
-    return fail(TAL_ERR_INVALID, "tal_cosine_round: scratch too small");
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": scratch too small");
   const int n_seg = static_cast<int>(plan_host[0]);
   const int64_t n_out = plan_host[1];
   int64_t extent = 0;  // a row's elements the plan reads
@@ -5401,7 +5484,7 @@ int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev,
     const int64_t* sg = plan_host + kCosHdr + kCosSegWords * static_cast<int64_t>(t);
     extent = std::max(extent, sg[0] + sg[1] * sg[2] * sg[3]);
   }
-  if (ld < extent) return fail(TAL_ERR_INVALID, "tal_cosine_round: row pitch shorter than the plan's parameters");
+  if (ld < extent) return fail(TAL_ERR_INVALID, std::string(fn) + ": row pitch shorter than the plan's parameters");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int32_t* groups = cosr_table(table_host).groups;
   float* nrm = static_cast<float*>(scratch);
@@ -5411,29 +5494,49 @@ int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev,
   const int64_t n_staged = plan_host[3], n_direct = n_chunks - n_staged;
   const int64_t direct8 = (n_direct + 7) / 8 * 8;
   if (direct8 * std::max(info->n_models, info->n_groups) > 0x7fffffff)
-    return fail(TAL_ERR_INVALID, "tal_cosine_round: too many workgroups");
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": too many workgroups");
   // every launch on the caller's stream: a whole round fills the GPU without a side stream
   if (n_staged > 0)
-    k_cosr_col_norms<<<dim3(static_cast<unsigned>(n_staged), (info->n_models + 7) / 8), kColThreads, 0, s>>>(
+    k_cosr_col_norms<T><<<dim3(static_cast<unsigned>(n_staged), (info->n_models + 7) / 8), kColThreads, 0, s>>>(
         pool, ld, table_dev, plan_dev, n_seg, nrm);
   if (n_direct > 0)
-    k_cosr_norms<<<static_cast<unsigned>(direct8 * info->n_models), kCosBlock, 0, s>>>(pool, ld, table_dev, plan_dev,
+    k_cosr_norms<T><<<static_cast<unsigned>(direct8 * info->n_models), kCosBlock, 0, s>>>(pool, ld, table_dev, plan_dev,
                                                                                       n_seg, n_direct, nrm);
   for (int32_t g = 0, ge = 0; g < info->n_groups; g = ge) {
     const int32_t cnt = cosr_batch(groups, info->n_groups, info->batch_pairs, g, &ge);
-    if (cnt <= 0) return fail(TAL_ERR_INVALID, "tal_cosine_round: a group exceeds the batch");
+    if (cnt <= 0) return fail(TAL_ERR_INVALID, std::string(fn) + ": a group exceeds the batch");
     const int32_t ng = ge - g, u0 = groups[3 * g + 1];
     if (n_staged > 0)
-      k_cosr_col_prods<<<dim3(static_cast<unsigned>(n_staged), ng), kColThreads, 0, s>>>(pool, ld, table_dev, plan_dev,
+      k_cosr_col_prods<T><<<dim3(static_cast<unsigned>(n_staged), ng), kColThreads, 0, s>>>(pool, ld, table_dev, plan_dev,
                                                                                         n_seg, g, u0, nrm, s_all);
     if (n_direct > 0)
-      k_cosr_prods<<<static_cast<unsigned>(direct8 * ng), kCosBlock, 0, s>>>(pool, ld, table_dev, plan_dev, n_seg,
+      k_cosr_prods<T><<<static_cast<unsigned>(direct8 * ng), kCosBlock, 0, s>>>(pool, ld, table_dev, plan_dev, n_seg,
                                                                             n_direct, g, ng, u0, nrm, s_all);
     k_cosine_means<<<dim3(n_seg, cnt), 64, 0, s>>>(plan_dev, n_seg, s_all, means);
     k_cosine_finish<<<cnt, 64, 0, s>>>(n_seg, means, res, u0);
   }
   k_cosr_gather<<<(info->n_pairs + 255) / 256, 256, 0, s>>>(table_dev, res, out_dev);
-  return check_launch("tal_cosine_round");
+  return check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t tal_cosine_round(const float* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
+                         int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
+                         const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
+                         float* out_dev, void* stream) {
+  return cosine_round<float>("tal_cosine_round", pool, ld, plan_dev, plan_host, n_chunks, table_dev, table_host, info,
+                             scratch, scratch_bytes, out_dev, stream);
+}
+
+int32_t tal_cosine_round_bf16(const uint16_t* pool, int64_t ld, const int64_t* plan_dev, const int64_t* plan_host,
+                              int32_t n_chunks, const int32_t* table_dev, const int32_t* table_host,
+                              const tal_cosine_round_info* info, void* scratch, int64_t scratch_bytes,
+                              float* out_dev, void* stream) {
+  return cosine_round<uint16_t>("tal_cosine_round_bf16", pool, ld, plan_dev, plan_host, n_chunks, table_dev,
+                                table_host, info, scratch, scratch_bytes, out_dev, stream);
 }
 
 
@@ -5995,42 +6098,44 @@ struct HostCos {
     return t;
   }
   static float clampn(float v) { return v < 1e-6f ? 1e-6f : v; }  // NaN stays NaN
-  // every output of chunk ch (plan words) of one pair
-  static void outputs(const int64_t* plan, int64_t ch, const float* a0, const float* b0, float* s_all) {
+  // every output of chunk ch (plan words) of one pair; T: float, or bf16 bit patterns widened by
+  // cos_ld as the kernels widen them
+  template <class T>
+  static void outputs(const int64_t* plan, int64_t ch, const T* a0, const T* b0, float* s_all) {
     const int64_t n_seg = plan[0];
     const int64_t* c = plan + kCosHdr + kCosSegWords * n_seg + kCosChunkWords * ch;
     const int64_t* sg = plan + kCosHdr + kCosSegWords * c[0];
     const int64_t I = sg[2], B = sg[3];
-    const float* a = a0 + sg[0];
-    const float* b = b0 + sg[0];
+    const T* a = a0 + sg[0];
+    const T* b = b0 + sg[0];
     float* s = s_all + sg[4];
     for (int64_t q = c[1]; q < c[1] + c[2]; ++q) {
       if (sg[5] == kCosElem) {
-        const float n1 = clampn(std::sqrt(std::fma(a[q], a[q], 0.f)));
-        const float n2 = clampn(std::sqrt(std::fma(b[q], b[q], 0.f)));
-        s[q] = 0.f + (a[q] / n1) * (b[q] / n2);
+        const float n1 = clampn(std::sqrt(std::fma(cos_ld(a, q), cos_ld(a, q), 0.f)));
+        const float n2 = clampn(std::sqrt(std::fma(cos_ld(b, q), cos_ld(b, q), 0.f)));
+        s[q] = 0.f + (cos_ld(a, q) / n1) * (cos_ld(b, q) / n2);
       } else if (sg[5] == kCosCol) {  // reduced dim strided by B
         const int64_t k = q % B;
-        const float* x = a + (q / B) * I * B + k;
-        const float* y = b + (q / B) * I * B + k;
+        const T* x = a + (q / B) * I * B + k;
+        const T* y = b + (q / B) * I * B + k;
         float m1 = 0.f, m2 = 0.f;
         for (int64_t i = 0; i < I; ++i) {
-          m1 = std::fma(x[i * B], x[i * B], m1);
-          m2 = std::fma(y[i * B], y[i * B], m2);
+          m1 = std::fma(cos_ld(x, i * B), cos_ld(x, i * B), m1);
+          m2 = std::fma(cos_ld(y, i * B), cos_ld(y, i * B), m2);
         }
         const float n1 = clampn(std::sqrt(m1)), n2 = clampn(std::sqrt(m2));
-        auto pr = [&](int64_t i) { return (x[i * B] / n1) * (y[i * B] / n2); };
+        auto pr = [&](int64_t i) { return (cos_ld(x, i * B) / n1) * (cos_ld(y, i * B) / n2); };
         // columns in groups of 32 share one cascade; groups of 8 and single columns: row_sum
         s[q] = 0.f + ((B >= kCosVw && k < B / 32 * 32) ? cascade(pr, I) : row(pr, I));
       } else {  // kCosRow: reduced dim contiguous, torch's 8-lane norm then its inner sum
-        const float* x = a + q * I;
-        const float* y = b + q * I;
+        const T* x = a + q * I;
+        const T* y = b + q * I;
         const int64_t ve = I - I % kCosVw;
         float l1[kCosVw] = {}, l2[kCosVw] = {};
         for (int64_t d = 0; d < ve; d += kCosVw)
           for (int l = 0; l < kCosVw; ++l) {
-            l1[l] = std::fma(x[d + l], x[d + l], l1[l]);
-            l2[l] = std::fma(y[d + l], y[d + l], l2[l]);
+            l1[l] = std::fma(cos_ld(x, d + l), cos_ld(x, d + l), l1[l]);
+            l2[l] = std::fma(cos_ld(y, d + l), cos_ld(y, d + l), l2[l]);
           }
         float t1 = l1[0], t2 = l2[0];
         for (int l = 1; l < kCosVw; ++l) {
@@ -6039,15 +6144,15 @@ struct HostCos {
         }
         int64_t d = ve;
         for (const int64_t e = ve + (I - ve) / 4 * 4; d < e; ++d) {  // groups of 4: square, add
-          t1 = t1 + x[d] * x[d];
-          t2 = t2 + y[d] * y[d];
+          t1 = t1 + cos_ld(x, d) * cos_ld(x, d);
+          t2 = t2 + cos_ld(y, d) * cos_ld(y, d);
         }
         for (; d < I; ++d) {  // the last < 4: fused
-          t1 = std::fma(x[d], x[d], t1);
-          t2 = std::fma(y[d], y[d], t2);
+          t1 = std::fma(cos_ld(x, d), cos_ld(x, d), t1);
+          t2 = std::fma(cos_ld(y, d), cos_ld(y, d), t2);
         }
         const float n1 = clampn(std::sqrt(t1)), n2 = clampn(std::sqrt(t2));
-        s[q] = 0.f + inner([&](int64_t i) { return (x[i] / n1) * (y[i] / n2); }, I);
+        s[q] = 0.f + inner([&](int64_t i) { return (cos_ld(x, i) / n1) * (cos_ld(y, i) / n2); }, I);
       }
     }
   }
@@ -6073,6 +6178,65 @@ struct HostCos {
     return (0.f + fin) / static_cast<float>(n);
   }
 };
+
+// tal_host_cosine / tal_host_cosine_round for either element type (fn: the entry point's name)
+template <class T>
+int32_t host_cosine(const char* fn, const T* const* a_host, const T* const* b_host, int32_t n_pairs,
+                    const int64_t* plan_host, float* out) {
+  if (!a_host || !b_host || !plan_host || !out || n_pairs <= 0 || plan_host[0] <= 0 || plan_host[1] <= 0 ||
+      plan_host[2] < 1 || plan_host[2] > kCosMaxThreads)
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
+  for (int j = 0; j < n_pairs; ++j)
+    if (!a_host[j] || !b_host[j]) return fail(TAL_ERR_INVALID, std::string(fn) + ": null model pointer");
+  const int64_t n_seg = plan_host[0], n_out = plan_host[1];
+  int64_t n_chunks = 0;  // chunk words follow the segment words; count them from the segments
+  for (int64_t t = 0; t < n_seg; ++t) {
+    const int64_t* sg = plan_host + kCosHdr + kCosSegWords * t;
+    n_chunks += (sg[1] * sg[3] + sg[6] - 1) / sg[6];
+  }
+  std::vector<float> s_all(static_cast<size_t>(n_out));
+  std::vector<float> means(static_cast<size_t>(n_seg));
+  for (int j = 0; j < n_pairs; ++j) {
+    // outputs chunk by chunk, then the means tensor by tensor, each on up to 16 host threads
+    host_blocks(n_chunks * kHostBlock, [&](int64_t e0, int64_t) {
+      HostCos::outputs(plan_host, e0 / kHostBlock, a_host[j], b_host[j], s_all.data());
+    });
+    host_blocks(n_seg * kHostBlock, [&](int64_t e0, int64_t) {
+      means[static_cast<size_t>(e0 / kHostBlock)] = HostCos::mean(plan_host, e0 / kHostBlock, s_all.data());
+    });
+    float avg = 0.f + means[0];  // 0 + mean_0, += mean_t in parameter order, / len(params)
+    for (int64_t t = 1; t < n_seg; ++t) avg = avg + means[static_cast<size_t>(t)];
+    out[j] = avg / static_cast<float>(n_seg);
+  }
+  g_err.clear();
+  return TAL_OK;
+}
+
+template <class T>
+int32_t host_cosine_round(const char* fn, const T* pool_host, int64_t ld, const int64_t* plan_host,
+                          const int32_t* table_host, const tal_cosine_round_info* info, float* out) {
+  if (!pool_host || !plan_host || !out || ld <= 0 || plan_host[0] <= 0)
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
+  if (!cosr_info_matches(table_host, info))
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": info does not describe the table");
+  for (int64_t t = 0; t < plan_host[0]; ++t) {
+    const int64_t* sg = plan_host + kCosHdr + kCosSegWords * t;
+    if (ld < sg[0] + sg[1] * sg[2] * sg[3])
+      return fail(TAL_ERR_INVALID, std::string(fn) + ": row pitch shorter than the plan's parameters");
+  }
+  // every unique pair once through the host cosine, then each ordered pair from its unique pair
+  const CosrTable tb = cosr_table(table_host);
+  std::vector<const T*> a(static_cast<size_t>(info->n_unique)), b(a.size());
+  for (int32_t u = 0; u < info->n_unique; ++u) {
+    a[static_cast<size_t>(u)] = pool_host + tb.models[tb.uniq[2 * u]] * ld;
+    b[static_cast<size_t>(u)] = pool_host + tb.models[tb.uniq[2 * u + 1]] * ld;
+  }
+  std::vector<float> res(a.size());
+  const int32_t rc = host_cosine<T>(fn, a.data(), b.data(), info->n_unique, plan_host, res.data());
+  if (rc != TAL_OK) return rc;
+  for (int32_t j = 0; j < info->n_pairs; ++j) out[j] = res[static_cast<size_t>(tb.map[j])];
+  return TAL_OK;
+}
 
 }  // namespace
 
@@ -6150,58 +6314,22 @@ int32_t tal_host_agg_bf16(const uint16_t* const* x_host, const double* w_host, i
 
 int32_t tal_host_cosine(const float* const* a_host, const float* const* b_host, int32_t n_pairs,
                         const int64_t* plan_host, float* out) {
-  if (!a_host || !b_host || !plan_host || !out || n_pairs <= 0 || plan_host[0] <= 0 || plan_host[1] <= 0 ||
-      plan_host[2] < 1 || plan_host[2] > kCosMaxThreads)
-    return fail(TAL_ERR_INVALID, "tal_host_cosine: bad arguments");
-  for (int j = 0; j < n_pairs; ++j)
-    if (!a_host[j] || !b_host[j]) return fail(TAL_ERR_INVALID, "tal_host_cosine: null model pointer");
-  const int64_t n_seg = plan_host[0], n_out = plan_host[1];
-  int64_t n_chunks = 0;  // chunk words follow the segment words; count them from the segments
-  for (int64_t t = 0; t < n_seg; ++t) {
-    const int64_t* sg = plan_host + kCosHdr + kCosSegWords * t;
-    n_chunks += (sg[1] * sg[3] + sg[6] - 1) / sg[6];
-  }
-  std::vector<float> s_all(static_cast<size_t>(n_out));
-  std::vector<float> means(static_cast<size_t>(n_seg));
-  for (int j = 0; j < n_pairs; ++j) {
-    // outputs chunk by chunk, then the means tensor by tensor, each on up to 16 host threads
-    host_blocks(n_chunks * kHostBlock, [&](int64_t e0, int64_t) {
-      HostCos::outputs(plan_host, e0 / kHostBlock, a_host[j], b_host[j], s_all.data());
-    });
-    host_blocks(n_seg * kHostBlock, [&](int64_t e0, int64_t) {
-      means[static_cast<size_t>(e0 / kHostBlock)] = HostCos::mean(plan_host, e0 / kHostBlock, s_all.data());
-    });
-    float avg = 0.f + means[0];  // 0 + mean_0, += mean_t in parameter order, / len(params)
-    for (int64_t t = 1; t < n_seg; ++t) avg = avg + means[static_cast<size_t>(t)];
-    out[j] = avg / static_cast<float>(n_seg);
-  }
-  g_err.clear();
-  return TAL_OK;
+  return host_cosine<float>("tal_host_cosine", a_host, b_host, n_pairs, plan_host, out);
+}
+
+int32_t tal_host_cosine_bf16(const uint16_t* const* a_host, const uint16_t* const* b_host, int32_t n_pairs,
+                             const int64_t* plan_host, float* out) {
+  return host_cosine<uint16_t>("tal_host_cosine_bf16", a_host, b_host, n_pairs, plan_host, out);
 }
 
 int32_t tal_host_cosine_round(const float* pool_host, int64_t ld, const int64_t* plan_host,
                               const int32_t* table_host, const tal_cosine_round_info* info, float* out) {
-  if (!pool_host || !plan_host || !out || ld <= 0 || plan_host[0] <= 0)
-    return fail(TAL_ERR_INVALID, "tal_host_cosine_round: bad arguments");
-  if (!cosr_info_matches(table_host, info))
-    return fail(TAL_ERR_INVALID, "tal_host_cosine_round: info does not describe the table");
-  for (int64_t t = 0; t < plan_host[0]; ++t) {
-    const int64_t* sg = plan_host + kCosHdr + kCosSegWords * t;
-    if (ld < sg[0] + sg[1] * sg[2] * sg[3])
-      return fail(TAL_ERR_INVALID, "tal_host_cosine_round: row pitch shorter than the plan's parameters");
-  }
-  // every unique pair once through tal_host_cosine, then each ordered pair from its unique pair
-  const CosrTable tb = cosr_table(table_host);
-  std::vector<const float*> a(static_cast<size_t>(info->n_unique)), b(a.size());
-  for (int32_t u = 0; u < info->n_unique; ++u) {
-    a[static_cast<size_t>(u)] = pool_host + tb.models[tb.uniq[2 * u]] * ld;
-    b[static_cast<size_t>(u)] = pool_host + tb.models[tb.uniq[2 * u + 1]] * ld;
-  }
-  std::vector<float> res(a.size());
-  const int32_t rc = tal_host_cosine(a.data(), b.data(), info->n_unique, plan_host, res.data());
-  if (rc != TAL_OK) return rc;
-  for (int32_t j = 0; j < info->n_pairs; ++j) out[j] = res[static_cast<size_t>(tb.map[j])];
-  return TAL_OK;
+  return host_cosine_round<float>("tal_host_cosine_round", pool_host, ld, plan_host, table_host, info, out);
+}
+
+int32_t tal_host_cosine_round_bf16(const uint16_t* pool_host, int64_t ld, const int64_t* plan_host,
+                                   const int32_t* table_host, const tal_cosine_round_info* info, float* out) {
+  return host_cosine_round<uint16_t>("tal_host_cosine_round_bf16", pool_host, ld, plan_host, table_host, info, out);
 }
 
 }  // extern "C"

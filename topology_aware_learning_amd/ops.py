@@ -1088,15 +1088,38 @@ def build_cosine_plan(segments: Sequence[Sequence[int]], threads: int = 1) -> Co
     return CosinePlan(n_seg=len(seg), n_chunks=nch.value, host=blob, threads=int(threads))
 
 
+# element types of the cosine entry points: fp32, or bf16 models widened exactly to fp32 by the
+# loads (tal_agg.h "K2 on bf16 models"); the suffix of the *_bf16 twins
+_COSINE_SUFFIX = {torch.float32: "", torch.bfloat16: "_bf16"}
+
+
+def _cosine_dtype(first: torch.Tensor, what: str) -> torch.dtype:
+    """The dtype of a cosine call, float32 or bfloat16: its first operand's (every operand is then
+    checked against it)."""
+    if not isinstance(first, torch.Tensor):
+        raise TypeError(f"{what}: model 0 must be a torch.Tensor")
+    if first.dtype not in _COSINE_SUFFIX:
+        raise ValueError(f"{what}: models must be float32 or bfloat16 (got {first.dtype})")
+    return first.dtype
+
+
+def _one_dtype(what: str, dtype: torch.dtype, i: int, t: torch.Tensor) -> ValueError:
+    return ValueError(f"{what}: every operand must have one dtype (model 0 is {dtype}, model {i} is {t.dtype})")
+
+
 def cosine(a_list: Sequence[torch.Tensor], b_list: Sequence[torch.Tensor], plan: CosinePlan,
            stream=None) -> torch.Tensor:
-    """K2: cosine_similarity(a_j, b_j) for every pair (flat fp32 parameter arenas), the
-    reference's fp32 value bit for bit."""
+    """K2: cosine_similarity(a_j, b_j) for every pair (flat parameter arenas, all float32 or all
+    bfloat16), the reference's fp32 value bit for bit; for bfloat16 models that of the models
+    widened to fp32 (tal_agg.h "K2 on bf16 models")."""
     if len(a_list) != len(b_list) or not a_list:
         raise ValueError("need matching, non-empty a/b lists")
     dev = a_list[0].device
+    dtype = _cosine_dtype(a_list[0], "cosine")
     for i, t in enumerate(list(a_list) + list(b_list)):
-        _require_gpu(t, f"model {i}", torch.float32)
+        if isinstance(t, torch.Tensor) and t.dtype != dtype:
+            raise _one_dtype("cosine", dtype, i, t)
+        _require_gpu(t, f"model {i}", dtype)
         if t.device != dev:
             raise ValueError("models on different devices")
     if plan.device is None or plan.device.device != dev:
@@ -1106,28 +1129,31 @@ def cosine(a_list: Sequence[torch.Tensor], b_list: Sequence[torch.Tensor], plan:
     hp = plan.host.ctypes.data_as(P64)
     scratch = torch.empty(int(L.tal_cosine_scratch_bytes(hp, len(a_list))), dtype=torch.uint8, device=dev)
     out = torch.empty(len(a_list), dtype=torch.float32, device=dev)
-    check(L.tal_cosine_params(_lib.ptr_array([t.data_ptr() for t in a_list]),
-                              _lib.ptr_array([t.data_ptr() for t in b_list]), len(a_list),
-                              ctypes.c_void_p(plan.device.data_ptr()), hp, plan.n_chunks,
-                              ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                              _stream(dev, stream)))
+    fn = getattr(L, "tal_cosine_params" + _COSINE_SUFFIX[dtype])
+    check(fn(_lib.ptr_array([t.data_ptr() for t in a_list]), _lib.ptr_array([t.data_ptr() for t in b_list]),
+             len(a_list), ctypes.c_void_p(plan.device.data_ptr()), hp, plan.n_chunks,
+             ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream(dev, stream)))
     return out
 
 
 def host_cosine(a_list: Sequence[torch.Tensor], b_list: Sequence[torch.Tensor], plan: CosinePlan) -> torch.Tensor:
-    """K2's arithmetic on the host (tal_host_cosine): cosine_similarity(a_j, b_j) for flat
-    contiguous CPU fp32 parameter arenas, the reference's fp32 value bit for bit, in a process
-    that sees no GPU (similarity.cosine_pairs dispatches on torch.cuda.is_available())."""
+    """K2's arithmetic on the host (tal_host_cosine / tal_host_cosine_bf16): cosine_similarity(a_j,
+    b_j) for flat contiguous CPU parameter arenas, all float32 or all bfloat16, the reference's
+    fp32 value bit for bit (bfloat16: of the widened models, as `cosine`), in a process that sees
+    no GPU (similarity.cosine_pairs dispatches on torch.cuda.is_available())."""
     if len(a_list) != len(b_list) or not a_list:
         raise ValueError("need matching, non-empty a/b lists")
+    dtype = _cosine_dtype(a_list[0], "host_cosine")
     for i, t in enumerate(list(a_list) + list(b_list)):
-        if t.device.type != "cpu" or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"host_cosine: model {i} must be a contiguous CPU float32 tensor")
+        if t.dtype != dtype:
+            raise _one_dtype("host_cosine", dtype, i, t)
+        if t.device.type != "cpu" or not t.is_contiguous():
+            raise ValueError(f"host_cosine: model {i} must be a contiguous CPU float32 or bfloat16 tensor")
     out = torch.empty(len(a_list), dtype=torch.float32)
     L = _lib.load()
-    check(L.tal_host_cosine(_lib.ptr_array([t.data_ptr() for t in a_list]), _lib.ptr_array([t.data_ptr() for t in b_list]),
-                            len(a_list), plan.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                            ctypes.c_void_p(out.data_ptr())))
+    fn = getattr(L, "tal_host_cosine" + _COSINE_SUFFIX[dtype])
+    check(fn(_lib.ptr_array([t.data_ptr() for t in a_list]), _lib.ptr_array([t.data_ptr() for t in b_list]),
+             len(a_list), plan.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.c_void_p(out.data_ptr())))
     return out
 
 
@@ -1170,14 +1196,14 @@ def build_cosine_round(pairs: Sequence[Sequence[int]], pool_rows: int) -> Cosine
 def _cosine_round_args(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan, what: str):
     if not isinstance(pool_f32, torch.Tensor):
         raise TypeError(f"{what}: the pool must be a torch.Tensor")
-    if pool_f32.dtype != torch.float32 or pool_f32.dim() != 2 or pool_f32.shape[0] < 1 or (
+    if pool_f32.dtype not in _COSINE_SUFFIX or pool_f32.dim() != 2 or pool_f32.shape[0] < 1 or (
             pool_f32.shape[1] > 1 and pool_f32.stride(1) != 1):
-        raise ValueError(f"{what}: the pool must be a 2-D float32 tensor with unit column stride")
+        raise ValueError(f"{what}: the pool must be a 2-D float32 or bfloat16 tensor with unit column stride")
     ld = int(pool_f32.stride(0)) if pool_f32.shape[0] > 1 else int(pool_f32.shape[1])
     seg = plan.host[4: 4 + 7 * plan.n_seg].reshape(-1, 7)
     extent = int((seg[:, 0] + seg[:, 1] * seg[:, 2] * seg[:, 3]).max())
     if pool_f32.shape[1] < extent or ld < pool_f32.shape[1]:
-        raise ValueError(f"{what}: the pool's rows ({pool_f32.shape[1]} floats, pitch {ld}) are shorter than the "
+        raise ValueError(f"{what}: the pool's rows ({pool_f32.shape[1]} elements, pitch {ld}) are shorter than the "
                          f"plan's parameters ({extent})")
     table = pairs_or_table if isinstance(pairs_or_table, CosineRound) else build_cosine_round(
         pairs_or_table, pool_f32.shape[0])
@@ -1189,8 +1215,9 @@ def _cosine_round_args(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan,
 def cosine_round(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan, budget_bytes: int = COSINE_ROUND_BUDGET,
                  stream=None) -> torch.Tensor:
     """K2r: cosine_similarity(pool[a_j], pool[b_j]) for every ordered pair of a round, rows of one
-    device pool f32[rows, ld]: every norm once per model, every unordered pair once, one launch
-    sequence on the current (or given) stream.  Bit for bit `cosine` on the same pairs.
+    device pool segment f32[rows, ld] or b16[rows, ld] (float32 or bfloat16; the name is
+    historical): every norm once per model, every unordered pair once, one launch sequence on the
+    current (or given) stream.  Bit for bit `cosine` on the same pairs.
     pairs_or_table: (row_a, row_b) pairs, or a CosineRound of build_cosine_round.  budget_bytes
     bounds the scratch (the unique pairs run in batches under it)."""
     if pool_f32.device.type != "cuda":
@@ -1210,27 +1237,27 @@ def cosine_round(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan, budge
         raise ValueError(f"cosine_round: budget_bytes={int(budget_bytes)} does not hold the norm table and one pair group")
     scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     out = torch.empty(table.n_pairs, dtype=torch.float32, device=dev)
-    check(L.tal_cosine_round(ctypes.c_void_p(pool_f32.data_ptr()), ld, ctypes.c_void_p(plan.device.data_ptr()), hp,
-                             plan.n_chunks, ctypes.c_void_p(table.device.data_ptr()), ht, ctypes.byref(table.info),
-                             ctypes.c_void_p(scratch.data_ptr()), need, ctypes.c_void_p(out.data_ptr()),
-                             _stream(dev, stream)))
+    fn = getattr(L, "tal_cosine_round" + _COSINE_SUFFIX[pool_f32.dtype])
+    check(fn(ctypes.c_void_p(pool_f32.data_ptr()), ld, ctypes.c_void_p(plan.device.data_ptr()), hp, plan.n_chunks,
+             ctypes.c_void_p(table.device.data_ptr()), ht, ctypes.byref(table.info),
+             ctypes.c_void_p(scratch.data_ptr()), need, ctypes.c_void_p(out.data_ptr()), _stream(dev, stream)))
     if stream is not None:  # the scratch is released to the current stream's allocator pool
         scratch.record_stream(stream)
     return out
 
 
 def host_cosine_round(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan) -> torch.Tensor:
-    """cosine_round on a CPU pool (tal_host_cosine_round: tal_host_cosine's arithmetic, every
-    unordered pair once), for a process that sees no GPU."""
+    """cosine_round on a CPU pool, float32 or bfloat16 (tal_host_cosine_round[_bf16]:
+    tal_host_cosine's arithmetic, every unordered pair once), for a process that sees no GPU."""
     if pool_f32.device.type != "cpu":
         raise ValueError("host_cosine_round: the pool must be a CPU tensor")
     ld, table = _cosine_round_args(pool_f32, pairs_or_table, plan, "host_cosine_round")
     out = torch.empty(table.n_pairs, dtype=torch.float32)
     L = _lib.load()
-    check(L.tal_host_cosine_round(ctypes.c_void_p(pool_f32.data_ptr()), ld,
-                                  plan.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                  table.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(table.info),
-                                  ctypes.c_void_p(out.data_ptr())))
+    fn = getattr(L, "tal_host_cosine_round" + _COSINE_SUFFIX[pool_f32.dtype])
+    check(fn(ctypes.c_void_p(pool_f32.data_ptr()), ld, plan.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+             table.host.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(table.info),
+             ctypes.c_void_p(out.data_ptr())))
     return out
 
 

@@ -11,6 +11,11 @@ near-ties and exact fp32 ties included — picks the reference's neighbor
 (tests/golden/near_ties.*).  A tensor mean over >= 32768 outputs (ViT-B/16's patch embedding,
 196,608) is a two-pass parallel sum in torch whose order depends on the intra-op thread count;
 K2 follows torch.get_num_threads() of the calling process (tests/golden/cosine_threads.json).
+
+bf16 models (every parameter bfloat16, as after `model.to(torch.bfloat16)`): the reference has no
+such path; here their cosine similarity is K2's fp32 result for the models widened exactly to
+fp32, bit for bit the reference's cosine_similarity(m1.float(), m2.float()) (include/tal_agg.h
+"K2 on bf16 models").  The kernels read the bf16 segment of the rows in place of the fp32 one.
 """
 from __future__ import annotations
 
@@ -30,35 +35,42 @@ def _param_names(model: nn.Module) -> List[str]:
     return [n for n, _ in model.named_parameters()]
 
 
-def _flat(models: Sequence[nn.Module], layout, device) -> List[torch.Tensor]:
+def _row(pool, r: int, kind: str) -> torch.Tensor:
+    return pool.row_f32(r) if kind == "f32" else pool.row_b16(r)
+
+
+def _flat(models: Sequence[nn.Module], layout, device, kind: str) -> List[torch.Tensor]:
+    """Each model's parameter segment (kind: "f32" or "b16") on `device`."""
     out: List = [None] * len(models)
     rest = []
     for j, m in enumerate(models):
         b = bound_row(m)
         if b is not None and b[0].device == device and b[0].layout == layout:
-            out[j] = b[0].row_f32(b[1])
+            out[j] = _row(b[0], b[1], kind)
         else:
             rest.append(j)
     if rest:
         staged = _stage([models[j] for j in rest], layout, device)
         for k, j in enumerate(rest):
-            out[j] = staged[k]["f32"]
+            out[j] = staged[k][kind]
     return out
 
 
-def _plan_for(layout, names: Sequence[str]) -> ops.CosinePlan:
+def _plan_for(layout, names: Sequence[str]) -> Tuple[ops.CosinePlan, str]:
+    """The layout's cosine plan over `names` and the segment its offsets index ("f32" or "b16")."""
     # a tensor mean over >= 32768 outputs follows torch's parallel order for this process's
     # intra-op thread count, as the reference's own call would (tal_agg.h K2).  The plan holds
     # at most 1024 (tal_cosine_plan_set_threads); a process with more intra-op threads gets
     # 1024's order, which differs from torch's only for a tensor mean over > 1024 x 32768
     # outputs (none in the reference's models: ViT-B/16's largest is 196,608)
     threads = max(1, min(torch.get_num_threads(), 1024))
-    key = (layout.key, tuple(names), threads)
+    kind = layout.param_segment_kind(names)
+    key = (layout.key, tuple(names), threads, kind)
     plan = _plans.get(key)
     if plan is None:
         plan = ops.build_cosine_plan(layout.param_segments(names), threads=threads)
         _plans[key] = plan
-    return plan
+    return plan, kind
 
 
 def cosine_round(pool, pairs: Sequence[Tuple[int, int]], model: nn.Module) -> List[float]:
@@ -72,11 +84,12 @@ def cosine_round(pool, pairs: Sequence[Tuple[int, int]], model: nn.Module) -> Li
     layout = pool.layout
     if layout_of_module(model) != layout:
         raise ValueError("cosine_round: the model does not have the pool's layout")
-    plan = _plan_for(layout, _param_names(model))
+    plan, kind = _plan_for(layout, _param_names(model))
+    seg = pool.f32 if kind == "f32" else pool.b16
     if not torch.cuda.is_available():
-        return [float(x) for x in ops.host_cosine_round(pool.f32, pairs, plan).tolist()]
+        return [float(x) for x in ops.host_cosine_round(seg, pairs, plan).tolist()]
     with torch.cuda.device(pool.device):
-        return [float(x) for x in ops.cosine_round(pool.f32, pairs, plan).cpu().tolist()]
+        return [float(x) for x in ops.cosine_round(seg, pairs, plan).cpu().tolist()]
 
 
 def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
@@ -84,9 +97,9 @@ def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
     if not others:
         return []
     layout = layout_of_module(model)
-    plan = _plan_for(layout, _param_names(model))
+    plan, kind = _plan_for(layout, _param_names(model))
     if not torch.cuda.is_available():  # no GPU (config 1's setting): the library's host K2
-        flats = _host_flat([model, *others], layout)
+        flats = _host_flat([model, *others], layout, kind)
         return [float(x) for x in ops.host_cosine([flats[0]] * len(others), flats[1:], plan).tolist()]
     device = _device_for([model, *others])
     b0 = bound_row(model)
@@ -98,25 +111,26 @@ def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
         pool = b0[0]
         with torch.cuda.device(pool.device):
             rows = mp[0].rows_for(mp[1], bounds)
-            res = ops.cosine([pool.row_f32(b0[1])] * len(others), [pool.row_f32(r) for r in rows], plan)
+            res = ops.cosine([_row(pool, b0[1], kind)] * len(others), [_row(pool, r, kind) for r in rows], plan)
             return [float(x) for x in res.cpu().tolist()]
-    flats = _flat([model, *others], layout, device)
+    flats = _flat([model, *others], layout, device, kind)
     res = ops.cosine([flats[0]] * len(others), flats[1:], plan)
     return [float(x) for x in res.cpu().tolist()]
 
 
-def _host_flat(models: Sequence[nn.Module], layout) -> List[torch.Tensor]:
-    """Each model's fp32 segment as a contiguous CPU tensor: a pinned-row view when the model
-    is bound to a host row, else its fp32 entries concatenated in state_dict order."""
+def _host_flat(models: Sequence[nn.Module], layout, kind: str) -> List[torch.Tensor]:
+    """Each model's parameter segment (kind: "f32" or "b16") as a contiguous CPU tensor: a
+    pinned-row view when the model is bound to a host row, else the segment's entries
+    concatenated in state_dict order."""
     out = []
     for j, m in enumerate(models):
         b = bound_row(m)
         if b is not None and b[0].device.type == "cpu" and b[0].layout == layout:
-            out.append(b[0].row_f32(b[1]))
+            out.append(_row(b[0], b[1], kind))
             continue
         sd = m.state_dict()
         layout.check_compatible(sd, f"model {j}")
         if any(t.device.type != "cpu" for t in sd.values()):
             raise RuntimeError("no GPU is visible, but a model has tensors off the CPU")
-        out.append(torch.cat([t.detach().reshape(-1) for t in layout.flatten_cat(sd, "f32")]))
+        out.append(torch.cat([t.detach().reshape(-1) for t in layout.flatten_cat(sd, kind)]))
     return out
