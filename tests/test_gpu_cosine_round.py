@@ -131,6 +131,49 @@ def test_round_groups_and_batches(cuda):
         ops.cosine_round(pool, table, plan, budget_bytes=fixed)
 
 
+# the direct kinds: row (B == 1), element (I == 1) and columns with B >= 32; the last shape's one
+# chunk is a streamed one
+_DIRECT_SHAPES = [(33, 7, 1), (5, 13, 1), (3, 100, 1), (2, 1030, 1), (300, 1, 1), (3, 50, 32), (2, 37, 40), (2, 513, 9)]
+
+
+@pytest.fixture(scope="module")
+def star_rows():
+    """One plan of the direct shapes at odd offsets; 9 models as float32 rows, and 9 as bf16 bit
+    patterns with their exact float32 values (what the oracle runs on)."""
+    segs, off = [], 3
+    for a, i, b in _DIRECT_SHAPES:
+        segs.append((off, a, i, b))
+        off += a * i * b + 5
+    f32 = _models(np.random.default_rng(31), segs, 9)
+    b16 = [oracle.f32_to_bf16(r) for r in _models(np.random.default_rng(32), segs, 9)]
+    return segs, {"float32": (f32, f32), "bfloat16": (b16, [oracle.bf16_to_f32(r).astype(np.float32) for r in b16])}
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+@pytest.mark.parametrize("k", range(1, 9))
+def test_round_star_group_sizes(cuda, star_rows, k, dtype):
+    """One row against k others, one pair group of k pairs: the row kind takes a group's pairs
+    four, two and one at a time, so k = 5, 6, 7 are its 4 + 1, 4 + 2 and 4 + 2 + 1 paths, and
+    ops.cosine takes every pair through the one-pair form of the same function.  Both are the
+    oracle's bits for every pair."""
+    segs, by_dtype = star_rows
+    rows, wide = by_dtype[dtype]
+    n, row_of = len(rows[0]), [4, 0, 7, 2, 8, 1, 6, 3, 5]
+    pool = torch.zeros(9, (n + 29) | 1, dtype=getattr(torch, dtype), device=cuda)[:, :n]
+    for m, r in enumerate(row_of):
+        t = torch.from_numpy(rows[m].view(np.int16)).view(torch.bfloat16) if dtype == "bfloat16" else torch.from_numpy(rows[m])
+        pool[r].copy_(t.to(cuda))
+    pairs = [(0, m) for m in range(1, k + 1)]
+    on_pool = [(row_of[a], row_of[b]) for a, b in pairs]
+    plan = ops.build_cosine_plan(segs)
+    table = ops.build_cosine_round(on_pool, 9)
+    assert table.info.n_groups == 1 and table.info.max_group == k
+    want = _bits(_refs(wide, segs, pairs))
+    assert _bits(ops.cosine_round(pool, table, plan).cpu().numpy()) == want
+    per_call = ops.cosine([pool[a] for a, _ in on_pool], [pool[b] for _, b in on_pool], plan)
+    assert _bits(per_call.cpu().numpy()) == want
+
+
 @pytest.mark.parametrize("threads", [1, 3, 8])
 def test_round_thread_word(cuda, threads):
     """A tensor mean over 196,608 outputs follows torch's two-pass order for the plan's thread

@@ -3068,11 +3068,17 @@ struct CosPairs {
   const T* b[kCosMaxPairs];
 };
 
-__device__ __forceinline__ int64_t cos_ceil_log2(int64_t x) {
-  int64_t r = 0;
-  while ((int64_t{1} << r) < x) ++r;
-  return r;
-}
+// K2's model slots: one a shared by all pairs (slot 0 = a, 1 + p = b_p) or one per pair (2 p = a_p,
+// 2 p + 1 = b_p).  The norms of a call are stored by slot.
+__device__ __forceinline__ int cos_slot_a(int same_a, int p) { return same_a ? 0 : 2 * p; }
+__device__ __forceinline__ int cos_slot_b(int same_a, int p) { return same_a ? 1 + p : 2 * p + 1; }
+
+// the model of slot sl counted from pair p0 on.  A macro, so that the kernel argument pr is
+// indexed in place: through an inlined function taking `const CosPairs<T>&`, k_cos_col_norms
+// copied the whole argument to scratch
+#define TAL_COS_SLOT_MODEL(pr, same_a, p0, sl)                          \
+  ((same_a) ? ((sl) == 0 ? (pr).a[p0] : (pr).b[(p0) + (sl) - 1])        \
+            : (((sl) & 1) ? (pr).b[(p0) + ((sl) >> 1)] : (pr).a[(p0) + ((sl) >> 1)]))
 
 // torch multi_row_sum: NR interleaved streams load(i, k), a 4-level cascade whose level
 // boundaries depend only on i (so one column of a 32-column chunk is the NR = 1 case).  The NR
@@ -3081,7 +3087,7 @@ __device__ __forceinline__ int64_t cos_ceil_log2(int64_t x) {
 template <int NR, int kU = 8, class LoadAll>
 __device__ __forceinline__ void cos_multi_row_v(LoadAll load_all, int64_t size, float* out) {
   constexpr int kL = 4;
-  const int64_t lp = cos_ceil_log2(size) / kL > 4 ? cos_ceil_log2(size) / kL : 4;
+  const int64_t lp = cos_lp(size);
   const int64_t step = int64_t{1} << lp;
   const int64_t mask0 = step - 1;
   float acc[kL][NR];
@@ -3137,37 +3143,30 @@ __device__ __forceinline__ void cos_multi_row(Load load, int64_t size, float* ou
   }, size, out);
 }
 
-// torch row_sum: 4 interleaved partial sums (element 4 i + k), the remainder into partial 0,
-// partials 1..3 added to partial 0 in order
-template <class Load>
-__device__ __forceinline__ float cos_row_sum(Load load, int64_t size) {
-  float ps[4];
-  const int64_t si = size / 4;
-  cos_multi_row<4>([&](int64_t i, int k) { return load(i * 4 + k); }, si, ps);
-  for (int64_t i = si * 4; i < size; ++i) ps[0] = __fadd_rn(ps[0], load(i));
-  for (int k = 1; k < 4; ++k) ps[0] = __fadd_rn(ps[0], ps[k]);
-  return ps[0];
-}
-
-// row_sum of the P product rows qa(i) qb(i, p) that share the factor qa: stream 4 p + k of the
-// cascade is row_sum's partial k of pair p, and qa(i) is computed once for the P pairs.  Each
-// out[p] is bit for bit cos_row_sum of pair p's own products (the streams do not interact).
-template <int P, int kU, class QA, class QB>
-__device__ __forceinline__ void cos_row_sum_pairs(QA qa, QB qb, int64_t size, float* out) {
+// torch row_sum of P rows at once.  One row: 4 interleaved partial sums (element 4 i + k), the
+// remainder into partial 0, partials 1..3 added to partial 0 in order.  terms(i, v) gives element
+// i of the P rows (v[p]), so a factor they share - the quotient of the row that P pairs of the
+// round form share - is computed once; stream 4 p + k of the cascade is partial k of row p.  Each
+// out[p] is bit for bit cos_row_sum of row p's own elements (the streams do not interact), and
+// cos_row_sum_pairs<1, 8> is cos_row_sum stream for stream.
+template <int P, int kU, class Terms>
+__device__ __forceinline__ void cos_row_sum_pairs(Terms terms, int64_t size, float* out) {
   float ps[4 * P];
   const int64_t si = size / 4;
   cos_multi_row_v<4 * P, kU>([&](int64_t i, float* v) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float a = qa(i * 4 + k);
+      float t[P];
+      terms(i * 4 + k, t);
 #pragma unroll
-      for (int p = 0; p < P; ++p) v[4 * p + k] = __fmul_rn(a, qb(i * 4 + k, p));
+      for (int p = 0; p < P; ++p) v[4 * p + k] = t[p];
     }
   }, si, ps);
   for (int64_t i = si * 4; i < size; ++i) {
-    const float a = qa(i);
+    float t[P];
+    terms(i, t);
 #pragma unroll
-    for (int p = 0; p < P; ++p) ps[4 * p] = __fadd_rn(ps[4 * p], __fmul_rn(a, qb(i, p)));
+    for (int p = 0; p < P; ++p) ps[4 * p] = __fadd_rn(ps[4 * p], t[p]);
   }
 #pragma unroll
   for (int p = 0; p < P; ++p) {
@@ -3175,6 +3174,13 @@ __device__ __forceinline__ void cos_row_sum_pairs(QA qa, QB qb, int64_t size, fl
     for (int k = 1; k < 4; ++k) ps[4 * p] = __fadd_rn(ps[4 * p], ps[4 * p + k]);
     out[p] = ps[4 * p];
   }
+}
+
+template <class Load>
+__device__ __forceinline__ float cos_row_sum(Load load, int64_t size) {
+  float r[1];
+  cos_row_sum_pairs<1, 8>([&](int64_t i, float* v) { v[0] = load(i); }, size, r);
+  return r[0];
 }
 
 // correctly rounded sqrt (llvm.sqrt.f32 under HIP's default correctly-rounded divide/sqrt);
@@ -3209,89 +3215,253 @@ __device__ __forceinline__ float cos_group_fold(float first, float v, int gbase)
   return r;
 }
 
+// ---- the direct kinds: one function per torch reduction ------------------------------------
+// Shared by K2 (k_cosine_outputs: a pair's two models at once, NM = 2, P = 1) and its round form
+// (k_cosr_norms: one model, NM = 1; k_cosr_prods: P pairs that share a row), so the two forms
+// are bitwise equal by construction.  The one exception is K2's row norm, which k_cosine_outputs
+// keeps written out for its two models (the reason is there).
+
+// torch's serial full sum of P rows of n terms each (terms(i, v): v[p] = term i of row p), without
+// the store's 0 +: scalar_inner_sum below 8 terms (one row_sum), else vectorized_inner_sum: lane
+// l sums terms 8 i + l by row_sum, then the scalar tail from 0, then the lanes in order.  One
+// 8-thread group (threads gbase .. gbase + 7 of the wave, this one its lane l) per P rows, `live`
+// if the group has rows at all; out[p] is valid in the group's thread 0.  Every thread of the
+// wave calls it.
+template <int P, int kU, class Terms>
+__device__ __forceinline__ void cos_inner_sum_pairs(Terms terms, int64_t n, bool live, int l, int gbase, float* out) {
+  if (n < kCosVw) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) out[p] = 0.f;
+    if (l == 0 && live) cos_row_sum_pairs<P, kU>(terms, n, out);
+    return;
+  }
+  const int64_t nv = n / kCosVw;
+  float lane_sum[P], tail[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) lane_sum[p] = tail[p] = 0.f;
+  if (live) cos_row_sum_pairs<P, kU>([&](int64_t i, float* v) { terms(i * kCosVw + l, v); }, nv, lane_sum);
+  if (l == 0 && live)
+    for (int64_t k = nv * kCosVw; k < n; ++k) {
+      float t[P];
+      terms(k, t);
+#pragma unroll
+      for (int p = 0; p < P; ++p) tail[p] = __fadd_rn(tail[p], t[p]);
+    }
+#pragma unroll
+  for (int p = 0; p < P; ++p) out[p] = cos_group_fold(tail[p], lane_sum[p], gbase);
+}
+
+// the same sum of the array s[0 .. n) by the wave's threads 0 .. 7 (l: the thread's lane in the
+// wave), for k_cosine_means; valid in thread 0
+__device__ __forceinline__ float cos_inner_sum(const float* s, int64_t n, int l) {
+  float r[1];
+  cos_inner_sum_pairs<1, 8>([&](int64_t i, float* v) { v[0] = s[i]; }, n, l < kCosVw, l, 0, r);
+  return r[0];
+}
+
+// Element kind (a 1-D parameter unsqueezed to [n, 1]): the clamped norm |x|, and the one product
+// with the store's 0 + (q1 = x1 / n1, which the round form divides once for a group's pairs)
+__device__ __forceinline__ float cos_norm_elem(float x) { return cos_clamp(cos_sqrt_rn(__fmaf_rn(x, x, 0.f))); }
+__device__ __forceinline__ float cos_prod_elem(float q1, float x2, float n2) {
+  return __fadd_rn(0.f, __fmul_rn(q1, __fdiv_rn(x2, n2)));
+}
+
+// Column kind (B > 1: the reduced dim strided by B), the clamped norms of column x[m] of NM
+// models: torch NormTwoOps, an fma chain in index order.  The loads come in batches of 8, a
+// batch's loads of all NM models before its fma chains.
+template <int NM, class T>
+__device__ __forceinline__ void cos_norm_col(const T* const* x, int64_t I, int64_t B, float* n) {
+  float acc[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) acc[m] = 0.f;
+  int64_t i0 = 0;
+  for (; i0 + 8 <= I; i0 += 8) {
+    float v[8][NM];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int m = 0; m < NM; ++m) v[u][m] = cos_ld(x[m], (i0 + u) * B);
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int m = 0; m < NM; ++m) acc[m] = __fmaf_rn(v[u][m], v[u][m], acc[m]);
+  }
+  for (int64_t i = i0; i < I; ++i)
+#pragma unroll
+    for (int m = 0; m < NM; ++m) acc[m] = __fmaf_rn(cos_ld(x[m], i * B), cos_ld(x[m], i * B), acc[m]);
+#pragma unroll
+  for (int m = 0; m < NM; ++m) n[m] = cos_clamp(cos_sqrt_rn(acc[m]));
+}
+
+// Column kind, one column's products (x1 / n1) (x2 / n2) summed over i, column k of B: the
+// columns in chunks of 32 share one cascade (multi_row_sum, a column is one of its streams), the
+// chunks of 8 and the single columns after them are a row_sum each; then the store's 0 +
+template <class T>
+__device__ __forceinline__ float cos_prod_col(const T* x1, float n1, const T* x2, float n2, int64_t I, int64_t B,
+                                              int64_t k) {
+  auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i * B), n1), __fdiv_rn(cos_ld(x2, i * B), n2)); };
+  float r;
+  if (B >= kCosVw && k < B / 32 * 32) {
+    float c[1];
+    cos_multi_row<1>([&](int64_t i, int) { return prod(i); }, I, c);
+    r = c[0];
+  } else {
+    r = cos_row_sum(prod, I);
+  }
+  return __fadd_rn(0.f, r);
+}
+
+// Row kind (B == 1, I > 1: the reduced dim contiguous; 8 threads per row, one per lane of torch's
+// vector accumulators), the clamped norms of row x[m] of NM models: vector_norm's reduce-lastdim
+// kernel - the lane accumulators fma over whole vectors (loads in batches of 8 vectors, as
+// cos_norm_col's), the lane fold in lane order started by lane 0, then the tail: groups of 4 as
+// square-then-add, the rest fused.  n[m] is valid in thread 0 of a live group (0 elsewhere);
+// every thread of the wave calls it.
+template <int NM, class T>
+__device__ __forceinline__ void cos_norm_row(const T* const* x, int64_t I, bool live, int l, int gbase, float* n) {
+  const int64_t vec_end = I - I % kCosVw;
+  float acc[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) acc[m] = 0.f;
+  if (live) {
+    int64_t d = l;
+    for (; d + 7 * kCosVw < vec_end; d += 8 * kCosVw) {
+      float v[8][NM];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int m = 0; m < NM; ++m) v[u][m] = cos_ld(x[m], d + u * kCosVw);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int m = 0; m < NM; ++m) acc[m] = __fmaf_rn(v[u][m], v[u][m], acc[m]);
+    }
+    for (; d < vec_end; d += kCosVw)
+#pragma unroll
+      for (int m = 0; m < NM; ++m) acc[m] = __fmaf_rn(cos_ld(x[m], d), cos_ld(x[m], d), acc[m]);
+  }
+  float t[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) t[m] = __shfl(acc[m], gbase, 64);
+  for (int j = 1; j < kCosVw; ++j)
+#pragma unroll
+    for (int m = 0; m < NM; ++m) t[m] = __fadd_rn(t[m], __shfl(acc[m], gbase + j, 64));
+#pragma unroll
+  for (int m = 0; m < NM; ++m) n[m] = 0.f;
+  if (l == 0 && live) {
+    int64_t d = vec_end;
+    const int64_t sep = (I - vec_end) / 4 * 4;
+    for (int64_t e = 0; e < sep; ++e, ++d)
+#pragma unroll
+      for (int m = 0; m < NM; ++m) t[m] = __fadd_rn(t[m], __fmul_rn(cos_ld(x[m], d), cos_ld(x[m], d)));
+    for (; d < I; ++d)
+#pragma unroll
+      for (int m = 0; m < NM; ++m) t[m] = __fmaf_rn(cos_ld(x[m], d), cos_ld(x[m], d), t[m]);
+#pragma unroll
+    for (int m = 0; m < NM; ++m) n[m] = cos_clamp(cos_sqrt_rn(t[m]));
+  }
+}
+
+// Row kind, the products of P pairs that share row x1: torch's inner sum (cos_inner_sum_pairs)
+// of each pair's (x1 / n1) (x2[p] / n2[p]), x1's element loaded and divided once for the P
+// pairs, kU indices per load batch; then the store's 0 +.  out[p] is valid in thread 0 of a live
+// group; every thread of the wave calls it.
+// (K2 measured the reciprocal division of the streamed column kernels here, and it does not pay:
+// with per-element range checks the row tensors ran 0.255 -> 0.335 ms for ResNet-50's, with one
+// check per row (bounds of |x| gathered in the norm loop, a templated product phase) 0.259 ms; the
+// row kind is bound by its loads, not its divisions; profiles/r06/r06k/r06k14, r06k17)
+template <int P, int kU, class T>
+__device__ __forceinline__ void cos_prod_row(const T* x1, float n1, const T* const* x2, const float* n2, int64_t I,
+                                             bool live, int l, int gbase, float* out) {
+  float r[P];
+  cos_inner_sum_pairs<P, kU>([&](int64_t i, float* v) {
+    const float q1 = __fdiv_rn(cos_ld(x1, i), n1);
+#pragma unroll
+    for (int p = 0; p < P; ++p) v[p] = __fmul_rn(q1, __fdiv_rn(cos_ld(x2[p], i), n2[p]));
+  }, I, live, l, gbase, r);
+#pragma unroll
+  for (int p = 0; p < P; ++p) out[p] = __fadd_rn(0.f, r[p]);
+}
+
+// The head of a (direct chunk, item) grid: workgroup 8 k + x takes item k % cnt of direct chunk
+// 8 (k / cnt) + x.  Dispatch deals workgroups round-robin over the 8 XCDs, so a chunk's items run
+// one after another on XCD x and meet in its L2: K2's pairs (all but the first find the chunk's
+// `a` rows there), or the round form's models or pair groups (a group's pairs share a row).
+// ch, sg: the chunk's and its tensor's plan words.  False: the workgroup is past the last chunk
+// (the grid is a multiple of 8 chunks).
+__device__ __forceinline__ bool cos_direct_chunk(const int64_t* __restrict__ plan, int n_seg, int cnt, int64_t n_direct,
+                                                 int* item, const int64_t** ch, const int64_t** sg) {
+  const int64_t kq = blockIdx.x >> 3;
+  *item = static_cast<int>(kq % cnt);
+  const int64_t c = kq / cnt * 8 + (blockIdx.x & 7);
+  if (c >= n_direct) return false;
+  *ch = plan + kCosHdr + kCosSegWords * static_cast<int64_t>(n_seg) +
+        kCosChunkWords * (plan[3] + c);  // after the streamed chunks
+  *sg = plan + kCosHdr + kCosSegWords * (*ch)[0];
+  return true;
+}
+
+// Row kind, 8 threads per row: this thread's row q of the chunk's rows first .. first + count
+// (live: it is one of them), its lane l in the 8-thread group, the group's first lane in the wave
+struct CosRowThread {
+  int64_t q;
+  bool live;
+  int l, gbase;
+};
+
+__device__ __forceinline__ CosRowThread cos_row_thread(int64_t first, int64_t count) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  CosRowThread r;
+  r.q = first + tid / kCosVw;
+  r.live = r.q < first + count;
+  r.l = lane & (kCosVw - 1);
+  r.gbase = lane & ~(kCosVw - 1);
+  return r;
+}
+
+// K2's direct chunks: one workgroup per (chunk, pair); both norms, then the products
 template <class T>
 __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs<T> pr, const int64_t* __restrict__ plan,
                                                               int n_seg, int cnt, int64_t n_direct,
                                                               float* __restrict__ s_all) {
-  // XCD-aware order: dispatch deals workgroups round-robin over the 8 XCDs, so workgroup 8 k + x
-  // takes pair k % cnt of direct chunk 8 (k / cnt) + x: a chunk's pairs run one after another
-  // on XCD x, and all but the first find the chunk's `a` rows in that XCD's L2
-  const int64_t kq = blockIdx.x >> 3;
-  const int pair = static_cast<int>(kq % cnt);
-  const int64_t c = kq / cnt * 8 + (blockIdx.x & 7);
-  if (c >= n_direct) return;
-  const int64_t n_out = plan[1];
-  const int64_t* ch = plan + kCosHdr + kCosSegWords * static_cast<int64_t>(n_seg) +
-                      kCosChunkWords * (plan[3] + c);  // after the streamed chunks
-  const int64_t* sg = plan + kCosHdr + kCosSegWords * ch[0];
-  const int64_t first = ch[1], count = ch[2];
-  const int64_t I = sg[2], B = sg[3];
+  int pair;
+  const int64_t *ch, *sg;
+  if (!cos_direct_chunk(plan, n_seg, cnt, n_direct, &pair, &ch, &sg)) return;
+  const int64_t first = ch[1], count = ch[2], I = sg[2], B = sg[3];
   const int kind = static_cast<int>(sg[5]);
   const T* a = pr.a[pair] + sg[0];
   const T* b = pr.b[pair] + sg[0];
-  float* s = s_all + static_cast<int64_t>(pair) * n_out + sg[4];
-  const int tid = threadIdx.x;
-  if (kind == kCosElem) {  // 1-D parameter unsqueezed to [n, 1]: norm |x|, one product
-    const int64_t q = first + tid;
-    if (q < first + count) {
-      const float x = cos_ld(a, q), y = cos_ld(b, q);
-      const float n1 = cos_clamp(cos_sqrt_rn(__fmaf_rn(x, x, 0.f)));
-      const float n2 = cos_clamp(cos_sqrt_rn(__fmaf_rn(y, y, 0.f)));
-      s[q] = __fadd_rn(0.f, __fmul_rn(__fdiv_rn(x, n1), __fdiv_rn(y, n2)));
-    }
-    return;
-  }
-  if (kind == kCosCol) {  // B > 1: reduced dim strided by B; one thread per (row, column)
-    const int64_t q = first + tid;
+  float* s = s_all + static_cast<int64_t>(pair) * plan[1] + sg[4];
+  if (kind == kCosElem) {
+    const int64_t q = first + threadIdx.x;
     if (q >= first + count) return;
-    const int64_t o = q / B, k = q % B;
-    const T* x1 = a + o * I * B + k;
-    const T* x2 = b + o * I * B + k;
-    float m1 = 0.f, m2 = 0.f;  // torch NormTwoOps: fma in index order (loads in batches of 8)
-    int64_t i0 = 0;
-    for (; i0 + 8 <= I; i0 += 8) {
-      float u1[8], u2[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        u1[u] = cos_ld(x1, (i0 + u) * B);
-        u2[u] = cos_ld(x2, (i0 + u) * B);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        m1 = __fmaf_rn(u1[u], u1[u], m1);
-        m2 = __fmaf_rn(u2[u], u2[u], m2);
-      }
-    }
-    for (int64_t i = i0; i < I; ++i) {
-      m1 = __fmaf_rn(cos_ld(x1, i * B), cos_ld(x1, i * B), m1);
-      m2 = __fmaf_rn(cos_ld(x2, i * B), cos_ld(x2, i * B), m2);
-    }
-    const float n1 = cos_clamp(cos_sqrt_rn(m1)), n2 = cos_clamp(cos_sqrt_rn(m2));
-    auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i * B), n1), __fdiv_rn(cos_ld(x2, i * B), n2)); };
-    float r;
-    if (B >= kCosVw && k < B / 32 * 32) {  // columns in chunks of 32 share one cascade
-      float c[1];
-      cos_multi_row<1>([&](int64_t i, int) { return prod(i); }, I, c);
-      r = c[0];
-    } else {  // chunks of 8 and single columns: row_sum per column
-      r = cos_row_sum(prod, I);
-    }
-    s[q] = __fadd_rn(0.f, r);
+    const float x = cos_ld(a, q), y = cos_ld(b, q);
+    s[q] = cos_prod_elem(__fdiv_rn(x, cos_norm_elem(x)), y, cos_norm_elem(y));
     return;
   }
-  // kCosRow (B == 1, I > 1): reduced dim contiguous; 8 threads per row (torch's vector lanes)
-  const int lane = tid & 63;
-  const int l = lane & (kCosVw - 1);
-  const int gbase = lane & ~(kCosVw - 1);
-  const int64_t q = first + tid / kCosVw;
-  const bool live = q < first + count;
-  const T* x1 = a + (live ? q : first) * I;
-  const T* x2 = b + (live ? q : first) * I;
+  if (kind == kCosCol) {  // one thread per (row, column)
+    const int64_t q = first + threadIdx.x;
+    if (q >= first + count) return;
+    const int64_t k = q % B, e = q / B * I * B + k;
+    const T* x[2] = {a + e, b + e};
+    float n[2];
+    cos_norm_col<2>(x, I, B, n);
+    s[q] = cos_prod_col(x[0], n[0], x[1], n[1], I, B, k);
+    return;
+  }
+  const CosRowThread t = cos_row_thread(first, count);
+  const int64_t e = (t.live ? t.q : first) * I;
+  const T* x1 = a + e;
+  const T* x2 = b + e;
+  // The two models' norms are cos_norm_row's operations written out for two models, not
+  // cos_norm_row<2>: through the template the fp32 kernel compiles to 112 VGPRs instead of 129
+  // and its product loop no longer issues its 64 loads ahead of the divisions (36, then one per
+  // wait), and 8 ViT-B/16 pairs ran 1.64-1.65 ms against 1.49, 8 ResNet-50 pairs 0.396-0.404
+  // against 0.371-0.378 (profiles/r08/cosine_refactor).  A change here goes into cos_norm_row too.
   const int64_t vec_end = I - I % kCosVw;
-  // vector_norm (reduce-lastdim kernel): lane accumulators fma over whole vectors
   float m1 = 0.f, m2 = 0.f;
-  if (live) {  // loads in batches of 8 vectors, fma in index order
-    int64_t d = l;
+  if (t.live) {  // loads in batches of 8 vectors, fma in index order
+    int64_t d = t.l;
     for (; d + 7 * kCosVw < vec_end; d += 8 * kCosVw) {
       float u1[8], u2[8];
 #pragma unroll
@@ -3310,16 +3480,16 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs<T> pr, co
       m2 = __fmaf_rn(cos_ld(x2, d), cos_ld(x2, d), m2);
     }
   }
-  float t1 = __shfl(m1, gbase, 64), t2 = __shfl(m2, gbase, 64);  // lane 0 starts the fold
+  float t1 = __shfl(m1, t.gbase, 64), t2 = __shfl(m2, t.gbase, 64);  // lane 0 starts the fold
   for (int j = 1; j < kCosVw; ++j) {
-    t1 = __fadd_rn(t1, __shfl(m1, gbase + j, 64));
-    t2 = __fadd_rn(t2, __shfl(m2, gbase + j, 64));
+    t1 = __fadd_rn(t1, __shfl(m1, t.gbase + j, 64));
+    t2 = __fadd_rn(t2, __shfl(m2, t.gbase + j, 64));
   }
   float n1 = 0.f, n2 = 0.f;
-  if (l == 0 && live) {  // the tail: groups of 4 as square-then-add, the rest fused
+  if (t.l == 0 && t.live) {  // the tail: groups of 4 as square-then-add, the rest fused
     int64_t d = vec_end;
     const int64_t sep = (I - vec_end) / 4 * 4;
-    for (int64_t e = 0; e < sep; ++e, ++d) {
+    for (int64_t i = 0; i < sep; ++i, ++d) {
       t1 = __fadd_rn(t1, __fmul_rn(cos_ld(x1, d), cos_ld(x1, d)));
       t2 = __fadd_rn(t2, __fmul_rn(cos_ld(x2, d), cos_ld(x2, d)));
     }
@@ -3330,28 +3500,12 @@ __global__ __launch_bounds__(kCosBlock) void k_cosine_outputs(CosPairs<T> pr, co
     n1 = cos_clamp(cos_sqrt_rn(t1));
     n2 = cos_clamp(cos_sqrt_rn(t2));
   }
-  n1 = __shfl(n1, gbase, 64);
-  n2 = __shfl(n2, gbase, 64);
-  // (the reciprocal division of the streamed column kernels does not pay here: with per-element
-  // range checks the row tensors ran 0.255 -> 0.335 ms for ResNet-50's, with one check per row
-  // (bounds of |x| gathered in the norm loop, a templated product phase) 0.259 ms; the row kind
-  // is bound by its loads, not its divisions; profiles/r06/r06k/r06k14, r06k17)
-  auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i), n1), __fdiv_rn(cos_ld(x2, i), n2)); };
-  if (I < kCosVw) {  // scalar_inner_sum
-    if (l == 0 && live) s[q] = __fadd_rn(0.f, cos_row_sum(prod, I));
-    return;
-  }
-  // vectorized_inner_sum: lane l sums elements 8 i + l by row_sum; then the scalar tail from 0,
-  // then the lanes in order
-  const int64_t nv = I / kCosVw;
-  const float lane_sum = live ? cos_row_sum([&](int64_t i) { return prod(i * kCosVw + l); }, nv) : 0.f;
-  float tail = 0.f;
-  if (l == 0 && live)
-    for (int64_t k2 = nv * kCosVw; k2 < I; ++k2) tail = __fadd_rn(tail, prod(k2));
-  const float fin = cos_group_fold(tail, lane_sum, gbase);
-  if (l == 0 && live) s[q] = __fadd_rn(0.f, fin);
+  n1 = __shfl(n1, t.gbase, 64);
+  n2 = __shfl(n2, t.gbase, 64);
+  float r[1];
+  cos_prod_row<1, 8>(x1, n1, &x2, &n2, I, t.live, t.l, t.gbase, r);
+  if (t.l == 0 && t.live) s[t.q] = r[0];
 }
-
 
 // ---- streamed column chunks (see kColIc) ---------------------------------------------------
 struct ColChunk {
@@ -3505,11 +3659,8 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_norms(CosPairs<T> pr, c
   const T* gm[kColModels];
 #pragma unroll
   for (int m = 0; m < kColModels; ++m) {
-    // model slot s: one a shared by all pairs (slot 0 = a, 1 + p = b_p) or one per pair (2 p = a_p,
-    // 2 p + 1 = b_p); the kernel argument is indexed in place (a reference to it would copy it
-    // to scratch)
     const int sl = m0 + min(m, nmod - 1);
-    gm[m] = same_a ? (sl == 0 ? pr.a[0] : pr.b[sl - 1]) : ((sl & 1) ? pr.b[sl >> 1] : pr.a[sl >> 1]);
+    gm[m] = TAL_COS_SLOT_MODEL(pr, same_a, 0, sl);
   }
   cos_col_norms_body(k, gm, nmod, m0, plan[1], lds, nrm);
 }
@@ -3630,33 +3781,20 @@ __global__ __launch_bounds__(kColThreads) void k_cos_col_prods(CosPairs<T> pr, c
   const T* gm[kColModels];
 #pragma unroll
   for (int m = 0; m < kColModels; ++m) {
-    const int mm = min(m, nmod - 1);
-    gm[m] = same_a ? (mm == 0 ? pr.a[p0] : pr.b[p0 + mm - 1]) : ((mm & 1) ? pr.b[p0 + (mm >> 1)] : pr.a[p0 + (mm >> 1)]);
+    const int sl = min(m, nmod - 1);
+    gm[m] = TAL_COS_SLOT_MODEL(pr, same_a, p0, sl);
   }
+#undef TAL_COS_SLOT_MODEL
   const int t = threadIdx.x, g = t / k.Cf, c = t - g * k.Cf;
   const bool live = g < np && c < k.C;
-  const int ma = same_a ? 0 : 2 * g, mb = same_a ? 1 + g : 2 * g + 1;
   const int64_t n_out = plan[1];
   float na = 1.f, nb = 1.f;
-  if (live) {
-    const int sa = same_a ? 0 : 2 * (p0 + g), sb = same_a ? 1 + p0 + g : 2 * (p0 + g) + 1;
-    na = nrm[sa * n_out + k.out0 + c];
-    nb = nrm[sb * n_out + k.out0 + c];
+  if (live) {  // the norms lie by the call's slots, the LDS models by the workgroup's (from p0)
+    na = nrm[cos_slot_a(same_a, p0 + g) * n_out + k.out0 + c];
+    nb = nrm[cos_slot_b(same_a, p0 + g) * n_out + k.out0 + c];
   }
-  cos_col_prods_body(k, gm, nmod, live, c, ma, mb, na, nb, lds, s_all + static_cast<int64_t>(p0 + g) * n_out + k.out0 + c);
-}
-
-// torch's serial full sum of s[0 .. n) (scalar_inner_sum below 8 elements, else
-// vectorized_inner_sum: lane l sums elements 8 i + l by row_sum, then the scalar tail, then the
-// lanes in order), without the store's 0 +; valid in thread 0, every thread of the wave calls it
-__device__ __forceinline__ float cos_inner_sum(const float* s, int64_t n, int l) {
-  if (n < kCosVw) return l == 0 ? cos_row_sum([&](int64_t i) { return s[i]; }, n) : 0.f;
-  const int64_t nv = n / kCosVw;
-  const float lane_sum = l < kCosVw ? cos_row_sum([&](int64_t i) { return s[i * kCosVw + l]; }, nv) : 0.f;
-  float tail = 0.f;
-  if (l == 0)
-    for (int64_t k = nv * kCosVw; k < n; ++k) tail = __fadd_rn(tail, s[k]);
-  return cos_group_fold(tail, lane_sum, 0);
+  cos_col_prods_body(k, gm, nmod, live, c, cos_slot_a(same_a, g), cos_slot_b(same_a, g), na, nb, lds,
+                     s_all + static_cast<int64_t>(p0 + g) * n_out + k.out0 + c);
 }
 
 // per (tensor, pair): mean = sum(s) / numel (torch sum then div_); 8 threads = the lanes.
@@ -3706,14 +3844,16 @@ __global__ void k_cosine_finish(int n_seg, const float* __restrict__ means, floa
 // ------------------------------------------------------------------------------------------
 // K2r: K2 over a round's pair list (tal_cosine_round; table format in tal_agg.h).  The models
 // are rows of one pool segment.  Every clamped norm is computed once per model into
-// nrm[model slot][output] (streamed column chunks: cos_col_norms_body as K2 runs it; the direct
-// kinds: k_cosr_norms, the norm halves of k_cosine_outputs), then every unique unordered pair's
-// products once (streamed: cos_col_prods_body, one workgroup per (chunk, pair group), the group's
-// shared row in LDS slot 0; direct: k_cosr_prods, the product halves of k_cosine_outputs with the
-// norms read from the table), then k_cosine_means / k_cosine_finish over the batch's unique pairs
-// and one gather into the caller's ordered pairs.  No fp32 operation differs from K2's: the value
-// of a pair is symmetric (fl(x/n1) fl(y/n2) commutes, the sums run in the same order), so the
-// unordered pair's value serves both orders.
+// nrm[model slot][output] (streamed column chunks: k_cosr_col_norms through cos_col_norms_body;
+// the direct kinds: k_cosr_norms through cos_norm_elem / cos_norm_col<1> / cos_norm_row<1>), then
+// every unique unordered pair's products once, with both norms read from that table (streamed:
+// k_cosr_col_prods through cos_col_prods_body, one workgroup per (chunk, pair group), the group's
+// shared row in LDS slot 0; direct: k_cosr_prods through cos_prod_elem / cos_prod_col /
+// cos_prod_row<P>), then k_cosine_means / k_cosine_finish over the batch's unique pairs and one
+// gather into the caller's ordered pairs.  Every one of those functions is the one K2's kernels
+// call, so no fp32 operation differs from K2's; and the value of a pair is symmetric (fl(x/n1)
+// fl(y/n2) commutes, the sums run in the same order), so the unordered pair's value serves both
+// orders.
 // ------------------------------------------------------------------------------------------
 constexpr int kCosrHdr = 8;     // table words: {n_pairs, n_unique, n_models, n_groups, max_group, pool_rows, words, 0}
 constexpr int kCosrGroup = 8;   // pairs per group: kColPairs, the 9-model LDS area of kColModels
@@ -3788,22 +3928,7 @@ __global__ __launch_bounds__(kColThreads) void k_cosr_col_prods(const T* __restr
                      s_all + static_cast<int64_t>(first - u0 + g) * n_out + k.out0 + c);
 }
 
-// XCD-aware order of a (direct chunk, item) grid, as k_cosine_outputs: workgroup 8 k + x takes
-// item k % cnt of direct chunk 8 (k / cnt) + x, so a chunk's items (models, or pair groups, which
-// share rows) run one after another on XCD x and meet in its L2
-__device__ __forceinline__ bool cosr_direct_chunk(const int64_t* __restrict__ plan, int n_seg, int cnt, int64_t n_direct,
-                                                  int* item, const int64_t** ch, const int64_t** sg) {
-  const int64_t kq = blockIdx.x >> 3;
-  *item = static_cast<int>(kq % cnt);
-  const int64_t c = kq / cnt * 8 + (blockIdx.x & 7);
-  if (c >= n_direct) return false;
-  *ch = plan + kCosHdr + kCosSegWords * static_cast<int64_t>(n_seg) + kCosChunkWords * (plan[3] + c);
-  *sg = plan + kCosHdr + kCosSegWords * (*ch)[0];
-  return true;
-}
-
-// direct chunks: one workgroup per (chunk, model): the clamped norms of the chunk's outputs, the
-// norm halves of k_cosine_outputs for one model
+// direct chunks: one workgroup per (chunk, model): the clamped norms of the chunk's outputs
 template <class T>
 __global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const T* __restrict__ pool, int64_t ld,
                                                          const int32_t* __restrict__ table,
@@ -3811,66 +3936,28 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_norms(const T* __restrict__ 
                                                          int64_t n_direct, float* __restrict__ nrm) {
   int slot;
   const int64_t *ch, *sg;
-  if (!cosr_direct_chunk(plan, n_seg, table[2], n_direct, &slot, &ch, &sg)) return;
-  const int64_t first = ch[1], count = ch[2];
-  const int64_t I = sg[2], B = sg[3];
+  if (!cos_direct_chunk(plan, n_seg, table[2], n_direct, &slot, &ch, &sg)) return;
+  const int64_t first = ch[1], count = ch[2], I = sg[2], B = sg[3];
   const int kind = static_cast<int>(sg[5]);
   const T* a = pool + cosr_table(table).models[slot] * ld + sg[0];
   float* nm = nrm + static_cast<int64_t>(slot) * plan[1] + sg[4];
-  const int tid = threadIdx.x;
   if (kind == kCosElem) {
-    const int64_t q = first + tid;
-    if (q < first + count) nm[q] = cos_clamp(cos_sqrt_rn(__fmaf_rn(cos_ld(a, q), cos_ld(a, q), 0.f)));
+    const int64_t q = first + threadIdx.x;
+    if (q < first + count) nm[q] = cos_norm_elem(cos_ld(a, q));
     return;
   }
-  if (kind == kCosCol) {  // torch NormTwoOps: fma in index order (loads in batches of 8)
-    const int64_t q = first + tid;
+  if (kind == kCosCol) {
+    const int64_t q = first + threadIdx.x;
     if (q >= first + count) return;
-    const int64_t o = q / B, k = q % B;
-    const T* x1 = a + o * I * B + k;
-    float m1 = 0.f;
-    int64_t i0 = 0;
-    for (; i0 + 8 <= I; i0 += 8) {
-      float u1[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) u1[u] = cos_ld(x1, (i0 + u) * B);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) m1 = __fmaf_rn(u1[u], u1[u], m1);
-    }
-    for (int64_t i = i0; i < I; ++i) m1 = __fmaf_rn(cos_ld(x1, i * B), cos_ld(x1, i * B), m1);
-    nm[q] = cos_clamp(cos_sqrt_rn(m1));
+    const T* x[1] = {a + q / B * I * B + q % B};
+    cos_norm_col<1>(x, I, B, nm + q);
     return;
   }
-  // kCosRow: 8 threads per row, vector_norm's lane accumulators over whole vectors, the lane
-  // fold in lane order, the tail (groups of 4 as square-then-add, the rest fused)
-  const int lane = tid & 63;
-  const int l = lane & (kCosVw - 1);
-  const int gbase = lane & ~(kCosVw - 1);
-  const int64_t q = first + tid / kCosVw;
-  const bool live = q < first + count;
-  const T* x1 = a + (live ? q : first) * I;
-  const int64_t vec_end = I - I % kCosVw;
-  float m1 = 0.f;
-  if (live) {
-    int64_t d = l;
-    for (; d + 7 * kCosVw < vec_end; d += 8 * kCosVw) {
-      float u1[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) u1[u] = cos_ld(x1, d + u * kCosVw);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) m1 = __fmaf_rn(u1[u], u1[u], m1);
-    }
-    for (; d < vec_end; d += kCosVw) m1 = __fmaf_rn(cos_ld(x1, d), cos_ld(x1, d), m1);
-  }
-  float t1 = __shfl(m1, gbase, 64);  // lane 0 starts the fold
-  for (int j = 1; j < kCosVw; ++j) t1 = __fadd_rn(t1, __shfl(m1, gbase + j, 64));
-  if (l == 0 && live) {
-    int64_t d = vec_end;
-    const int64_t sep = (I - vec_end) / 4 * 4;
-    for (int64_t e = 0; e < sep; ++e, ++d) t1 = __fadd_rn(t1, __fmul_rn(cos_ld(x1, d), cos_ld(x1, d)));
-    for (; d < I; ++d) t1 = __fmaf_rn(cos_ld(x1, d), cos_ld(x1, d), t1);
-    nm[q] = cos_clamp(cos_sqrt_rn(t1));
-  }
+  const CosRowThread t = cos_row_thread(first, count);
+  const T* x[1] = {a + (t.live ? t.q : first) * I};
+  float n[1];
+  cos_norm_row<1>(x, I, t.live, t.l, t.gbase, n);
+  if (t.l == 0 && t.live) nm[t.q] = n[0];
 }
 
 // One workgroup's view of a direct chunk and a pair group (k_cosr_prods)
@@ -3896,56 +3983,28 @@ __device__ __forceinline__ const float* cosr_nrm_b(const CosrGroup<T>& g, int j)
 template <class T>
 __device__ __forceinline__ float* cosr_s(const CosrGroup<T>& g, int j) { return g.s_all + j * g.n_out + g.out_off; }
 
-// Row kind, pairs j0 .. j0 + P of the group at once: torch's inner sum of each pair's products (x1
-// / n1) (x2 / n2) as in k_cosine_outputs - scalar_inner_sum below 8 elements, else
-// vectorized_inner_sum: lane l sums elements 8 i + l by row_sum, then the scalar tail from 0, then
-// the lanes in order - with the shared row's quotient x1 / n1 divided once per element for the P
-// pairs (cos_row_sum_pairs).  x1: the shared row's row q, n1 its norm.
+// Row kind: pairs j0 .. j0 + P of the group through one cos_prod_row: the other rows and their
+// norms from the table, the products stored.  x1: the shared row's row t.q (at e), n1 its norm.
 template <int P, int kU, class T>
-__device__ __forceinline__ void cosr_row_pairs(const CosrGroup<T>& g, int j0, const T* x1, float n1, int64_t q,
-                                               int64_t rowoff, int64_t I, bool live, int l, int gbase) {
+__device__ __forceinline__ void cosr_row_pairs(const CosrGroup<T>& g, int j0, const CosRowThread& t, const T* x1,
+                                               float n1, int64_t e, int64_t I) {
   const T* x2[P];
-  float n2[P];
+  float n2[P], r[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
-    x2[p] = cosr_b(g, j0 + p) + rowoff;
-    n2[p] = live ? cosr_nrm_b(g, j0 + p)[q] : 1.f;
+    x2[p] = cosr_b(g, j0 + p) + e;
+    n2[p] = t.live ? cosr_nrm_b(g, j0 + p)[t.q] : 1.f;
   }
-  auto qa = [&](int64_t i) { return __fdiv_rn(cos_ld(x1, i), n1); };
-  auto qb = [&](int64_t i, int p) { return __fdiv_rn(cos_ld(x2[p], i), n2[p]); };
-  if (I < kCosVw) {  // scalar_inner_sum
-    if (l == 0 && live) {
-      float r[P];
-      cos_row_sum_pairs<P, kU>(qa, qb, I, r);
+  cos_prod_row<P, kU>(x1, n1, x2, n2, I, t.live, t.l, t.gbase, r);
 #pragma unroll
-      for (int p = 0; p < P; ++p) cosr_s(g, j0 + p)[q] = __fadd_rn(0.f, r[p]);
-    }
-    return;
-  }
-  const int64_t nv = I / kCosVw;
-  float lane_sum[P], tail[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) lane_sum[p] = tail[p] = 0.f;
-  if (live)
-    cos_row_sum_pairs<P, kU>([&](int64_t i) { return qa(i * kCosVw + l); },
-                             [&](int64_t i, int p) { return qb(i * kCosVw + l, p); }, nv, lane_sum);
-  if (l == 0 && live)
-    for (int64_t k2 = nv * kCosVw; k2 < I; ++k2) {
-      const float a = qa(k2);
-#pragma unroll
-      for (int p = 0; p < P; ++p) tail[p] = __fadd_rn(tail[p], __fmul_rn(a, qb(k2, p)));
-    }
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const float fin = cos_group_fold(tail[p], lane_sum[p], gbase);
-    if (l == 0 && live) cosr_s(g, j0 + p)[q] = __fadd_rn(0.f, fin);
-  }
+  for (int p = 0; p < P; ++p)
+    if (t.l == 0 && t.live) cosr_s(g, j0 + p)[t.q] = r[p];
 }
 
-// direct chunks: one workgroup per (chunk, pair group): the product halves of k_cosine_outputs
-// with both norms read from the table.  Row tensors take the group's pairs four (then two, then
-// one) at a time, the shared row's loads and quotients once for them; the element and column
-// kinds (1-D parameters, B >= 32: few and small) take them one after another.
+// direct chunks: one workgroup per (chunk, pair group): the products, both norms read from the
+// table.  Row tensors take the group's pairs four (then two, then one) at a time, the shared
+// row's loads and quotients once for them; the element and column kinds (1-D parameters, B >=
+// 32: few and small) take them one after another.
 template <class T>
 __global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const T* __restrict__ pool, int64_t ld,
                                                          const int32_t* __restrict__ table,
@@ -3954,7 +4013,7 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const T* __restrict__ 
                                                          const float* __restrict__ nrm, float* __restrict__ s_all) {
   int gi;
   const int64_t *ch, *sg;
-  if (!cosr_direct_chunk(plan, n_seg, ng, n_direct, &gi, &ch, &sg)) return;
+  if (!cos_direct_chunk(plan, n_seg, ng, n_direct, &gi, &ch, &sg)) return;
   const CosrTable tb = cosr_table(table);
   const int32_t* grp = tb.groups + 3 * (g0 + gi);
   const int slot_a = grp[0], np = grp[2];
@@ -3968,60 +4027,41 @@ __global__ __launch_bounds__(kCosBlock) void k_cosr_prods(const T* __restrict__ 
   g.uniq = tb.uniq + 2 * grp[1];
   g.nrm = nrm;
   g.s_all = s_all + static_cast<int64_t>(grp[1] - u0) * g.n_out;
-  const int64_t first = ch[1], count = ch[2];
-  const int64_t I = sg[2], B = sg[3];
+  const int64_t first = ch[1], count = ch[2], I = sg[2], B = sg[3];
   const int kind = static_cast<int>(sg[5]);
   const T* a = pool + tb.models[slot_a] * ld + sg[0];
   const float* nma = nrm + static_cast<int64_t>(slot_a) * g.n_out + sg[4];
-  const int tid = threadIdx.x;
+  // (one branch per kind, in this order: the row kind's <4, 2> form needs 241 of the 256 VGPRs
+  // that two waves per SIMD leave, and with the two one-thread-per-output kinds under a common
+  // branch the bf16 instantiation came out at 266 registers and one wave)
   if (kind == kCosElem) {
-    const int64_t q = first + tid;
+    const int64_t q = first + threadIdx.x;
     if (q >= first + count) return;
-    const float qa = __fdiv_rn(cos_ld(a, q), nma[q]);
-    for (int j = 0; j < np; ++j)
-      cosr_s(g, j)[q] = __fadd_rn(0.f, __fmul_rn(qa, __fdiv_rn(cos_ld(cosr_b(g, j), q), cosr_nrm_b(g, j)[q])));
+    const float q1 = __fdiv_rn(cos_ld(a, q), nma[q]);
+    for (int j = 0; j < np; ++j) cosr_s(g, j)[q] = cos_prod_elem(q1, cos_ld(cosr_b(g, j), q), cosr_nrm_b(g, j)[q]);
     return;
   }
   if (kind == kCosCol) {
-    const int64_t q = first + tid;
+    const int64_t q = first + threadIdx.x;
     if (q >= first + count) return;
-    const int64_t o = q / B, k = q % B;
-    const T* x1 = a + o * I * B + k;
+    const int64_t k = q % B, e = q / B * I * B + k;
     const float n1 = nma[q];
 #pragma nounroll
-    for (int j = 0; j < np; ++j) {
-      const T* x2 = cosr_b(g, j) + o * I * B + k;
-      const float n2 = cosr_nrm_b(g, j)[q];
-      auto prod = [&](int64_t i) { return __fmul_rn(__fdiv_rn(cos_ld(x1, i * B), n1), __fdiv_rn(cos_ld(x2, i * B), n2)); };
-      float r;
-      if (B >= kCosVw && k < B / 32 * 32) {  // columns in chunks of 32 share one cascade
-        float c[1];
-        cos_multi_row<1>([&](int64_t i, int) { return prod(i); }, I, c);
-        r = c[0];
-      } else {  // chunks of 8 and single columns: row_sum per column
-        r = cos_row_sum(prod, I);
-      }
-      cosr_s(g, j)[q] = __fadd_rn(0.f, r);
-    }
+    for (int j = 0; j < np; ++j) cosr_s(g, j)[q] = cos_prod_col(a + e, n1, cosr_b(g, j) + e, cosr_nrm_b(g, j)[q], I, B, k);
     return;
   }
-  // kCosRow: 8 threads per row (torch's vector lanes)
-  const int lane = tid & 63;
-  const int l = lane & (kCosVw - 1);
-  const int gbase = lane & ~(kCosVw - 1);
-  const int64_t q = first + tid / kCosVw;
-  const bool live = q < first + count;
-  const int64_t rowoff = (live ? q : first) * I;
-  const T* x1 = a + rowoff;
-  const float n1 = live ? nma[q] : 1.f;
+  const CosRowThread t = cos_row_thread(first, count);
+  const int64_t e = (t.live ? t.q : first) * I;
+  const T* x1 = a + e;
+  const float n1 = t.live ? nma[t.q] : 1.f;
   int j = 0;
 #pragma nounroll
-  for (; j + 4 <= np; j += 4) cosr_row_pairs<4, 2>(g, j, x1, n1, q, rowoff, I, live, l, gbase);
+  for (; j + 4 <= np; j += 4) cosr_row_pairs<4, 2>(g, j, t, x1, n1, e, I);
   if (j + 2 <= np) {
-    cosr_row_pairs<2, 4>(g, j, x1, n1, q, rowoff, I, live, l, gbase);
+    cosr_row_pairs<2, 4>(g, j, t, x1, n1, e, I);
     j += 2;
   }
-  if (j < np) cosr_row_pairs<1, 8>(g, j, x1, n1, q, rowoff, I, live, l, gbase);
+  if (j < np) cosr_row_pairs<1, 8>(g, j, t, x1, n1, e, I);
 }
 
 // every ordered pair's result from its unique pair
@@ -5090,10 +5130,9 @@ static int cos_kind(int64_t I, int64_t B) { return I == 1 ? kCosElem : (B == 1 ?
 
 // outputs per chunk of a tensor and whether its chunks are streamed (k_cos_col_norms /
 // k_cos_col_prods: Ob output blocks of the column kind) or direct (k_cosine_outputs)
-static int64_t cos_seg_per(int64_t A, int64_t I, int64_t B, bool* staged) {
+static int64_t cos_seg_per(int64_t I, int64_t B, bool* staged) {
   const int kind = cos_kind(I, B);
   *staged = cos_col_streamed(kind, I, B);
-  (void)A;
   return *staged ? cos_col_ob(B) * B : cos_chunk_outputs(kind);
 }
 
@@ -5104,7 +5143,7 @@ int64_t tal_cosine_plan_words(const int64_t* seg_host, int32_t n_seg) {
     const int64_t A = seg_host[4 * s + 1], I = seg_host[4 * s + 2], B = seg_host[4 * s + 3];
     if (A <= 0 || I <= 0 || B <= 0 || seg_host[4 * s] < 0) return -1;
     bool staged;
-    const int64_t per = cos_seg_per(A, I, B, &staged);
+    const int64_t per = cos_seg_per(I, B, &staged);
     chunks += (A * B + per - 1) / per;
   }
   return kCosHdr + kCosSegWords * static_cast<int64_t>(n_seg) + kCosChunkWords * chunks;
@@ -5128,7 +5167,7 @@ int32_t tal_cosine_plan_build(const int64_t* seg_host, int32_t n_seg, int64_t* p
     sg[kCosSegWords * s + 3] = B;
     sg[kCosSegWords * s + 4] = out;
     sg[kCosSegWords * s + 5] = cos_kind(I, B);
-    sg[kCosSegWords * s + 6] = cos_seg_per(A, I, B, &staged);
+    sg[kCosSegWords * s + 6] = cos_seg_per(I, B, &staged);
     if (staged) n_staged += (A * B + sg[kCosSegWords * s + 6] - 1) / sg[kCosSegWords * s + 6];
     out += A * B;
   }
@@ -5138,7 +5177,7 @@ int32_t tal_cosine_plan_build(const int64_t* seg_host, int32_t n_seg, int64_t* p
     for (int s = 0; s < n_seg; ++s) {
       const int64_t A = sg[kCosSegWords * s + 1], B = sg[kCosSegWords * s + 3], per = sg[kCosSegWords * s + 6];
       bool staged;
-      cos_seg_per(A, sg[kCosSegWords * s + 2], B, &staged);
+      cos_seg_per(sg[kCosSegWords * s + 2], B, &staged);
       if (staged != (pass == 1)) continue;
       const int64_t total = A * B;
       for (int64_t f = 0; f < total; f += per) {
@@ -6059,9 +6098,7 @@ struct HostCos {
   // on the element index (a column of a 32-column group is this case too)
   template <class Load>
   static float cascade(Load x, int64_t size) {
-    int64_t lg = 0;
-    while ((int64_t{1} << lg) < size) ++lg;
-    const int64_t lp = lg / 4 > 4 ? lg / 4 : 4;
+    const int64_t lp = cos_lp(size);
     const int64_t step = int64_t{1} << lp;
     float lv[4] = {0.f, 0.f, 0.f, 0.f};
     int64_t i = 0;
