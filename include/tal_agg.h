@@ -275,6 +275,12 @@ int32_t tal_agg_round_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* poo
                            int64_t ld_out, int64_t n, const int32_t* plan_dev,
                            const tal_round_plan_info* info, int32_t mode, void* stream);
 
+/* The kernel tal_agg_round_f32 (bf16 != 0: tal_agg_round_bf16) runs over the float4 columns of
+ * aligned pools for this plan, answered by the function the launch itself dispatches on (ABI 28):
+ * "k_round_stream", "k_round_wide", "k_round_f32_narrow" (the broadcast form too),
+ * "k_round_f32_persistent" or "k_round_f32_tiled"; "" for a null info.  A static string. */
+const char* tal_round_kernel_name(const tal_round_plan_info* info, int32_t bf16);
+
 /* ---- K3r: a round over register-resident source groups ----------------------------------
  * Community graphs (BASELINE config 5's stochastic block model): the rows are grouped so that
  * each group reads <= 64 distinct sources; one wavefront loads a group's sources for a 128-

@@ -129,6 +129,31 @@ def test_round_bf16_vs_oracle(cuda, graph, c4, lds, mode):
             assert np.array_equal(host(pin, n), ref), pad
 
 
+@pytest.mark.parametrize("mode", [ops.MODE_EXACT, ops.MODE_FMA])
+@pytest.mark.parametrize("even", [False, True], ids=["odd_chunks", "even_chunks"])
+@pytest.mark.parametrize("c4", [16, 32])
+@pytest.mark.parametrize("graph", ["reg8x96_uniform", "reg8x96_random"])
+def test_round_bf16_narrow_lane_widths(cuda, graph, c4, even, mode):
+    """The narrow kernel's two staging lane widths on a bf16 pool: 16-byte lanes need an even
+    number of float4 chunks per row, an odd count takes the 8-byte lanes (J = 2 at c4 16, 4 at
+    c4 32: both widths exist).  n is two full tiles and a partial one (plus one chunk for the
+    even count) and a three-element scalar tail; the 96-row graph of the plan digests, with
+    uniform (ROWW) and per-operand (pairs) weights."""
+    from test_round_plan_digests import _graphs
+
+    row_ptr, col, w, out_rows = _graphs()[graph]
+    plan = ops.build_plan(row_ptr, col, w, out_rows, c4=c4, lds_bytes=160 * 1024, dense=0)
+    assert plan.info.max_src * c4 in (2 * 1024 * 3 // 4, 4 * 1024 * 3 // 4)  # 96 sources: J = 2 / 4
+    n = 4 * (2 * c4 + 1 + int(even)) + 3
+    rng = np.random.default_rng(c4 + n)
+    pool = np.stack([_bf16_bits(rng, n, special=(r == 0)) for r in range(96)])
+    ref = oracle.round_bf16(pool, row_ptr, col, w, out_rows, exact=(mode == ops.MODE_EXACT))
+    pin = dev_rows(pool, cuda)
+    pout = torch.zeros_like(pin)
+    ops.round_bf16(pin, pout, plan, n=n, mode=mode)
+    assert np.array_equal(host(pout, n), ref)
+
+
 def test_round_bf16_padded_rows(cuda):
     """Rows padded past n (the ModelPool layout): results in [0, n), padding left untouched."""
     g = nx.random_regular_graph(4, 20, seed=1)

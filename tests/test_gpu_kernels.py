@@ -334,6 +334,49 @@ def test_round_narrow_sbm256_one_group(cuda, c4):
     assert _bits_equal(host(pout, n), oracle.round_f32(pool, row_ptr, col, w, out_rows))
 
 
+@pytest.mark.parametrize("uniform", [True, False], ids=["roww", "pairs"])
+@pytest.mark.parametrize("c4,sources,j", [(16, 300, 8), (16, 600, 12), (32, 300, 12)])
+def test_round_narrow_wide_groups(cuda, c4, sources, j, uniform):
+    """Groups past 256 sources at c4 = 16 (128 at c4 = 32): the narrow kernel's 8 and 12 staging
+    loads per lane, which none of the graphs above reaches.  Six rows, each over nearly all of
+    `sources` models; n is two full tiles, a partial one and a three-element scalar tail."""
+    rows = 6
+    orders = [[s for s in range(rows, sources) if (s + r) % 29] + [r] for r in range(rows)]
+    rng = np.random.default_rng(sources + c4)
+    ws = [ra.unweighted_weights(len(o)) if uniform else list(rng.uniform(0.05, 1.0, len(o)) / len(o)) for o in orders]
+    row_ptr, col, w = ra.round_csr(orders, ws)
+    out_rows = np.arange(rows, dtype=np.int32)
+    plan = ops.build_plan(row_ptr, col, w, out_rows, c4=c4, lds_bytes=160 * 1024)
+    lo, hi = {8: (4, 8), 12: (8, 12)}[j]
+    assert lo * 1024 < plan.info.max_src * c4 <= hi * 1024 and plan.info.narrow_roww == int(uniform)
+    n = 4 * (2 * c4 + 1) + 3
+    pool = np.stack([_rand_f32(rng, n) for _ in range(sources)])
+    pin = dev_rows(pool, cuda)
+    pout = torch.zeros_like(pin)
+    ops.round_f32(pin, pout, plan, n=n)
+    assert _bits_equal(host(pout, n)[:rows], oracle.round_f32(pool, row_ptr, col, w, out_rows)[:rows])
+
+
+@pytest.mark.parametrize("dense", [0, 8])
+def test_round_f32_tiled_kernel(cuda, dense):
+    """A group of 150 sources at c4 = 64 is past what the persistent kernel stages (8 float4 per
+    lane x 1024 threads = 128 sources): the tiled kernel, sparse and dense.  Four rows in
+    reference order; n is two full tiles, a partial one and a three-element scalar tail."""
+    rows, c4 = 4, 64
+    orders = [[s for s in range(rows, 154) if (s + r) % 31] + [r] for r in range(rows)]
+    row_ptr, col, w = ra.round_csr(orders, [ra.unweighted_weights(len(o)) for o in orders])
+    out_rows = np.arange(rows, dtype=np.int32)
+    plan = ops.build_plan(row_ptr, col, w, out_rows, c4=c4, lds_bytes=160 * 1024, dense=dense)
+    assert plan.info.dense_rb == dense and ops.round_kernel_name(plan) == "k_round_f32_tiled"
+    n = 4 * (2 * c4 + 1) + 3
+    rng = np.random.default_rng(154 + dense)
+    pool = np.stack([_rand_f32(rng, n) for _ in range(154)])
+    pin = dev_rows(pool, cuda)
+    pout = torch.zeros_like(pin)
+    ops.round_f32(pin, pout, plan, n=n)
+    assert _bits_equal(host(pout, n)[:rows], oracle.round_f32(pool, row_ptr, col, w, out_rows)[:rows])
+
+
 _STREAM_GRAPHS = {
     "ring": lambda: nx.cycle_graph(16),
     "regular": lambda: nx.random_regular_graph(8, 64, seed=0),

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -45,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 27;
+constexpr int kAbiVersion = 28;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -1878,15 +1879,14 @@ __global__ __launch_bounds__(kWideThreads) void k_round_wide(const T* __restrict
   }
 }
 
-template <typename T>
+template <typename T, bool EXACT>
 int32_t launch_round_wide(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4, const PlanView& v,
-                          const tal_round_plan_info& in, bool exact, hipStream_t s) {
+                          const tal_round_plan_info& in, hipStream_t s) {
   if (in.max_rows > kWideRows) return fail(TAL_ERR_INVALID, "wide-row round: groups of at most 16 rows");
   const int64_t tiles = (n4 + kWideC4 - 1) / kWideC4;
   if (tiles > 0x7fffffff || in.n_groups > 65535) return fail(TAL_ERR_INVALID, "wide-row round: grid too large");
   const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(in.n_groups));
-  if (exact) k_round_wide<T, true><<<grid, kWideThreads, 0, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v);
-  else k_round_wide<T, false><<<grid, kWideThreads, 0, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v);
+  k_round_wide<T, EXACT><<<grid, kWideThreads, 0, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v);
   return check_launch("round kernel (wide rows)");
 }
 
@@ -2068,23 +2068,49 @@ int32_t launch_round_scalar(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
 // Threads per round workgroup: 16 wavefronts at c4 = 64 (a 64-source tile is 4 loads per lane),
 // 8 at c4 = 128 (dense rows: fewer, longer rows per wavefront).  Tuned on MI355X with
 // tools/tune/round_variants.hip (config 3: 2.0-2.1 ms / round, config 4: 7.8 ms).
-template <int C4>
-constexpr int round_threads() { return C4 >= 128 ? 512 : 1024; }
+constexpr int round_threads(int c4) { return c4 >= 128 ? 512 : 1024; }
+
+// float4 staging loads per lane (J) of the persistent kernel whose tile takes `loads` of them;
+// 0: more than it stages, the tiled kernel's plan.  16-20 float4 in flight per lane: 512-thread
+// blocks only (VGPRs).
+constexpr int persistent_j_max(int c4) { return round_threads(c4) <= 512 ? 20 : 8; }
+constexpr int persistent_j(int c4, int64_t loads) {
+  for (int j : {1, 2, 4, 8, 16, 20})
+    if (j <= persistent_j_max(c4) && loads <= static_cast<int64_t>(j) * round_threads(c4)) return j;
+  return 0;
+}
+
+// Runtime values to template arguments: f is called with the std::integral_constant that equals
+// the value (with_int: TAL_ERR_INVALID when it is none of Vs).
+template <class F>
+int32_t with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int... Vs, class F>
+int32_t with_int(int v, F&& f) {
+  int32_t rc = TAL_ERR_INVALID;
+  const bool found = ((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...);
+  return found ? rc : fail(TAL_ERR_INVALID, "round launch: no kernel for " + std::to_string(v));
+}
+
+// Grid of the persistent round kernels: the 256 CUs x per_cu resident workgroups shared among
+// the groups (grid.y), each walking the column tiles of its group; at most one per tile.
+dim3 persistent_grid(int64_t tiles, int64_t per_cu, int32_t n_groups) {
+  const int64_t gx = std::min<int64_t>(std::max<int64_t>(1, 256 * per_cu / n_groups), tiles);
+  return dim3(static_cast<unsigned>(gx), static_cast<unsigned>(n_groups));
+}
 
 template <int C4, int J, bool EXACT, bool DENSE, typename T = float>
 int32_t launch_round_persistent(const T* pin, int64_t ld_in, T* pout, int64_t ld_out,
                                 int64_t n4, const PlanView& v, const tal_round_plan_info& in,
                                 size_t lds, hipStream_t s) {
-  constexpr int kRoundThreads = round_threads<C4>();
+  constexpr int kRoundThreads = round_threads(C4);
   auto k = k_round_f32_persistent<C4, kRoundThreads, J, EXACT, DENSE, T>;
   int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
   if (rc) return rc;
   const int64_t tiles = (n4 + C4 - 1) / C4;
   const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / static_cast<int64_t>(lds)));
-  int64_t gx = std::max<int64_t>(1, 256 * per_cu / in.n_groups);
-  gx = std::min<int64_t>(gx, tiles);
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(in.n_groups));
-  k<<<grid, kRoundThreads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
+  k<<<persistent_grid(tiles, per_cu, in.n_groups), kRoundThreads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
   return check_launch("round kernel (persistent)");
 }
 
@@ -2162,19 +2188,9 @@ int32_t launch_round_narrow_jr(const T* pin, int64_t ld_in, T* pout, int64_t ld_
   int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
   if (rc) return rc;
   const int64_t tiles = (n4 + C4 - 1) / C4;
-  const int64_t per_cu = resident_per_cu(reinterpret_cast<const void*>(k), kNarrowThreads, lds);
-  int64_t gx = std::max<int64_t>(1, 256 * per_cu / in.n_groups);
-  gx = std::min<int64_t>(gx, tiles);
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(in.n_groups));
-  k<<<grid, kNarrowThreads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
+  const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k), kNarrowThreads, lds);
+  k<<<persistent_grid(tiles, per_cu, in.n_groups), kNarrowThreads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
   return check_launch("round kernel (narrow tiles)");
-}
-
-template <int C4, int J, bool EXACT, typename T = float>
-int32_t launch_round_narrow_j(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4,
-                              const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
-  return in.narrow_roww ? launch_round_narrow_jr<C4, J, EXACT, T, true>(pin, ld_in, pout, ld_out, n4, v, in, s)
-                        : launch_round_narrow_jr<C4, J, EXACT, T, false>(pin, ld_in, pout, ld_out, n4, v, in, s);
 }
 
 // Broadcast form: NT = 64 x the plan's waves; J staging loads per lane cover the largest group.
@@ -2198,11 +2214,8 @@ int32_t launch_round_bcast_j(const T* pin, int64_t ld_in, T* pout, int64_t ld_ou
   int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
   if (rc) return rc;
   const int64_t tiles = (n4 + C4 - 1) / C4;
-  const int64_t per_cu = resident_per_cu(reinterpret_cast<const void*>(k), NT, lds);
-  int64_t gx = std::max<int64_t>(1, 256 * per_cu / in.n_groups);
-  gx = std::min<int64_t>(gx, tiles);
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(in.n_groups));
-  k<<<grid, NT, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
+  const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k), NT, lds);
+  k<<<persistent_grid(tiles, per_cu, in.n_groups), NT, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
   return check_launch("round kernel (narrow tiles, broadcast form)");
 }
 
@@ -2234,22 +2247,29 @@ int32_t launch_round_bcast_nt(const T* pin, int64_t ld_in, T* pout, int64_t ld_o
 template <int C4, bool EXACT, typename T>
 int32_t launch_round_bcast(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4,
                            const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
-  if (in.narrow_bcast == 8) return launch_round_bcast_nt<C4, 512, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  if (in.narrow_bcast == 12) return launch_round_bcast_nt<C4, 768, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  return launch_round_bcast_nt<C4, 1024, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
+  return with_int<8, 12, 16>(in.narrow_bcast, [&](auto waves) {
+    return launch_round_bcast_nt<C4, 64 * decltype(waves)::value, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
+  });
+}
+
+// J of the narrow kernel for `loads` float4 staging loads per tile (0: past its largest tile)
+constexpr int narrow_j(int64_t loads) {
+  for (int j : {1, 2, 4, 8, 12})
+    if (loads <= static_cast<int64_t>(j) * kNarrowThreads) return j;
+  return 0;
 }
 
 template <int C4, bool EXACT, typename T = float>
 int32_t launch_round_narrow(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4,
                             const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
-  if (in.narrow_bcast) return launch_round_bcast<C4, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  const int64_t loads = static_cast<int64_t>(in.max_src) * C4;  // float4 staging loads per tile
-  if (loads <= 1LL * kNarrowThreads) return launch_round_narrow_j<C4, 1, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  if (loads <= 2LL * kNarrowThreads) return launch_round_narrow_j<C4, 2, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  if (loads <= 4LL * kNarrowThreads) return launch_round_narrow_j<C4, 4, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  if (loads <= 8LL * kNarrowThreads) return launch_round_narrow_j<C4, 8, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  if (loads <= 12LL * kNarrowThreads) return launch_round_narrow_j<C4, 12, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  return fail(TAL_ERR_CAPACITY, "narrow round plan: group tile larger than 160 KiB");
+  const int j = narrow_j(static_cast<int64_t>(in.max_src) * C4);
+  if (j == 0) return fail(TAL_ERR_CAPACITY, "narrow round plan: group tile larger than 160 KiB");
+  return with_int<1, 2, 4, 8, 12>(j, [&](auto J) {
+    return with_bool(in.narrow_roww != 0, [&](auto roww) {
+      return launch_round_narrow_jr<C4, decltype(J)::value, EXACT, T, decltype(roww)::value>(pin, ld_in, pout, ld_out,
+                                                                                            n4, v, in, s);
+    });
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2922,20 +2942,8 @@ int32_t launch_round_stream_nt(const float* pin, int64_t ld_in, float* pout, int
   if (rc) return rc;
   const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k), NT, lds);
   const int64_t tiles = (n4 + 63) / 64;
-  int64_t gx = std::max<int64_t>(1, 256LL * per_cu / in.n_groups);
-  gx = std::min<int64_t>(gx, tiles);
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(in.n_groups));
-  k<<<grid, NT, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
+  k<<<persistent_grid(tiles, per_cu, in.n_groups), NT, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
   return check_launch("round kernel (streamed)");
-}
-
-int32_t launch_round_stream(const float* pin, int64_t ld_in, float* pout, int64_t ld_out, int64_t n4,
-                            const PlanView& v, const tal_round_plan_info& in, bool exact, hipStream_t s) {
-  if (in.stream_cs == 8 * kStreamPerWave)
-    return exact ? launch_round_stream_nt<512, true>(pin, ld_in, pout, ld_out, n4, v, in, s)
-                 : launch_round_stream_nt<512, false>(pin, ld_in, pout, ld_out, n4, v, in, s);
-  return exact ? launch_round_stream_nt<1024, true>(pin, ld_in, pout, ld_out, n4, v, in, s)
-               : launch_round_stream_nt<1024, false>(pin, ld_in, pout, ld_out, n4, v, in, s);
 }
 
 template <bool IS_I64>
@@ -2959,17 +2967,15 @@ int32_t launch_round_stream_scalar(const void* pin, int64_t ld_in, void* pout, i
 template <int C4, bool EXACT, bool DENSE, typename T = float>
 int32_t launch_round_vec(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4,
                          const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
-  constexpr int kRoundThreads = round_threads<C4>();
+  constexpr int kRoundThreads = round_threads(C4);
   const size_t lds = static_cast<size_t>(in.max_src) * C4 * 16;
-  const int64_t loads = static_cast<int64_t>(in.max_src) * C4;  // float4 staging loads per tile
-  if (loads <= 1LL * kRoundThreads) return launch_round_persistent<C4, 1, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
-  if (loads <= 2LL * kRoundThreads) return launch_round_persistent<C4, 2, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
-  if (loads <= 4LL * kRoundThreads) return launch_round_persistent<C4, 4, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
-  if (loads <= 8LL * kRoundThreads) return launch_round_persistent<C4, 8, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
-  if constexpr (kRoundThreads <= 512) {  // 16-20 float4 in flight per lane: 512-thread blocks only (VGPRs)
-    if (loads <= 16LL * kRoundThreads) return launch_round_persistent<C4, 16, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
-    if (loads <= 20LL * kRoundThreads) return launch_round_persistent<C4, 20, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
-  }
+  const int j = persistent_j(C4, static_cast<int64_t>(in.max_src) * C4);  // float4 staging loads per tile
+  if (j > 0)
+    return with_int<1, 2, 4, 8, 16, 20>(j, [&](auto J) -> int32_t {
+      if constexpr (decltype(J)::value <= persistent_j_max(C4))
+        return launch_round_persistent<C4, decltype(J)::value, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, lds, s);
+      return TAL_ERR_INVALID;  // persistent_j never answers it
+    });
   auto k = k_round_f32_tiled<C4, kRoundThreads, EXACT, DENSE, T>;
   int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
   if (rc) return rc;
@@ -4171,87 +4177,112 @@ __global__ __launch_bounds__(kBlock) void k_prox_grad(const float* __restrict__ 
 // ==========================================================================================
 namespace {
 
+// A round as the caller's CSR (check_csr validates it and fills max_col).
+struct Csr {
+  int32_t rows;
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const double* w;
+  const int32_t* out_row;
+  int32_t max_col = 0;
+  int64_t nnz() const { return row_ptr[rows]; }
+  // operands of rows r0 .. r0+nr-1
+  int32_t ops(int64_t r0, int64_t nr = 1) const { return row_ptr[r0 + nr] - row_ptr[r0]; }
+};
+
+// What a plan is laid out for (see tal_round_plan_info).
+struct PlanForm {
+  int32_t c4;             // tile width; 16 / 32: the narrow forms
+  int32_t dense_rb = 0;   // dense row blocks: 0 = sparse form only, kDenseRb, -1 = when they save LDS reads
+  int32_t stream_cs = 0;  // > 0: streamed tables, chunks of that many sources
+  int32_t bc_waves = 0;   // > 0: the broadcast form, that many wavefronts per workgroup ...
+  int32_t bc_wg = 0;      // ... and resident workgroups per CU
+  bool roww = false;      // narrow, not broadcast: one weight per row (16-bit slots + row weights)
+  bool narrow() const { return c4 < 64; }
+  bool bcast() const { return narrow() && bc_waves > 0; }
+};
+
 // Row groups: consecutive rows and the union of their sources (ascending pool rows after
-// finish_plan sorts them).
+// encode_base sorts them).
 struct Groups {
   std::vector<int32_t> row_ptr{0};
   std::vector<std::vector<int32_t>> srcs;
+  int32_t count() const { return static_cast<int32_t>(srcs.size()); }
+  int32_t first(int g) const { return row_ptr[g]; }
+  int32_t rows(int g) const { return row_ptr[g + 1] - row_ptr[g]; }
 };
 
-int32_t check_csr(const char* fn, int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
-                  const double* w_host, const int32_t* out_row_host, int32_t* max_col) {
-  if (rows <= 0 || !row_ptr_host || !col_host || !w_host || !out_row_host)
+// fp32 bits of a weight as the kernels read it
+int32_t f32_bits(double w) {
+  const float f = static_cast<float>(w);
+  int32_t b;
+  memcpy(&b, &f, 4);
+  return b;
+}
+
+int32_t check_csr(const char* fn, Csr* c) {
+  if (c->rows <= 0 || !c->row_ptr || !c->col || !c->w || !c->out_row)
     return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
-  if (row_ptr_host[0] != 0) return fail(TAL_ERR_INVALID, std::string(fn) + ": row_ptr[0] != 0");
-  for (int r = 0; r < rows; ++r)
-    if (row_ptr_host[r + 1] <= row_ptr_host[r])
+  if (c->row_ptr[0] != 0) return fail(TAL_ERR_INVALID, std::string(fn) + ": row_ptr[0] != 0");
+  for (int r = 0; r < c->rows; ++r)
+    if (c->row_ptr[r + 1] <= c->row_ptr[r])
       return fail(TAL_ERR_INVALID, std::string(fn) + ": every row needs >= 1 operand");
-  const int64_t nnz = row_ptr_host[rows];
-  *max_col = 0;
-  for (int64_t k = 0; k < nnz; ++k) {
-    if (col_host[k] < 0) return fail(TAL_ERR_INVALID, std::string(fn) + ": negative source row");
-    *max_col = std::max(*max_col, col_host[k]);
+  c->max_col = 0;
+  for (int64_t k = 0; k < c->nnz(); ++k) {
+    if (c->col[k] < 0) return fail(TAL_ERR_INVALID, std::string(fn) + ": negative source row");
+    c->max_col = std::max(c->max_col, c->col[k]);
   }
   return TAL_OK;
 }
 
 // Reference operand order (decentralized_app.py:618-625): ascending distinct neighbors, then
 // the row's own model, which does not occur among them.
-bool reference_order(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host) {
-  for (int r = 0; r < rows; ++r) {
-    const int32_t k0 = row_ptr_host[r], k1 = row_ptr_host[r + 1];
+bool reference_order(const Csr& c) {
+  for (int r = 0; r < c.rows; ++r) {
+    const int32_t k0 = c.row_ptr[r], k1 = c.row_ptr[r + 1];
     for (int32_t k = k0 + 1; k < k1 - 1; ++k)
-      if (col_host[k] <= col_host[k - 1]) return false;
+      if (c.col[k] <= c.col[k - 1]) return false;
     for (int32_t k = k0; k < k1 - 1; ++k)
-      if (col_host[k] == col_host[k1 - 1]) return false;
+      if (c.col[k] == c.col[k1 - 1]) return false;
   }
   return true;
 }
 
 // Every row's operands carry one fp32 weight (bitwise): the narrow ROWW encoding applies.
-bool rows_uniform_weights(int32_t rows, const int32_t* row_ptr_host, const double* w_host) {
-  for (int r = 0; r < rows; ++r) {
-    const float w0 = static_cast<float>(w_host[row_ptr_host[r]]);
-    for (int32_t k = row_ptr_host[r] + 1; k < row_ptr_host[r + 1]; ++k) {
-      const float wk = static_cast<float>(w_host[k]);
-      if (memcmp(&wk, &w0, 4) != 0) return false;
-    }
-  }
+bool rows_uniform_weights(const Csr& c) {
+  for (int r = 0; r < c.rows; ++r)
+    for (int32_t k = c.row_ptr[r] + 1; k < c.row_ptr[r + 1]; ++k)
+      if (f32_bits(c.w[k]) != f32_bits(c.w[c.row_ptr[r]])) return false;
   return true;
 }
 
 // Greedy grouping: a row joins the current group unless that breaks
-// `fits(n_src, n_rows, n_ops, first_row)` (the candidate group is rows first_row .. +n_rows-1).
+// `fits(n_src, n_rows, first_row)` (the candidate group is rows first_row .. +n_rows-1).
 template <class Fits>
-int32_t group_rows(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host, int32_t max_col,
-                   Fits fits, Groups* out) {
-  std::vector<int32_t> seen(static_cast<size_t>(max_col) + 1, -1);  // source -> group that has it
+int32_t group_rows(const Csr& c, Fits fits, Groups* out) {
+  std::vector<int32_t> seen(static_cast<size_t>(c.max_col) + 1, -1);  // source -> group that has it
   Groups& G = *out;
   G.srcs.assign(1, {});
-  int64_t cur_nnz = 0;
   auto fresh_of = [&](int r, int g, std::vector<int32_t>* fresh) {
     fresh->clear();
-    for (int32_t k = row_ptr_host[r]; k < row_ptr_host[r + 1]; ++k) {
-      const int32_t sr = col_host[k];
+    for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) {
+      const int32_t sr = c.col[k];
       if (seen[sr] != g && std::find(fresh->begin(), fresh->end(), sr) == fresh->end()) fresh->push_back(sr);
     }
   };
   std::vector<int32_t> fresh;
-  for (int r = 0; r < rows; ++r) {
-    int g = static_cast<int>(G.srcs.size()) - 1;
+  for (int r = 0; r < c.rows; ++r) {
+    int g = G.count() - 1;
     fresh_of(r, g, &fresh);
-    const int64_t row_nnz = row_ptr_host[r + 1] - row_ptr_host[r];
-    const int64_t cur_rows = r - G.row_ptr.back();
-    if (!fits(static_cast<int64_t>(G.srcs[g].size() + fresh.size()), cur_rows + 1, cur_nnz + row_nnz,
-              static_cast<int64_t>(G.row_ptr.back()))) {
-      if (cur_rows > 0) {
+    const int64_t first = G.row_ptr.back();
+    if (!fits(static_cast<int64_t>(G.srcs[g].size() + fresh.size()), r - first + 1, first)) {
+      if (r > first) {
         G.row_ptr.push_back(r);
         G.srcs.emplace_back();
-        cur_nnz = 0;
-        g = static_cast<int>(G.srcs.size()) - 1;
+        g = G.count() - 1;
         fresh_of(r, g, &fresh);
       }
-      if (!fits(static_cast<int64_t>(fresh.size()), 1, row_nnz, static_cast<int64_t>(r)))
+      if (!fits(static_cast<int64_t>(fresh.size()), 1, static_cast<int64_t>(r)))
         return fail(TAL_ERR_CAPACITY, "tal_round_plan_build: row " + std::to_string(r) +
                                           " has more distinct sources than one LDS tile holds");
     }
@@ -4259,9 +4290,8 @@ int32_t group_rows(int32_t rows, const int32_t* row_ptr_host, const int32_t* col
       seen[sr] = g;
       G.srcs[g].push_back(sr);
     }
-    cur_nnz += row_nnz;
   }
-  G.row_ptr.push_back(rows);
+  G.row_ptr.push_back(c.rows);
   return TAL_OK;
 }
 
@@ -4270,25 +4300,46 @@ bool roww_slots_fit(int32_t max_col, int32_t c4) {
   return (static_cast<int64_t>(max_col) + 3) * c4 <= 0xffff;
 }
 
-// Slots a group of rows r0 .. r0+nr-1 takes in the ROWW encoding: the narrow builder orders a
-// group's rows by operand count (descending) and pads each pass of 64 / c4 consecutive rows to
-// the batch count of its first (longest) row.
-int64_t roww_padded_slots(const int32_t* row_ptr_host, int64_t r0, int64_t nr, int32_t c4,
-                          std::vector<int32_t>* batches) {
-  batches->resize(static_cast<size_t>(nr));
-  for (int64_t i = 0; i < nr; ++i)
-    (*batches)[i] = (row_ptr_host[r0 + i + 1] - row_ptr_host[r0 + i] + 3) / 4;
-  std::sort(batches->begin(), batches->end(), std::greater<int32_t>());
+// Operand counts of rows r0 .. r0+nr-1, descending: the order the narrow forms compute a
+// group's rows in (round_plan_build permutes the rows so before it encodes them).
+std::vector<int32_t> counts_descending(const Csr& c, int64_t r0, int64_t nr) {
+  std::vector<int32_t> m(static_cast<size_t>(nr));
+  for (int64_t i = 0; i < nr; ++i) m[i] = c.ops(r0 + i);
+  std::sort(m.begin(), m.end(), std::greater<int32_t>());
+  return m;
+}
+
+// Slots a group takes in the ROWW encoding: each pass of 64 / c4 consecutive rows is padded to
+// the batch count (of 4 slots) of its first (longest) row.
+int64_t roww_padded_slots(const Csr& c, int64_t r0, int64_t nr, int32_t c4) {
+  const std::vector<int32_t> m = counts_descending(c, r0, nr);
   const int64_t rpw = 64 / c4;
   int64_t slots = 0;
-  for (int64_t i = 0; i < nr; i += rpw) slots += 4LL * (*batches)[i] * std::min(rpw, nr - i);
+  for (int64_t i = 0; i < nr; i += rpw) slots += 4LL * ((m[i] + 3) / 4) * std::min(rpw, nr - i);
   return slots;
 }
 
+// Pairs a group takes in the pairs encoding: each row's operands after the first padded to
+// whole batches of 4.
+int64_t padded_pairs(const Csr& c, int64_t r0, int64_t nr) {
+  int64_t pairs = 0;
+  for (int64_t r = r0; r < r0 + nr; ++r) pairs += c.ops(r) + (4 - (c.ops(r) - 1) % 4) % 4;
+  return pairs;
+}
+
 // Broadcast form: a pass is 4 rows (16 lanes each: one float4 chunk per lane at c4 = 16, two
-// at c4 = 32) and takes ceil(operands of its longest row / 16) records; passes are dealt to
-// wavefronts longest first, each to the least loaded one.  False when a wavefront would hold
-// more than rmax records.
+// at c4 = 32) and takes ceil(operands of its longest row / 16) records.
+constexpr int32_t kBcRowsPerPass = 4;
+
+std::vector<int32_t> bc_pass_records(const Csr& c, int64_t r0, int64_t nr) {
+  const std::vector<int32_t> m = counts_descending(c, r0, nr);
+  std::vector<int32_t> recs;
+  for (int64_t i = 0; i < nr; i += kBcRowsPerPass) recs.push_back((m[i] + 15) / 16);
+  return recs;
+}
+
+// Passes are dealt to wavefronts longest first, each to the least loaded one.  False when a
+// wavefront would hold more than rmax records.
 bool bc_deal(const std::vector<int32_t>& pass_recs, int waves, int rmax, std::vector<std::vector<int32_t>>* per_wave) {
   std::vector<int32_t> order(pass_recs.size());
   for (size_t k = 0; k < order.size(); ++k) order[k] = static_cast<int32_t>(k);
@@ -4305,360 +4356,404 @@ bool bc_deal(const std::vector<int32_t>& pass_recs, int waves, int rmax, std::ve
   return true;
 }
 
-// Records of the passes of rows r0 .. r0+nr-1 once ordered by operand count (descending).
-constexpr int32_t kBcRowsPerPass = 4;
-
-std::vector<int32_t> bc_pass_records(const int32_t* row_ptr_host, int64_t r0, int64_t nr, bool sorted) {
-  std::vector<int32_t> m(static_cast<size_t>(nr));
-  for (int64_t i = 0; i < nr; ++i) m[i] = row_ptr_host[r0 + i + 1] - row_ptr_host[r0 + i];
-  if (!sorted) std::sort(m.begin(), m.end(), std::greater<int32_t>());
-  const int64_t rpw = kBcRowsPerPass;
-  std::vector<int32_t> recs;
-  for (int64_t i = 0; i < nr; i += rpw) recs.push_back((m[i] + 15) / 16);
-  return recs;
-}
-
 constexpr int64_t bc_lds_bytes(int64_t ns, int c4) { return (ns + 1) * c4 * 16; }
 
-// Lay the plan blob out (see tal_round_plan_info).  rb = dense row-block size (0 = sparse
-// form only, -1 = dense when it saves LDS reads); stream_cs > 0 pads each block's entries
-// chunk by chunk for the streamed kernel.
-int32_t finish_plan(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
-                    const double* w_host, const int32_t* out_row_host, int32_t max_col,
-                    Groups& grp, int32_t c4, int32_t dense_rb, int32_t stream_cs,
-                    int32_t* plan_host, int64_t plan_capacity_words, tal_round_plan_info* info,
-                    int32_t bc_waves = 0, int32_t bc_wg = 2) {
-  const int64_t nnz = row_ptr_host[rows];
-  const int32_t G = static_cast<int32_t>(grp.srcs.size());
-  const std::vector<int32_t>& grp_row_ptr = grp.row_ptr;
+// ---- LDS of one group (rows r0 .. r0+nr-1, ns distinct sources) --------------------------
+// The ONE sizing per form: round_plan_build's grouping predicate and the encoders' lds figures
+// (tal_round_plan_info.lds_bytes / scalar_lds_bytes, what the kernels carve) both call these,
+// so a plan the planner returns always launches.
 
-  // staged sources of a group in ascending pool-row order; operand slots
-  std::vector<int32_t> grp_src_ptr{0}, src_row, slot(nnz);
-  std::vector<int32_t> map(static_cast<size_t>(max_col) + 1, -1);
+// the staged scalar kernel (the n mod 4 tail, the int64 segment, unaligned pools) and, at
+// c4 >= 64, the round kernels' own tile + plan slice
+int64_t scalar_group_lds(const Csr& c, int32_t c4, int64_t r0, int64_t nr, int64_t ns) {
+  return group_lds_bytes(ns, nr, c.ops(r0, nr), scalar_c4(c4));
+}
+
+// The form's vector kernel.  kGrouping is what the grouping predicate budgets and differs from
+// the emitted size in the pairs form only: there it counts 3 pad pairs for every row (an upper
+// bound of padded_pairs), so groups stay as they always were while lds_bytes is exact.
+enum class Sizing { kEmitted, kGrouping };
+
+int64_t vector_group_lds(const Csr& c, const PlanForm& f, int64_t r0, int64_t nr, int64_t ns, Sizing how) {
+  if (!f.narrow()) return scalar_group_lds(c, f.c4, r0, nr, ns);
+  if (f.bcast()) return bc_lds_bytes(ns, f.c4);
+  if (f.roww) return static_cast<int64_t>(narrow_roww_lds_bytes(ns, nr, roww_padded_slots(c, r0, nr, f.c4), f.c4));
+  const int64_t pairs = how == Sizing::kGrouping ? c.ops(r0, nr) + 3 * nr : padded_pairs(c, r0, nr);
+  return static_cast<int64_t>(narrow_lds_bytes(ns, nr, pairs, f.c4));
+}
+
+// ---- the encoders: each owns the arrays it emits ------------------------------------------
+
+// Every form: a group's staged sources in ascending pool-row order and the operands' slots.
+struct PlanBase {
+  std::vector<int32_t> grp_src_ptr{0}, src_row, slot;
   int32_t max_src = 0, max_rows = 0, max_nnz = 0;
-  for (int g = 0; g < G; ++g) {
+  int64_t scalar_lds = 0;  // the largest group's, in the staged scalar kernel
+  int32_t sources(int g) const { return grp_src_ptr[g + 1] - grp_src_ptr[g]; }
+};
+
+PlanBase encode_base(const Csr& c, Groups& grp, int32_t c4) {
+  PlanBase b;
+  b.slot.resize(static_cast<size_t>(c.nnz()));
+  std::vector<int32_t> map(static_cast<size_t>(c.max_col) + 1, -1);
+  for (int g = 0; g < grp.count(); ++g) {
     std::vector<int32_t>& ss = grp.srcs[g];
     std::sort(ss.begin(), ss.end());
     for (size_t i = 0; i < ss.size(); ++i) map[ss[i]] = static_cast<int32_t>(i);
-    for (int r = grp_row_ptr[g]; r < grp_row_ptr[g + 1]; ++r)
-      for (int32_t k = row_ptr_host[r]; k < row_ptr_host[r + 1]; ++k) slot[k] = map[col_host[k]];
-    src_row.insert(src_row.end(), ss.begin(), ss.end());
-    grp_src_ptr.push_back(static_cast<int32_t>(src_row.size()));
-    max_src = std::max<int32_t>(max_src, static_cast<int32_t>(ss.size()));
-    max_rows = std::max<int32_t>(max_rows, grp_row_ptr[g + 1] - grp_row_ptr[g]);
-    max_nnz = std::max<int32_t>(max_nnz, row_ptr_host[grp_row_ptr[g + 1]] - row_ptr_host[grp_row_ptr[g]]);
+    const int32_t r0 = grp.first(g), nr = grp.rows(g), ns = static_cast<int32_t>(ss.size());
+    for (int32_t k = c.row_ptr[r0]; k < c.row_ptr[r0 + nr]; ++k) b.slot[k] = map[c.col[k]];
+    b.src_row.insert(b.src_row.end(), ss.begin(), ss.end());
+    b.grp_src_ptr.push_back(static_cast<int32_t>(b.src_row.size()));
+    b.max_src = std::max(b.max_src, ns);
+    b.max_rows = std::max(b.max_rows, nr);
+    b.max_nnz = std::max(b.max_nnz, c.ops(r0, nr));
+    b.scalar_lds = std::max(b.scalar_lds, scalar_group_lds(c, c4, r0, nr, ns));
   }
+  return b;
+}
 
-  // dense row blocks need reference order; per block of kDenseRb rows, one LDS read per
-  // table entry (distinct non-self source the block uses, padded) plus one per row for its
-  // own model
-  bool dense_ok = dense_rb != 0 && reference_order(rows, row_ptr_host, col_host);
-  std::vector<std::vector<int32_t>> blk_used;  // per block: table slots (padded), ascending
-  int64_t dense_reads = 0;
-  if (dense_ok) {
-    for (int g = 0; g < G; ++g) {
-      for (int r0 = grp_row_ptr[g]; r0 < grp_row_ptr[g + 1]; r0 += kDenseRb) {
-        std::vector<int32_t> used;
-        const int r1 = std::min(r0 + kDenseRb, grp_row_ptr[g + 1]);
-        for (int r = r0; r < r1; ++r)  // streamed tables also list each row's own model
-          for (int32_t k = row_ptr_host[r]; k < row_ptr_host[r + 1] - (stream_cs > 0 ? 0 : 1); ++k)
-            used.push_back(slot[k]);
-        std::sort(used.begin(), used.end());
-        used.erase(std::unique(used.begin(), used.end()), used.end());
-        std::vector<int32_t> tab;
-        if (stream_cs > 0) {  // each chunk's run starts on a multiple of 4 entries
-          for (size_t i = 0; i < used.size();) {
-            const int32_t chunk = used[i] / stream_cs;
-            const int32_t first = used[i];
-            while (i < used.size() && used[i] / stream_cs == chunk) tab.push_back(used[i++]);
-            while (tab.size() % 4) tab.push_back(first);  // a repeated slot marks padding (mask 0)
-          }
-        } else {
-          tab = used;
-          while (tab.size() % 4) tab.push_back(-1);
-        }
-        dense_reads += stream_cs > 0 ? static_cast<int64_t>(tab.size()) : static_cast<int64_t>(used.size()) + (r1 - r0);
-        blk_used.push_back(std::move(tab));
-      }
-    }
-    // automatic choice: dense only when one LDS read serves >= 4 operands on average (cliques);
-    // a dense entry costs every row of its block a masked multiply-add, so at the 0.69 reads per
-    // operand of a random 8-regular graph the dense form ran 6.2 vs 2.45 ms (config 3)
-    if (dense_rb == -1) dense_ok = dense_reads * 4 <= nnz;
+// Dense row blocks (also the streamed form's): per block of kDenseRb rows a table
+// {n, 7 x 0, slot[n], mask[n], w[n][rb]} (tal_round_plan_info.off_dense).
+struct DenseTables {
+  int32_t rb = 0;                    // 0: the plan stays sparse
+  std::vector<int32_t> grp_blk_ptr;  // [n_groups + 1] first block of each group
+  std::vector<int32_t> blk_off;      // [n_blocks] each table's offset in `words`
+  std::vector<int32_t> words;        // the tables, each a multiple of 8 words
+  int64_t reads = 0;                 // LDS reads per column: one per table entry (distinct source
+                                     // a block uses, padded) plus one per row for its own model
+};
+
+// The table slots of rows r0 .. r1-1: the distinct slots they use (their own models too in a
+// streamed table), ascending, padded to a multiple of 4 - with -1, or streamed, where each
+// chunk's run starts on a multiple of 4 entries, with the run's first slot (a repeated slot
+// marks padding: mask 0).
+std::vector<int32_t> block_slots(const Csr& c, const PlanBase& base, int r0, int r1, int32_t stream_cs, int64_t* reads) {
+  std::vector<int32_t> used;
+  for (int r = r0; r < r1; ++r)
+    for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1] - (stream_cs > 0 ? 0 : 1); ++k) used.push_back(base.slot[k]);
+  std::sort(used.begin(), used.end());
+  used.erase(std::unique(used.begin(), used.end()), used.end());
+  if (stream_cs == 0) {
+    *reads += static_cast<int64_t>(used.size()) + (r1 - r0);
+    while (used.size() % 4) used.push_back(-1);
+    return used;
   }
-  if (stream_cs > 0 && !dense_ok)
+  std::vector<int32_t> tab;
+  for (size_t i = 0; i < used.size();) {
+    const int32_t chunk = used[i] / stream_cs, first = used[i];
+    while (i < used.size() && used[i] / stream_cs == chunk) tab.push_back(used[i++]);
+    while (tab.size() % 4) tab.push_back(first);
+  }
+  *reads += static_cast<int64_t>(tab.size());
+  return tab;
+}
+
+void append_block_table(const Csr& c, const PlanBase& base, int r0, int r1, const std::vector<int32_t>& tabs,
+                        bool streamed, std::vector<int32_t>* out) {
+  constexpr int rb = kDenseRb;
+  const int64_t nu = static_cast<int64_t>(tabs.size());  // multiple of 4
+  const size_t at = out->size();
+  out->resize(at + 8 + static_cast<size_t>(nu) * (rb + 2), 0);  // multiple of 8: the next table stays aligned
+  int32_t* tab = out->data() + at;
+  tab[0] = static_cast<int32_t>(nu);
+  int32_t* t_slot = tab + 8;
+  int32_t* t_mask = t_slot + nu;
+  int32_t* t_w = t_mask + nu;
+  // real entries ascend strictly; padding repeats an earlier slot (or is -1: repeat the last)
+  std::vector<int64_t> entry_of;  // parallel to the sorted distinct slots
+  std::vector<int32_t> distinct;
+  for (int64_t e = 0; e < nu; ++e) {
+    const int32_t sl = tabs[e];
+    const bool pad = sl < 0 || (!distinct.empty() && sl <= distinct.back());
+    t_slot[e] = sl < 0 ? (e > 0 ? t_slot[e - 1] : 0) : sl;
+    if (!pad) {
+      distinct.push_back(sl);
+      entry_of.push_back(e);
+    }
+  }
+  auto entry = [&](int32_t k) {
+    return entry_of[std::lower_bound(distinct.begin(), distinct.end(), base.slot[k]) - distinct.begin()];
+  };
+  std::vector<int32_t> wbits(static_cast<size_t>(nu), 0);
+  std::vector<uint8_t> uniform(static_cast<size_t>(nu), 1);
+  for (int r = r0; r < r1; ++r) {
+    for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1] - 1; ++k) {  // self excluded
+      const int64_t e = entry(k);
+      const int32_t wb = f32_bits(c.w[k]);
+      if (t_mask[e] != 0 && wb != wbits[e]) uniform[e] = 0;
+      wbits[e] = wb;
+      t_mask[e] |= static_cast<int32_t>(1u << (r - r0));
+      t_w[e * rb + (r - r0)] = wb;
+    }
+  }
+  // every row using the entry has the same fp32 weight: one product w*x serves them all
+  // (identical operands round identically); the weight then fills all rb slots
+  for (int64_t e = 0; e < nu; ++e) {
+    if (t_mask[e] == 0 || !uniform[e] || __builtin_popcount(static_cast<uint32_t>(t_mask[e])) < 2) continue;
+    t_mask[e] = static_cast<int32_t>(static_cast<uint32_t>(t_mask[e]) | kMaskUniform);
+    for (int r = 0; r < rb; ++r) t_w[e * rb + r] = wbits[e];
+  }
+  if (!streamed) return;
+  for (int r = r0; r < r1; ++r) {  // bit 8+r: the entry is row r's own model (captured, added last)
+    const int64_t e = entry(c.row_ptr[r + 1] - 1);
+    t_mask[e] = static_cast<int32_t>(static_cast<uint32_t>(t_mask[e]) | (kMaskSelf0 << (r - r0)));
+  }
+}
+
+// Dense row blocks need reference order.  The automatic choice (dense_rb -1) takes them only
+// when one LDS read serves >= 4 operands on average (cliques): a dense entry costs every row of
+// its block a masked multiply-add, so at the 0.69 reads per operand of a random 8-regular graph
+// the dense form ran 6.2 vs 2.45 ms (config 3).
+int32_t encode_dense(const Csr& c, const Groups& grp, const PlanBase& base, const PlanForm& f, DenseTables* out) {
+  DenseTables& d = *out;
+  bool ok = f.dense_rb != 0 && reference_order(c);
+  std::vector<std::vector<int32_t>> slots;  // per block
+  auto each_block = [&](auto&& fn) {
+    for (int g = 0; g < grp.count(); ++g)
+      for (int r0 = grp.row_ptr[g]; r0 < grp.row_ptr[g + 1]; r0 += kDenseRb)
+        fn(g, r0, std::min(r0 + kDenseRb, grp.row_ptr[g + 1]));
+  };
+  if (ok) {
+    each_block([&](int, int r0, int r1) { slots.push_back(block_slots(c, base, r0, r1, f.stream_cs, &d.reads)); });
+    if (f.dense_rb == -1) ok = d.reads * 4 <= c.nnz();
+  }
+  if (f.stream_cs > 0 && !ok)
     return fail(TAL_ERR_INVALID, "tal_round_plan_build_stream: rows must list operands in reference order");
-  const int32_t rb = dense_ok ? kDenseRb : 0;
-  std::vector<int32_t> grp_blk_ptr{0};
-  int64_t dense_words = 0;
-  if (rb) {
-    for (int g = 0; g < G; ++g)
-      grp_blk_ptr.push_back(grp_blk_ptr.back() + (grp_row_ptr[g + 1] - grp_row_ptr[g] + rb - 1) / rb);
-    for (const auto& u : blk_used) dense_words += 8 + static_cast<int64_t>(u.size()) * (rb + 2);
-  }
-  const int32_t n_blocks = rb ? grp_blk_ptr.back() : 0;
+  if (!ok) return TAL_OK;
+  d.rb = kDenseRb;
+  d.grp_blk_ptr.assign(1, 0);
+  for (int g = 0; g < grp.count(); ++g) d.grp_blk_ptr.push_back(d.grp_blk_ptr.back() + (grp.rows(g) + d.rb - 1) / d.rb);
+  each_block([&](int, int r0, int r1) {
+    d.blk_off.push_back(static_cast<int32_t>(d.words.size()));
+    append_block_table(c, base, r0, r1, slots[d.blk_off.size() - 1], f.stream_cs > 0, &d.words);
+  });
+  return TAL_OK;
+}
 
-  // narrow form: (slot * c4, weight) pairs, each row's operands after the first padded to whole
-  // batches of 4 with (max_src * c4, 1.0f): the kernel's -0.0 tile makes them exact identities
-  std::vector<int32_t> nrp, npr;
-  int64_t max_np = 0;
-  int64_t lds_need = 0;  // the largest group's LDS (exact, per group: what the kernels carve)
-  for (int g = 0; g < G; ++g) {
-    const int64_t nr = grp_row_ptr[g + 1] - grp_row_ptr[g];
-    const int64_t no = row_ptr_host[grp_row_ptr[g + 1]] - row_ptr_host[grp_row_ptr[g]];
-    lds_need = std::max(lds_need, group_lds_bytes(grp_src_ptr[g + 1] - grp_src_ptr[g], nr, no, scalar_c4(c4)));
+// The narrow kernel's own encoding of the rows (off_nrow_ptr, off_npairs, off_nrow_w).
+struct NarrowArrays {
+  std::vector<int32_t> row_ptr;  // [rows + 1] pair (ROWW: slot) offset of each row
+  std::vector<int32_t> words;    // the pairs, or the 16-bit slots two per word
+  std::vector<int32_t> row_w;    // ROWW: [rows] weight bits
+  int64_t count = 0;             // pairs (slots) over all rows
+  int64_t max_group = 0;         // ... of the largest group
+  int64_t lds = 0;               // the largest group's, in the narrow kernel
+};
+
+// (slot * c4, weight) pairs, each row's operands after the first padded to whole batches of 4
+// with (ns * c4, 1.0f): the kernel's -0.0 tile makes them exact identities.
+NarrowArrays encode_narrow_pairs(const Csr& c, const Groups& grp, const PlanBase& base, const PlanForm& f) {
+  NarrowArrays a;
+  a.row_ptr.assign(static_cast<size_t>(c.rows) + 1, 0);
+  const int32_t one_bits = f32_bits(1.0);
+  for (int g = 0; g < grp.count(); ++g) {
+    const int32_t ns = base.sources(g), r0 = grp.first(g), nr = grp.rows(g);
+    const int64_t g0 = static_cast<int64_t>(a.words.size()) / 2;
+    for (int r = r0; r < r0 + nr; ++r) {
+      for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) {
+        a.words.push_back(base.slot[k] * f.c4);
+        a.words.push_back(f32_bits(c.w[k]));
+      }
+      for (int32_t pad = (4 - (c.ops(r) - 1) % 4) % 4; pad > 0; --pad) {
+        a.words.push_back(ns * f.c4);  // the group's -0.0 tile
+        a.words.push_back(one_bits);
+      }
+      a.row_ptr[r + 1] = static_cast<int32_t>(a.words.size() / 2);
+    }
+    a.max_group = std::max(a.max_group, static_cast<int64_t>(a.words.size()) / 2 - g0);
+    a.lds = std::max(a.lds, vector_group_lds(c, f, r0, nr, ns, Sizing::kEmitted));
   }
-  const int64_t scalar_need = lds_need;
-  const bool roww = bc_waves == 0 && c4 < 64 && rows_uniform_weights(rows, row_ptr_host, w_host) &&
-                    roww_slots_fit(max_col, c4);
-  std::vector<uint16_t> nsl;   // ROWW slots
-  std::vector<int32_t> nrw;    // ROWW row weights
-  std::vector<int32_t> bcp;    // broadcast form: program offsets (relative to the program region)
-  std::vector<int32_t> bcw;    // broadcast form: the programs
-  int64_t bc_records = 0;
-  const int32_t bc_rmax = bc_waves > 0 ? kBcRecPerWg / bc_waves : 0;
-  if (c4 < 64 && bc_waves > 0) {
-    lds_need = 0;
-    const int32_t rpw = kBcRowsPerPass;
-    const float one = 1.0f;
-    int32_t one_bits;
-    memcpy(&one_bits, &one, 4);
-    bcp.assign(static_cast<size_t>(G) * bc_waves, 0);
-    for (int g = 0; g < G; ++g) {
-      const int32_t ns = grp_src_ptr[g + 1] - grp_src_ptr[g];
-      const int32_t r0 = grp_row_ptr[g], nr = grp_row_ptr[g + 1] - r0;
-      lds_need = std::max<int64_t>(lds_need, bc_lds_bytes(ns, c4));
-      const std::vector<int32_t> recs = bc_pass_records(row_ptr_host, r0, nr, true);
-      std::vector<std::vector<int32_t>> per_wave;
-      if (!bc_deal(recs, bc_waves, bc_rmax, &per_wave))
-        return fail(TAL_ERR_CAPACITY, "tal_round_plan_build_bcast: a group's records exceed the wavefronts' registers");
-      for (int w = 0; w < bc_waves; ++w) {
-        if (bcw.size() % 2) bcw.push_back(0);
-        const size_t start = bcw.size();
-        bcp[static_cast<size_t>(g) * bc_waves + w] = static_cast<int32_t>(start);
-        const std::vector<int32_t>& ps = per_wave[w];
-        int32_t n_rec = 0;
-        for (int32_t k : ps) n_rec += recs[k];
-        bc_records += n_rec;
-        const size_t np = ps.size();
-        const size_t data_off = (kBcHdr + bc_rmax + 4 * np + 1) / 2 * 2;
-        bcw.resize(start + data_off + 128 * static_cast<size_t>(n_rec), 0);
-        int32_t* pr = bcw.data() + start;
-        pr[0] = n_rec;
-        pr[1] = static_cast<int32_t>(np);
-        pr[2] = static_cast<int32_t>(data_off);
-        int32_t ri = 0;
-        for (size_t i = 0; i < np; ++i) {
-          const int32_t k = ps[i];
-          const int32_t pr0 = r0 + k * rpw, prows = std::min(rpw, r0 + nr - pr0);
-          const int32_t m_lead = row_ptr_host[pr0 + 1] - row_ptr_host[pr0];
-          for (int sb = 0; sb < 4; ++sb) pr[kBcHdr + bc_rmax + 4 * i + sb] = sb < prows ? out_row_host[pr0 + sb] : -1;
-          for (int32_t c = 0; c < recs[k]; ++c, ++ri) {
-            const int32_t cnt = std::min(16, m_lead - 16 * c);
-            pr[kBcHdr + ri] = cnt | ((c == recs[k] - 1) ? 0x100 : 0) | static_cast<int32_t>(i << 16);
-            int32_t* rec = pr + data_off + 128 * static_cast<size_t>(ri);
-            for (int L = 0; L < 64; ++L) {
-              const int32_t sb = L / 16, j = 16 * c + L % 16;
-              int32_t off = ns * c4 * 16, wb = one_bits;  // identity pad: the -0.0 tile, weight 1.0
-              if (sb < prows) {
-                const int32_t row = pr0 + sb, k0 = row_ptr_host[row];
-                if (j < row_ptr_host[row + 1] - k0) {
-                  off = slot[k0 + j] * c4 * 16;
-                  const float wf = static_cast<float>(w_host[k0 + j]);
-                  memcpy(&wb, &wf, 4);
-                }
-              }
-              rec[2 * L] = off;
-              rec[2 * L + 1] = wb;
-            }
-          }
+  a.count = static_cast<int64_t>(a.words.size()) / 2;
+  return a;
+}
+
+// ROWW: slots only, in batches of 4, every row of a pass padded to the batch count of the pass's
+// first (longest: rows are ordered by count) row; the pad reads the zero tile that keeps -0:
+// fl(w * z) is -0.0 for z = -0.0 (w >= 0) or +0.0 (w < 0).
+NarrowArrays encode_narrow_roww(const Csr& c, const Groups& grp, const PlanBase& base, const PlanForm& f) {
+  NarrowArrays a;
+  a.row_ptr.assign(static_cast<size_t>(c.rows) + 1, 0);
+  std::vector<uint16_t> nsl;
+  const int32_t rpw = 64 / f.c4;
+  for (int g = 0; g < grp.count(); ++g) {
+    const int32_t ns = base.sources(g), r0 = grp.first(g), nr = grp.rows(g);
+    const size_t g0 = nsl.size();
+    for (int r = r0; r < r0 + nr; ++r) {
+      a.row_w.push_back(f32_bits(c.w[c.row_ptr[r]]));
+      const int32_t lead = r0 + (r - r0) / rpw * rpw;
+      const size_t end = nsl.size() + 4 * static_cast<size_t>((c.ops(lead) + 3) / 4);
+      for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) nsl.push_back(static_cast<uint16_t>(base.slot[k] * f.c4));
+      const bool neg = std::signbit(static_cast<float>(c.w[c.row_ptr[r]]));
+      while (nsl.size() < end) nsl.push_back(static_cast<uint16_t>((neg ? ns + 1 : ns) * f.c4));
+      a.row_ptr[r + 1] = static_cast<int32_t>(nsl.size());
+    }
+    a.max_group = std::max(a.max_group, static_cast<int64_t>(nsl.size() - g0));
+    a.lds = std::max(a.lds, vector_group_lds(c, f, r0, nr, ns, Sizing::kEmitted));
+  }
+  a.count = static_cast<int64_t>(nsl.size());
+  a.words.assign((nsl.size() + 1) / 2, 0);  // two slots per int32 word
+  memcpy(a.words.data(), nsl.data(), 2 * nsl.size());
+  return a;
+}
+
+// Broadcast form: every wavefront's program (tal_round_plan_info.off_bc_prog).
+struct BcastPrograms {
+  std::vector<int32_t> prog_off;  // [n_groups * waves] each program's (even) offset in `words`
+  std::vector<int32_t> words;
+  int64_t records = 0;
+  int64_t lds = 0;  // the largest group's: its data tile and the -0.0 tile
+};
+
+// One record: 64 lanes x {LDS byte offset, weight bits} holding operands 16c .. 16c+15 of the
+// pass's rows pr0 .. pr0+prows-1; past a row's count the identity pad (the -0.0 tile at slot
+// ns, weight 1.0).
+void fill_bc_record(const Csr& c, const PlanBase& base, int32_t c4, int32_t ns, int32_t pr0, int32_t prows,
+                    int32_t rec_c, int32_t* rec) {
+  for (int L = 0; L < 64; ++L) {
+    const int32_t row = pr0 + L / 16, j = 16 * rec_c + L % 16;
+    const bool real = L / 16 < prows && j < c.ops(row);
+    const int32_t k = real ? c.row_ptr[row] + j : 0;
+    rec[2 * L] = (real ? base.slot[k] : ns) * c4 * 16;
+    rec[2 * L + 1] = f32_bits(real ? c.w[k] : 1.0);
+  }
+}
+
+int32_t encode_bcast(const Csr& c, const Groups& grp, const PlanBase& base, const PlanForm& f, BcastPrograms* out) {
+  BcastPrograms& b = *out;
+  const int32_t rmax = kBcRecPerWg / f.bc_waves, rpw = kBcRowsPerPass;
+  b.prog_off.assign(static_cast<size_t>(grp.count()) * f.bc_waves, 0);
+  for (int g = 0; g < grp.count(); ++g) {
+    const int32_t ns = base.sources(g), r0 = grp.first(g), nr = grp.rows(g);
+    b.lds = std::max(b.lds, vector_group_lds(c, f, r0, nr, ns, Sizing::kEmitted));
+    const std::vector<int32_t> recs = bc_pass_records(c, r0, nr);
+    std::vector<std::vector<int32_t>> per_wave;
+    if (!bc_deal(recs, f.bc_waves, rmax, &per_wave))
+      return fail(TAL_ERR_CAPACITY, "tal_round_plan_build_bcast: a group's records exceed the wavefronts' registers");
+    for (int w = 0; w < f.bc_waves; ++w) {
+      if (b.words.size() % 2) b.words.push_back(0);
+      const size_t start = b.words.size();
+      b.prog_off[static_cast<size_t>(g) * f.bc_waves + w] = static_cast<int32_t>(start);
+      const std::vector<int32_t>& ps = per_wave[w];
+      int32_t n_rec = 0;
+      for (int32_t k : ps) n_rec += recs[k];
+      b.records += n_rec;
+      const size_t np = ps.size();
+      const size_t data_off = (kBcHdr + rmax + 4 * np + 1) / 2 * 2;
+      b.words.resize(start + data_off + 128 * static_cast<size_t>(n_rec), 0);
+      int32_t* pr = b.words.data() + start;
+      pr[0] = n_rec;
+      pr[1] = static_cast<int32_t>(np);
+      pr[2] = static_cast<int32_t>(data_off);
+      int32_t ri = 0;
+      for (size_t i = 0; i < np; ++i) {
+        const int32_t k = ps[i];
+        const int32_t pr0 = r0 + k * rpw, prows = std::min(rpw, r0 + nr - pr0);
+        for (int sb = 0; sb < 4; ++sb) pr[kBcHdr + rmax + 4 * i + sb] = sb < prows ? c.out_row[pr0 + sb] : -1;
+        for (int32_t rc = 0; rc < recs[k]; ++rc, ++ri) {
+          const int32_t cnt = std::min(16, c.ops(pr0) - 16 * rc);
+          pr[kBcHdr + ri] = cnt | ((rc == recs[k] - 1) ? 0x100 : 0) | static_cast<int32_t>(i << 16);
+          fill_bc_record(c, base, f.c4, ns, pr0, prows, rc, pr + data_off + 128 * static_cast<size_t>(ri));
         }
       }
     }
-  } else if (c4 < 64) {
-    lds_need = 0;  // the narrow kernel's carve replaces the staged one
-    nrp.assign(static_cast<size_t>(rows) + 1, 0);
-    const float one = 1.0f;
-    int32_t one_bits;
-    memcpy(&one_bits, &one, 4);
-    for (int g = 0; g < G; ++g) {
-      const int32_t ns = grp_src_ptr[g + 1] - grp_src_ptr[g];
-      const int64_t g0 = roww ? static_cast<int64_t>(nsl.size()) : static_cast<int64_t>(npr.size()) / 2;
-      for (int r = grp_row_ptr[g]; r < grp_row_ptr[g + 1]; ++r) {
-        const int32_t k0 = row_ptr_host[r], k1 = row_ptr_host[r + 1];
-        if (roww) {  // slots only, in batches of 4, every row of a pass padded to the batch count
-          // of the pass's first (longest: rows are ordered by count) row; the pad reads the zero
-          // tile that keeps -0: fl(w * z) is -0.0 for z = -0.0 (w >= 0) or +0.0 (w < 0)
-          const float wf = static_cast<float>(w_host[k0]);
-          int32_t wb;
-          memcpy(&wb, &wf, 4);
-          nrw.push_back(wb);
-          const int32_t lead = grp_row_ptr[g] + (r - grp_row_ptr[g]) / (64 / c4) * (64 / c4);
-          const int64_t nb = (row_ptr_host[lead + 1] - row_ptr_host[lead] + 3) / 4;
-          const size_t start = nsl.size();
-          for (int32_t k = k0; k < k1; ++k) nsl.push_back(static_cast<uint16_t>(slot[k] * c4));
-          const uint16_t zero = static_cast<uint16_t>((std::signbit(wf) ? ns + 1 : ns) * c4);
-          while (nsl.size() < start + 4 * static_cast<size_t>(nb)) nsl.push_back(zero);
-          nrp[r + 1] = static_cast<int32_t>(nsl.size());
-          continue;
-        }
-        for (int32_t k = k0; k < k1; ++k) {
-          const float wf = static_cast<float>(w_host[k]);
-          int32_t wb;
-          memcpy(&wb, &wf, 4);
-          npr.push_back(slot[k] * c4);
-          npr.push_back(wb);
-        }
-        for (int32_t pad = (4 - (k1 - k0 - 1) % 4) % 4; pad > 0; --pad) {
-          npr.push_back(ns * c4);  // the group's -0.0 tile
-          npr.push_back(one_bits);
-        }
-        nrp[r + 1] = static_cast<int32_t>(npr.size() / 2);
-      }
-      const int64_t gp = (roww ? static_cast<int64_t>(nsl.size()) : static_cast<int64_t>(npr.size()) / 2) - g0;
-      max_np = std::max<int64_t>(max_np, gp);
-      const int64_t nr = grp_row_ptr[g + 1] - grp_row_ptr[g];
-      lds_need = std::max<int64_t>(lds_need, static_cast<int64_t>(
-          roww ? narrow_roww_lds_bytes(ns, nr, gp, c4) : narrow_lds_bytes(ns, nr, gp, c4)));
-    }
-    if (roww) {  // two slots per int32 word
-      npr.assign((nsl.size() + 1) / 2, 0);
-      memcpy(npr.data(), nsl.data(), 2 * nsl.size());
-    }
   }
+  return TAL_OK;
+}
 
+// Assign the blob's offsets (see tal_round_plan_info) and copy the arrays in.
+int32_t write_plan(const Csr& c, const Groups& grp, const PlanForm& f, const PlanBase& base, const DenseTables& d,
+                   const NarrowArrays& na, const BcastPrograms& bc, int32_t* plan_host, int64_t plan_capacity_words,
+                   tal_round_plan_info* info) {
+  const int64_t nnz = c.nnz();
+  const int32_t rows = c.rows, G = grp.count(), n_blocks = static_cast<int32_t>(d.blk_off.size());
   tal_round_plan_info in;
   memset(&in, 0, sizeof(in));
   in.rows = rows;
   in.nnz = static_cast<int32_t>(nnz);
   in.n_groups = G;
-  in.total_src = static_cast<int32_t>(src_row.size());
-  in.max_src = max_src;
-  in.max_rows = max_rows;
-  in.max_nnz = max_nnz;
-  in.c4 = c4;
-  in.dense_rb = rb;
+  in.total_src = static_cast<int32_t>(base.src_row.size());
+  in.max_src = base.max_src;
+  in.max_rows = base.max_rows;
+  in.max_nnz = base.max_nnz;
+  in.c4 = f.c4;
+  in.dense_rb = d.rb;
   in.n_blocks = n_blocks;
-  in.dense_reads = static_cast<int32_t>(rb ? dense_reads : nnz);
-  in.stream_cs = stream_cs;
+  in.dense_reads = static_cast<int32_t>(d.rb ? d.reads : nnz);
+  in.stream_cs = f.stream_cs;
   int64_t off = 0;
-  in.off_grp_row_ptr = static_cast<int32_t>(off); off += G + 1;
-  in.off_grp_src_ptr = static_cast<int32_t>(off); off += G + 1;
-  in.off_src_row = static_cast<int32_t>(off); off += in.total_src;
-  in.off_row_ptr = static_cast<int32_t>(off); off += rows + 1;
-  in.off_op_slot = static_cast<int32_t>(off); off += nnz;
-  in.off_op_w = static_cast<int32_t>(off); off += nnz;
-  in.off_out_row = static_cast<int32_t>(off); off += rows;
-  in.off_grp_blk_ptr = static_cast<int32_t>(off); off += rb ? G + 1 : 0;
-  in.off_blk_tab = static_cast<int32_t>(off); off += n_blocks;
+  auto take = [&](int64_t words) { const int64_t at = off; off += words; return static_cast<int32_t>(at); };
+  in.off_grp_row_ptr = take(G + 1);
+  in.off_grp_src_ptr = take(G + 1);
+  in.off_src_row = take(in.total_src);
+  in.off_row_ptr = take(rows + 1);
+  in.off_op_slot = take(nnz);
+  in.off_op_w = take(nnz);
+  in.off_out_row = take(rows);
+  in.off_grp_blk_ptr = take(static_cast<int64_t>(d.grp_blk_ptr.size()));
+  in.off_blk_tab = take(n_blocks);
   off = (off + 7) / 8 * 8;  // dense tables 32-B aligned (vector scalar loads)
-  in.off_dense = static_cast<int32_t>(off); off += dense_words;
-  in.off_nrow_ptr = static_cast<int32_t>(off); off += static_cast<int64_t>(nrp.size());
-  in.off_npairs = static_cast<int32_t>(off); off += static_cast<int64_t>(npr.size());
-  in.npairs = static_cast<int32_t>(roww ? nsl.size() : npr.size() / 2);
-  in.max_npairs = static_cast<int32_t>(max_np);
-  in.narrow_roww = roww ? 1 : 0;
-  in.off_nrow_w = static_cast<int32_t>(off); off += static_cast<int64_t>(nrw.size());
-  in.scalar_lds_bytes = static_cast<int32_t>(scalar_need);
-  in.narrow_bcast = bc_waves > 0 && c4 < 64 ? bc_waves : 0;
-  in.bc_rec_max = in.narrow_bcast ? bc_rmax : 0;
-  in.bc_wg_per_cu = in.narrow_bcast ? bc_wg : 0;
-  in.bc_records = static_cast<int32_t>(bc_records);
-  in.off_bc_prog = static_cast<int32_t>(off); off += static_cast<int64_t>(bcp.size());
+  in.off_dense = take(static_cast<int64_t>(d.words.size()));
+  in.off_nrow_ptr = take(static_cast<int64_t>(na.row_ptr.size()));
+  in.off_npairs = take(static_cast<int64_t>(na.words.size()));
+  in.npairs = static_cast<int32_t>(na.count);
+  in.max_npairs = static_cast<int32_t>(na.max_group);
+  in.narrow_roww = f.roww ? 1 : 0;
+  in.off_nrow_w = take(static_cast<int64_t>(na.row_w.size()));
+  in.scalar_lds_bytes = static_cast<int32_t>(base.scalar_lds);
+  in.narrow_bcast = f.bcast() ? f.bc_waves : 0;
+  in.bc_rec_max = f.bcast() ? kBcRecPerWg / f.bc_waves : 0;
+  in.bc_wg_per_cu = f.bcast() ? f.bc_wg : 0;
+  in.bc_records = static_cast<int32_t>(bc.records);
+  in.off_bc_prog = take(static_cast<int64_t>(bc.prog_off.size()));
   off = (off + 1) / 2 * 2;  // programs start on an even word (8-B records)
-  const int64_t bc_region = off;
-  off += static_cast<int64_t>(bcw.size());
+  const int32_t bc_region = take(static_cast<int64_t>(bc.words.size()));
   if (off > 0x7fffffff) return fail(TAL_ERR_INVALID, "tal_round_plan_build: plan larger than 2^31 words");
   in.words = static_cast<int32_t>(off);
-  in.lds_bytes = static_cast<int32_t>(stream_cs > 0 ? stream_lds_bytes(stream_cs) : lds_need);
-  if (!plan_host || off > plan_capacity_words) {
-    *info = in;
+  // the vector kernel's LDS: the streamed ring, the narrow form's own carve, else the staged tile + slice
+  in.lds_bytes = static_cast<int32_t>(f.stream_cs > 0 ? stream_lds_bytes(f.stream_cs)
+                                      : f.bcast()     ? bc.lds
+                                      : f.narrow()    ? na.lds
+                                                      : base.scalar_lds);
+  *info = in;
+  if (!plan_host || off > plan_capacity_words)
     return fail(TAL_ERR_CAPACITY, "tal_round_plan_build: plan buffer too small: need " +
                                       std::to_string(off) + " words");
-  }
 
-  memcpy(plan_host + in.off_grp_row_ptr, grp_row_ptr.data(), 4 * (G + 1));
-  memcpy(plan_host + in.off_grp_src_ptr, grp_src_ptr.data(), 4 * (G + 1));
-  memcpy(plan_host + in.off_src_row, src_row.data(), 4 * src_row.size());
-  memcpy(plan_host + in.off_row_ptr, row_ptr_host, 4 * (static_cast<size_t>(rows) + 1));
-  memcpy(plan_host + in.off_op_slot, slot.data(), 4 * nnz);
-  for (int64_t k = 0; k < nnz; ++k) {
-    const float wf = static_cast<float>(w_host[k]);
-    memcpy(plan_host + in.off_op_w + k, &wf, 4);
-  }
-  memcpy(plan_host + in.off_out_row, out_row_host, 4 * static_cast<size_t>(rows));
-  if (!nrp.empty()) {
-    memcpy(plan_host + in.off_nrow_ptr, nrp.data(), 4 * nrp.size());
-    memcpy(plan_host + in.off_npairs, npr.data(), 4 * npr.size());
-  }
-  if (!nrw.empty()) memcpy(plan_host + in.off_nrow_w, nrw.data(), 4 * nrw.size());
-  for (size_t k = 0; k < bcp.size(); ++k) plan_host[in.off_bc_prog + k] = static_cast<int32_t>(bc_region + bcp[k]);
-  if (!bcw.empty()) memcpy(plan_host + bc_region, bcw.data(), 4 * bcw.size());
-  if (rb) {
-    memcpy(plan_host + in.off_grp_blk_ptr, grp_blk_ptr.data(), 4 * (G + 1));
-    int64_t pos = in.off_dense;
-    int b = 0;
-    for (int g = 0; g < G; ++g) {
-      for (int r0 = grp_row_ptr[g]; r0 < grp_row_ptr[g + 1]; r0 += rb, ++b) {
-        const std::vector<int32_t>& tabs = blk_used[b];
-        const int64_t nu = static_cast<int64_t>(tabs.size());  // multiple of 4
-        plan_host[in.off_blk_tab + b] = static_cast<int32_t>(pos);
-        int32_t* tab = plan_host + pos;
-        const int64_t words = 8 + nu * (rb + 2);  // multiple of 8: the next table stays aligned
-        memset(tab, 0, 4 * static_cast<size_t>(words));
-        tab[0] = static_cast<int32_t>(nu);
-        int32_t* t_slot = tab + 8;
-        int32_t* t_mask = t_slot + nu;
-        int32_t* t_w = t_mask + nu;
-        // real entries ascend strictly; padding repeats an earlier slot (or is -1: repeat the last)
-        std::vector<int64_t> entry_of;  // parallel to the sorted distinct slots
-        std::vector<int32_t> distinct;
-        for (int64_t e = 0; e < nu; ++e) {
-          const int32_t sl = tabs[e];
-          const bool pad = sl < 0 || (!distinct.empty() && sl <= distinct.back());  // real slots ascend
-          t_slot[e] = sl < 0 ? (e > 0 ? t_slot[e - 1] : 0) : sl;
-          if (!pad) {
-            distinct.push_back(sl);
-            entry_of.push_back(e);
-          }
-        }
-        std::vector<uint32_t> wbits(static_cast<size_t>(nu), 0);
-        std::vector<uint8_t> uniform(static_cast<size_t>(nu), 1);
-        for (int r = r0; r < std::min(r0 + rb, grp_row_ptr[g + 1]); ++r) {
-          for (int32_t k = row_ptr_host[r]; k < row_ptr_host[r + 1] - 1; ++k) {  // self excluded
-            const int64_t d = std::lower_bound(distinct.begin(), distinct.end(), slot[k]) - distinct.begin();
-            const int64_t e = entry_of[d];
-            const float wf = static_cast<float>(w_host[k]);
-            uint32_t wb;
-            memcpy(&wb, &wf, 4);
-            if (t_mask[e] != 0 && wb != wbits[e]) uniform[e] = 0;
-            wbits[e] = wb;
-            t_mask[e] |= static_cast<int32_t>(1u << (r - r0));
-            memcpy(t_w + e * rb + (r - r0), &wf, 4);
-          }
-        }
-        // every row using the entry has the same fp32 weight: one product w*x serves them all
-        // (identical operands round identically); the weight then fills all rb slots
-        for (int64_t e = 0; e < nu; ++e) {
-          if (t_mask[e] == 0 || !uniform[e] || __builtin_popcount(static_cast<uint32_t>(t_mask[e])) < 2) continue;
-          t_mask[e] = static_cast<int32_t>(static_cast<uint32_t>(t_mask[e]) | kMaskUniform);
-          for (int r = 0; r < rb; ++r) memcpy(t_w + e * rb + r, &wbits[e], 4);
-        }
-        if (stream_cs > 0) {  // bit 8+r: the entry is row r's own model (captured, added last)
-          for (int r = r0; r < std::min(r0 + rb, grp_row_ptr[g + 1]); ++r) {
-            const int32_t ks = row_ptr_host[r + 1] - 1;
-            const int64_t d = std::lower_bound(distinct.begin(), distinct.end(), slot[ks]) - distinct.begin();
-            t_mask[entry_of[d]] = static_cast<int32_t>(static_cast<uint32_t>(t_mask[entry_of[d]]) |
-                                                       (kMaskSelf0 << (r - r0)));
-          }
-        }
-        pos += words;
-      }
-    }
-  }
-  *info = in;
+  auto put = [&](int32_t at, const std::vector<int32_t>& v) {
+    if (!v.empty()) memcpy(plan_host + at, v.data(), 4 * v.size());
+  };
+  put(in.off_grp_row_ptr, grp.row_ptr);
+  put(in.off_grp_src_ptr, base.grp_src_ptr);
+  put(in.off_src_row, base.src_row);
+  memcpy(plan_host + in.off_row_ptr, c.row_ptr, 4 * (static_cast<size_t>(rows) + 1));
+  put(in.off_op_slot, base.slot);
+  for (int64_t k = 0; k < nnz; ++k) plan_host[in.off_op_w + k] = f32_bits(c.w[k]);
+  memcpy(plan_host + in.off_out_row, c.out_row, 4 * static_cast<size_t>(rows));
+  put(in.off_grp_blk_ptr, d.grp_blk_ptr);
+  for (int32_t b = 0; b < n_blocks; ++b) plan_host[in.off_blk_tab + b] = in.off_dense + d.blk_off[b];
+  put(in.off_dense, d.words);
+  put(in.off_nrow_ptr, na.row_ptr);
+  put(in.off_npairs, na.words);
+  put(in.off_nrow_w, na.row_w);
+  for (size_t k = 0; k < bc.prog_off.size(); ++k) plan_host[in.off_bc_prog + k] = bc_region + bc.prog_off[k];
+  put(bc_region, bc.words);
   g_err.clear();
   return TAL_OK;
+}
+
+// Lay the plan of grouped rows out in form f: the common arrays, then the form's own.
+int32_t finish_plan(const Csr& c, Groups& grp, const PlanForm& f, int32_t* plan_host, int64_t plan_capacity_words,
+                    tal_round_plan_info* info) {
+  const PlanBase base = encode_base(c, grp, f.c4);
+  DenseTables dense;
+  NarrowArrays narrow;
+  BcastPrograms bcast;
+  int32_t rc = encode_dense(c, grp, base, f, &dense);
+  if (rc == TAL_OK && f.bcast()) rc = encode_bcast(c, grp, base, f, &bcast);
+  if (rc) return rc;
+  if (f.narrow() && !f.bcast())
+    narrow = f.roww ? encode_narrow_roww(c, grp, base, f) : encode_narrow_pairs(c, grp, base, f);
+  return write_plan(c, grp, f, base, dense, narrow, bcast, plan_host, plan_capacity_words, info);
 }
 
 }  // namespace
@@ -4789,70 +4884,167 @@ int64_t tal_round_plan_words(int32_t rows, int64_t nnz) {
 
 namespace {
 
-int32_t round_plan_build(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
-                         const double* w_host, const int32_t* out_row_host, int32_t c4,
-                         int32_t lds_bytes, int32_t dense_rb, int32_t* plan_host,
-                         int64_t plan_capacity_words, tal_round_plan_info* info, int32_t bc_waves,
-                         int32_t bc_wg) {
+// The rows of each group ordered by operand count (descending, stable), into `out`'s own
+// storage: a narrow wavefront pass computes 64 / c4 consecutive plan rows in lock step, so rows
+// of a pass then have similar counts and few lanes idle.  Rows are independent and each names
+// its output row, so the order is free.
+struct OrderedCsr {
+  std::vector<int32_t> row_ptr, col, out_row;
+  std::vector<double> w;
+  Csr csr;
+};
+
+void order_rows_by_count(const Csr& c, const Groups& grp, OrderedCsr* out) {
+  std::vector<int32_t> perm(c.rows);
+  for (int g = 0; g < grp.count(); ++g) {
+    const auto r0 = perm.begin() + grp.row_ptr[g], r1 = perm.begin() + grp.row_ptr[g + 1];
+    std::iota(r0, r1, grp.row_ptr[g]);
+    std::stable_sort(r0, r1, [&](int32_t a, int32_t b) { return c.ops(a) > c.ops(b); });
+  }
+  out->row_ptr.assign(static_cast<size_t>(c.rows) + 1, 0);
+  out->col.resize(static_cast<size_t>(c.nnz()));
+  out->w.resize(static_cast<size_t>(c.nnz()));
+  out->out_row.resize(c.rows);
+  for (int r = 0; r < c.rows; ++r) {
+    const int32_t src = perm[r], k0 = c.row_ptr[src], k1 = c.row_ptr[src + 1], at = out->row_ptr[r];
+    out->row_ptr[r + 1] = at + (k1 - k0);
+    std::copy(c.col + k0, c.col + k1, out->col.begin() + at);
+    std::copy(c.w + k0, c.w + k1, out->w.begin() + at);
+    out->out_row[r] = c.out_row[src];
+  }
+  out->csr = Csr{c.rows, out->row_ptr.data(), out->col.data(), out->w.data(), out->out_row.data(), c.max_col};
+}
+
+int32_t round_plan_build(Csr c, PlanForm f, int32_t lds_bytes, int32_t* plan_host, int64_t plan_capacity_words,
+                         tal_round_plan_info* info) {
   if (!info) return fail(TAL_ERR_INVALID, "tal_round_plan_build: bad arguments");
-  int32_t max_col = 0;
-  int32_t rc = check_csr("tal_round_plan_build", rows, row_ptr_host, col_host, w_host, out_row_host, &max_col);
+  int32_t rc = check_csr("tal_round_plan_build", &c);
   if (rc) return rc;
-  if (c4 != 16 && c4 != 32 && c4 != 64 && c4 != 128)
+  if (f.c4 != 16 && f.c4 != 32 && f.c4 != 64 && f.c4 != 128)
     return fail(TAL_ERR_INVALID, "tal_round_plan_build: c4 must be 16, 32, 64 or 128");
-  if (c4 < 64) dense_rb = 0;  // narrow tiles: sparse form (a wavefront covers 64 / c4 rows)
-  if (dense_rb != 0 && dense_rb != kDenseRb && dense_rb != -1)
+  if (f.narrow()) f.dense_rb = 0;  // narrow tiles: sparse form (a wavefront covers 64 / c4 rows)
+  if (f.dense_rb != 0 && f.dense_rb != kDenseRb && f.dense_rb != -1)
     return fail(TAL_ERR_INVALID, "tal_round_plan_build: dense_rb must be 0, 8 or -1");
-  // group consecutive rows while the union of their sources fits the LDS budget (both round
-  // kernels stage 16*c4 bytes per source; the scalar one also the plan slice)
-  const bool roww = c4 < 64 && rows_uniform_weights(rows, row_ptr_host, w_host) && roww_slots_fit(max_col, c4);
-  std::vector<int32_t> batches;
-  auto fits = [&](int64_t ns, int64_t nr, int64_t no, int64_t r0) {
-    const int64_t sliced = group_lds_bytes(ns, nr, no, scalar_c4(c4));  // c4 >= 64: the round kernel's own
-    if (c4 >= 64) return sliced <= lds_bytes;
-    // narrow kernel: its own carve (exact ROWW padding; pairs: <= 3 per row) and read-ahead
-    // within the budget; the staged scalar tail kernel within the hardware's 160 KiB
-    if (bc_waves > 0) {
-      std::vector<std::vector<int32_t>> per_wave;
-      // staging: what the form's launch takes (bc_max_loads)
-      return bc_lds_bytes(ns, c4) <= lds_bytes && ns * c4 <= bc_max_loads(c4, bc_waves, bc_wg) && sliced <= 160 * 1024 &&
-             bc_deal(bc_pass_records(row_ptr_host, r0, nr, false), bc_waves, kBcRecPerWg / bc_waves, &per_wave);
-    }
-    const int64_t narrow = static_cast<int64_t>(
-        roww ? narrow_roww_lds_bytes(ns, nr, roww_padded_slots(row_ptr_host, r0, nr, c4, &batches), c4)
-             : narrow_lds_bytes(ns, nr, no + 3 * nr, c4));
-    return narrow <= lds_bytes && sliced <= 160 * 1024;
+  f.roww = f.narrow() && !f.bcast() && rows_uniform_weights(c) && roww_slots_fit(c.max_col, f.c4);
+  // group consecutive rows while the form's vector kernel fits the LDS budget with them
+  // (vector_group_lds); narrow plans also keep the staged scalar tail kernel within the
+  // hardware's 160 KiB, and broadcast plans within what the form's launch stages (bc_max_loads)
+  // and a wavefront's registers hold (bc_deal)
+  auto fits = [&](int64_t ns, int64_t nr, int64_t r0) {
+    if (vector_group_lds(c, f, r0, nr, ns, Sizing::kGrouping) > lds_bytes) return false;
+    if (!f.narrow()) return true;
+    if (scalar_group_lds(c, f.c4, r0, nr, ns) > 160 * 1024) return false;
+    if (!f.bcast()) return true;
+    std::vector<std::vector<int32_t>> per_wave;
+    return ns * f.c4 <= bc_max_loads(f.c4, f.bc_waves, f.bc_wg) &&
+           bc_deal(bc_pass_records(c, r0, nr), f.bc_waves, kBcRecPerWg / f.bc_waves, &per_wave);
   };
   Groups grp;
-  rc = group_rows(rows, row_ptr_host, col_host, max_col, fits, &grp);
+  rc = group_rows(c, fits, &grp);
   if (rc) return rc;
-  if (c4 >= 64)
-    return finish_plan(rows, row_ptr_host, col_host, w_host, out_row_host, max_col, grp, c4, dense_rb, 0,
-                       plan_host, plan_capacity_words, info);
-  // Narrow tiles: a wavefront pass computes 64 / c4 consecutive plan rows in lock step, so the
-  // rows of each group are ordered by operand count (descending, stable): rows of a pass then
-  // have similar counts and few lanes idle.  Rows are independent and each names its output
-  // row, so the order is free.
-  std::vector<int32_t> perm(rows);
-  for (int g = 0; g + 1 < static_cast<int>(grp.row_ptr.size()); ++g) {
-    const int r0 = grp.row_ptr[g], r1 = grp.row_ptr[g + 1];
-    for (int r = r0; r < r1; ++r) perm[r] = r;
-    std::stable_sort(perm.begin() + r0, perm.begin() + r1, [&](int32_t a, int32_t b) {
-      return row_ptr_host[a + 1] - row_ptr_host[a] > row_ptr_host[b + 1] - row_ptr_host[b];
+  if (!f.narrow()) return finish_plan(c, grp, f, plan_host, plan_capacity_words, info);
+  OrderedCsr ordered;
+  order_rows_by_count(c, grp, &ordered);
+  return finish_plan(ordered.csr, grp, f, plan_host, plan_capacity_words, info);
+}
+
+// ---- the round's launch -------------------------------------------------------------------
+
+// The vector (float4) kernel a plan runs on an fp32 or bf16 pool: agg_round dispatches on it and
+// tal_round_kernel_name names it.
+enum class RoundForm { kStream, kWide, kNarrow, kBcast, kPersistent, kTiled };
+
+RoundForm round_vec_form(const tal_round_plan_info& in, bool bf16) {
+  if (in.stream_cs != 0) return bf16 ? RoundForm::kWide : RoundForm::kStream;
+  if (in.c4 < 64) return in.narrow_bcast ? RoundForm::kBcast : RoundForm::kNarrow;
+  return persistent_j(in.c4, static_cast<int64_t>(in.max_src) * in.c4) ? RoundForm::kPersistent : RoundForm::kTiled;
+}
+
+const char* round_form_kernel(RoundForm form) {
+  switch (form) {
+    case RoundForm::kStream: return "k_round_stream";
+    case RoundForm::kWide: return "k_round_wide";
+    case RoundForm::kNarrow:
+    case RoundForm::kBcast: return "k_round_f32_narrow";
+    case RoundForm::kPersistent: return "k_round_f32_persistent";
+    case RoundForm::kTiled: return "k_round_f32_tiled";
+  }
+  return "";
+}
+
+// What tal_agg_round_<T> has kernels for: the pools' alignment for the vector forms (0: none,
+// every column runs the tail kernels), and dense row blocks and the streamed kernels (bf16
+// has neither: it refuses dense plans and runs streamed ones in the wide-row form).
+template <typename T>
+constexpr uintptr_t kRoundVecAlign = std::is_same<T, float>::value ? 16 : kIsBf16<T> ? 8 : 0;
+template <typename T>
+constexpr bool kRoundDenseStream = !kIsBf16<T>;
+
+// The plan's vector kernel over the n4 float4 columns of an aligned pool.
+template <typename T>
+int32_t launch_round_form(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4, const PlanView& v,
+                          const tal_round_plan_info& in, bool exact, hipStream_t s) {
+  const RoundForm form = round_vec_form(in, kIsBf16<T>);
+  return with_bool(exact, [&](auto ex) -> int32_t {
+    constexpr bool EXACT = decltype(ex)::value;
+    if constexpr (kRoundDenseStream<T>) {
+      if (form == RoundForm::kStream)
+        return with_int<512, 1024>(in.stream_cs == 8 * kStreamPerWave ? 512 : 1024, [&](auto nt) {
+          return launch_round_stream_nt<decltype(nt)::value, EXACT>(pin, ld_in, pout, ld_out, n4, v, in, s);
+        });
+    } else {
+      if (form == RoundForm::kWide) return launch_round_wide<T, EXACT>(pin, ld_in, pout, ld_out, n4, v, in, s);
+    }
+    if (form == RoundForm::kNarrow || form == RoundForm::kBcast)
+      return with_int<16, 32>(in.c4, [&](auto c4) {
+        constexpr int C4 = decltype(c4)::value;
+        return form == RoundForm::kBcast ? launch_round_bcast<C4, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s)
+                                         : launch_round_narrow<C4, EXACT, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
+      });
+    return with_int<64, 128>(in.c4, [&](auto c4) {  // kPersistent / kTiled: launch_round_vec picks J
+      return with_bool(in.dense_rb > 0, [&](auto dense) {
+        constexpr bool DENSE = decltype(dense)::value && kRoundDenseStream<T>;  // bf16: agg_round refused dense plans
+        return launch_round_vec<decltype(c4)::value, EXACT, DENSE, T>(pin, ld_in, pout, ld_out, n4, v, in, s);
+      });
     });
+  });
+}
+
+// tal_agg_round_<T>: the plan's vector kernel over the whole float4 columns of aligned pools,
+// then the tail kernel over the rest (every column of an int64 or unaligned pool).
+template <typename T>
+int32_t agg_round(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
+                  const int32_t* plan_dev, const tal_round_plan_info* info, int32_t mode, void* stream) {
+  int32_t rc = validate_info(info);
+  if (rc) return rc;
+  if (!kRoundDenseStream<T> && ((info->dense_rb != 0 && info->stream_cs == 0) || (info->stream_cs != 0 && info->max_rows > kWideRows)))
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bf16 rounds take sparse or narrow plans (dense_rb 0), or "
+                                        "streamed plans of at most 16 rows per group (the wide-row form)");
+  if (!pool_in || !pool_out || !plan_dev) return fail(TAL_ERR_INVALID, std::string(fn) + ": null pointer");
+  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, std::string(fn) + ": bad n / ld");
+  if (pool_in == pool_out && info->n_groups > 1)
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": in-place round needs a single-group plan (snapshot semantics)");
+  if (n == 0) { g_err.clear(); return TAL_OK; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const PlanView v = make_view(plan_dev, *info);
+  const bool exact = mode == TAL_MODE_EXACT;
+  int64_t e_vec = 0;
+  if constexpr (kRoundVecAlign<T> != 0) {
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(pool_in) | reinterpret_cast<uintptr_t>(pool_out);
+    if (ptrs % kRoundVecAlign<T> == 0 && ld_in % 4 == 0 && ld_out % 4 == 0 && n >= 4) {
+      rc = launch_round_form<T>(pool_in, ld_in, pool_out, ld_out, n / 4, v, *info, exact, s);
+      if (rc) return rc;
+      e_vec = n / 4 * 4;
+    }
   }
-  const int64_t nnz = row_ptr_host[rows];
-  std::vector<int32_t> rp(static_cast<size_t>(rows) + 1, 0), cl(nnz), orow(rows);
-  std::vector<double> wv(nnz);
-  for (int r = 0; r < rows; ++r) {
-    const int32_t src = perm[r], k0 = row_ptr_host[src], k1 = row_ptr_host[src + 1];
-    rp[r + 1] = rp[r] + (k1 - k0);
-    std::copy(col_host + k0, col_host + k1, cl.begin() + rp[r]);
-    std::copy(w_host + k0, w_host + k1, wv.begin() + rp[r]);
-    orow[r] = out_row_host[src];
-  }
-  return finish_plan(rows, rp.data(), cl.data(), wv.data(), orow.data(), max_col, grp, c4, 0, 0,
-                     plan_host, plan_capacity_words, info, bc_waves, bc_wg);
+  if (n <= e_vec) return TAL_OK;
+  if (use_direct(pool_in, pool_out, e_vec, n))
+    return launch_round_direct<T>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
+  if constexpr (kRoundDenseStream<T>)
+    if (info->stream_cs > 0)
+      return launch_round_stream_scalar<std::is_same<T, int64_t>::value>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v,
+                                                                         *info, exact, s);
+  return launch_round_scalar<T>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
 }
 
 }  // namespace
@@ -4863,8 +5055,10 @@ int32_t tal_round_plan_build(int32_t rows, const int32_t* row_ptr_host, const in
                              const double* w_host, const int32_t* out_row_host, int32_t c4,
                              int32_t lds_bytes, int32_t dense_rb, int32_t* plan_host,
                              int64_t plan_capacity_words, tal_round_plan_info* info) {
-  return round_plan_build(rows, row_ptr_host, col_host, w_host, out_row_host, c4, lds_bytes, dense_rb,
-                          plan_host, plan_capacity_words, info, 0, 2);
+  PlanForm f{c4};
+  f.dense_rb = dense_rb;
+  return round_plan_build(Csr{rows, row_ptr_host, col_host, w_host, out_row_host}, f, lds_bytes, plan_host,
+                          plan_capacity_words, info);
 }
 
 int64_t tal_round_bcast_max_loads(int32_t c4, int32_t waves, int32_t wg_per_cu) {
@@ -4884,8 +5078,11 @@ int32_t tal_round_plan_build_bcast(int32_t rows, const int32_t* row_ptr_host, co
   if (wg_per_cu != 1 && wg_per_cu != 2)
     return fail(TAL_ERR_INVALID, "tal_round_plan_build_bcast: wg_per_cu must be 1 or 2");
   if (wg_per_cu == 2 && lds_bytes > 80 * 1024) lds_bytes = 80 * 1024;  // two groups' tiles per CU
-  return round_plan_build(rows, row_ptr_host, col_host, w_host, out_row_host, c4, lds_bytes, 0, plan_host,
-                          plan_capacity_words, info, waves, wg_per_cu);
+  PlanForm f{c4};
+  f.bc_waves = waves;
+  f.bc_wg = wg_per_cu;
+  return round_plan_build(Csr{rows, row_ptr_host, col_host, w_host, out_row_host}, f, lds_bytes, plan_host,
+                          plan_capacity_words, info);
 }
 
 int32_t tal_round_plan_build_stream(int32_t rows, const int32_t* row_ptr_host,
@@ -4894,101 +5091,49 @@ int32_t tal_round_plan_build_stream(int32_t rows, const int32_t* row_ptr_host,
                                     int32_t max_group_src, int32_t* plan_host,
                                     int64_t plan_capacity_words, tal_round_plan_info* info) {
   if (!info) return fail(TAL_ERR_INVALID, "tal_round_plan_build_stream: bad arguments");
-  int32_t max_col = 0;
-  int32_t rc = check_csr("tal_round_plan_build_stream", rows, row_ptr_host, col_host, w_host, out_row_host,
-                         &max_col);
+  Csr c{rows, row_ptr_host, col_host, w_host, out_row_host};
+  int32_t rc = check_csr("tal_round_plan_build_stream", &c);
   if (rc) return rc;
   if (max_group_rows < 1 || max_group_rows > kStreamMaxRows || max_group_src < 0)
     return fail(TAL_ERR_INVALID, "tal_round_plan_build_stream: max_group_rows must be 1.." +
                                      std::to_string(kStreamMaxRows) + ", max_group_src >= 0");
-  if (!reference_order(rows, row_ptr_host, col_host))
+  if (!reference_order(c))
     return fail(TAL_ERR_INVALID, "tal_round_plan_build_stream: rows must list operands in reference order");
-  auto fits = [&](int64_t ns, int64_t nr, int64_t, int64_t) {
+  auto fits = [&](int64_t ns, int64_t nr, int64_t) {
     return nr <= max_group_rows && (max_group_src == 0 || ns <= max_group_src || nr == 1);
   };
   Groups grp;
-  rc = group_rows(rows, row_ptr_host, col_host, max_col, fits, &grp);
+  rc = group_rows(c, fits, &grp);
   if (rc) return rc;
   int32_t max_rows = 0;
-  for (size_t g = 0; g + 1 < grp.row_ptr.size(); ++g) max_rows = std::max(max_rows, grp.row_ptr[g + 1] - grp.row_ptr[g]);
-  const int32_t cs = (max_rows <= 8 * 8 ? 8 : 16) * kStreamPerWave;  // one row block per wavefront
-  return finish_plan(rows, row_ptr_host, col_host, w_host, out_row_host, max_col, grp, 64, kDenseRb, cs,
-                     plan_host, plan_capacity_words, info);
+  for (int g = 0; g < grp.count(); ++g) max_rows = std::max(max_rows, grp.rows(g));
+  PlanForm f{64};
+  f.dense_rb = kDenseRb;
+  f.stream_cs = (max_rows <= 8 * 8 ? 8 : 16) * kStreamPerWave;  // one row block per wavefront
+  return finish_plan(c, grp, f, plan_host, plan_capacity_words, info);
 }
 
 int32_t tal_agg_round_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                           int64_t n, const int32_t* plan_dev, const tal_round_plan_info* info,
                           int32_t mode, void* stream) {
-  int32_t rc = validate_info(info);
-  if (rc) return rc;
-  if (!pool_in || !pool_out || !plan_dev) return fail(TAL_ERR_INVALID, "tal_agg_round_f32: null pointer");
-  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, "tal_agg_round_f32: bad n / ld");
-  if (pool_in == pool_out && info->n_groups > 1)
-    return fail(TAL_ERR_INVALID,
-                "tal_agg_round_f32: in-place round needs a single-group plan (snapshot semantics)");
-  if (n == 0) { g_err.clear(); return TAL_OK; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const PlanView v = make_view(plan_dev, *info);
-  const bool exact = mode == TAL_MODE_EXACT;
-  const bool vec = aligned16(pool_in) && aligned16(pool_out) && ld_in % 4 == 0 && ld_out % 4 == 0;
-  int64_t e_vec = 0;
-  if (vec) {
-    const int64_t n4 = n / 4;
-    e_vec = n4 * 4;
-    if (n4 > 0 && info->stream_cs > 0) {
-      rc = launch_round_stream(pool_in, ld_in, pool_out, ld_out, n4, v, *info, exact, s);
-      if (rc) return rc;
-    } else if (n4 > 0 && info->c4 < 64) {
-      if (info->c4 == 16)
-        rc = exact ? launch_round_narrow<16, true>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s)
-                   : launch_round_narrow<16, false>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s);
-      else
-        rc = exact ? launch_round_narrow<32, true>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s)
-                   : launch_round_narrow<32, false>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s);
-      if (rc) return rc;
-    } else if (n4 > 0) {
-      const bool dense = info->dense_rb > 0;
-      switch (info->c4 * 4 + (exact ? 2 : 0) + (dense ? 1 : 0)) {
-        case 515: rc = launch_round_vec<128, true, true>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 514: rc = launch_round_vec<128, true, false>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 513: rc = launch_round_vec<128, false, true>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 512: rc = launch_round_vec<128, false, false>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 259: rc = launch_round_vec<64, true, true>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 258: rc = launch_round_vec<64, true, false>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 257: rc = launch_round_vec<64, false, true>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        default: rc = launch_round_vec<64, false, false>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-      }
-      if (rc) return rc;
-    }
-  }
-  if (n <= e_vec) return TAL_OK;
-  if (use_direct(pool_in, pool_out, e_vec, n))
-    return launch_round_direct<float>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
-  if (info->stream_cs > 0)
-    return launch_round_stream_scalar<false>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
-  return launch_round_scalar<float>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
+  return agg_round<float>("tal_agg_round_f32", pool_in, ld_in, pool_out, ld_out, n, plan_dev, info, mode, stream);
 }
 
 int32_t tal_agg_round_i64(const int64_t* pool_in, int64_t ld_in, int64_t* pool_out, int64_t ld_out,
                           int64_t n, const int32_t* plan_dev, const tal_round_plan_info* info,
                           void* stream) {
-  int32_t rc = validate_info(info);
-  if (rc) return rc;
-  if (!pool_in || !pool_out || !plan_dev) return fail(TAL_ERR_INVALID, "tal_agg_round_i64: null pointer");
-  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, "tal_agg_round_i64: bad n / ld");
-  if (pool_in == pool_out && info->n_groups > 1)
-    return fail(TAL_ERR_INVALID,
-                "tal_agg_round_i64: in-place round needs a single-group plan (snapshot semantics)");
-  if (n == 0) { g_err.clear(); return TAL_OK; }
-  const PlanView v = make_view(plan_dev, *info);
-  if (use_direct(pool_in, pool_out, 0, n))
-    return launch_round_direct<int64_t>(pool_in, ld_in, pool_out, ld_out, 0, n, v, *info, true,
-                                     static_cast<hipStream_t>(stream));
-  if (info->stream_cs > 0)
-    return launch_round_stream_scalar<true>(pool_in, ld_in, pool_out, ld_out, 0, n, v, *info, true,
-                                            static_cast<hipStream_t>(stream));
-  return launch_round_scalar<int64_t>(pool_in, ld_in, pool_out, ld_out, 0, n, v, *info, true,
-                                   static_cast<hipStream_t>(stream));
+  return agg_round<int64_t>("tal_agg_round_i64", pool_in, ld_in, pool_out, ld_out, n, plan_dev, info,
+                            TAL_MODE_EXACT, stream);
+}
+
+int32_t tal_agg_round_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                           int64_t n, const int32_t* plan_dev, const tal_round_plan_info* info,
+                           int32_t mode, void* stream) {
+  return agg_round<uint16_t>("tal_agg_round_bf16", pool_in, ld_in, pool_out, ld_out, n, plan_dev, info, mode, stream);
+}
+
+const char* tal_round_kernel_name(const tal_round_plan_info* info, int32_t bf16) {
+  return info ? round_form_kernel(round_vec_form(*info, bf16 != 0)) : "";
 }
 
 int32_t tal_agg_round_clique_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
@@ -5078,52 +5223,6 @@ int32_t tal_agg_bf16(const uint16_t* const* x_host, const double* w_host, int32_
     else k_agg_b16_scalar<false><<<grid_for(n - 4 * n4), kBlock, 0, s>>>(t, m, out, 4 * n4, n);
   }
   return check_launch("tal_agg_bf16");
-}
-
-int32_t tal_agg_round_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
-                           int64_t n, const int32_t* plan_dev, const tal_round_plan_info* info,
-                           int32_t mode, void* stream) {
-  int32_t rc = validate_info(info);
-  if (rc) return rc;
-  const bool wide = info->stream_cs != 0;  // a streamed plan: the wide-row form (<= 16 rows per group)
-  if ((info->dense_rb != 0 && !wide) || (wide && info->max_rows > kWideRows))
-    return fail(TAL_ERR_INVALID, "tal_agg_round_bf16: bf16 rounds take sparse or narrow plans (dense_rb 0), or "
-                                 "streamed plans of at most 16 rows per group (the wide-row form)");
-  if (!pool_in || !pool_out || !plan_dev) return fail(TAL_ERR_INVALID, "tal_agg_round_bf16: null pointer");
-  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, "tal_agg_round_bf16: bad n / ld");
-  if (pool_in == pool_out && info->n_groups > 1)
-    return fail(TAL_ERR_INVALID,
-                "tal_agg_round_bf16: in-place round needs a single-group plan (snapshot semantics)");
-  if (n == 0) { g_err.clear(); return TAL_OK; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const PlanView v = make_view(plan_dev, *info);
-  const bool exact = mode == TAL_MODE_EXACT;
-  const bool vec = aligned8(pool_in) && aligned8(pool_out) && ld_in % 4 == 0 && ld_out % 4 == 0;
-  int64_t e_vec = 0;
-  if (vec) {
-    const int64_t n4 = n / 4;
-    e_vec = n4 * 4;
-    if (n4 > 0 && wide) {
-      rc = launch_round_wide<uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, exact, s);
-      if (rc) return rc;
-    } else if (n4 > 0) {
-      switch (info->c4 * 2 + (exact ? 1 : 0)) {
-        case 33: rc = launch_round_narrow<16, true, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 32: rc = launch_round_narrow<16, false, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 65: rc = launch_round_narrow<32, true, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 64: rc = launch_round_narrow<32, false, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 129: rc = launch_round_vec<64, true, false, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 128: rc = launch_round_vec<64, false, false, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        case 257: rc = launch_round_vec<128, true, false, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-        default: rc = launch_round_vec<128, false, false, uint16_t>(pool_in, ld_in, pool_out, ld_out, n4, v, *info, s); break;
-      }
-      if (rc) return rc;
-    }
-  }
-  if (n <= e_vec) return TAL_OK;
-  if (use_direct(pool_in, pool_out, e_vec, n))
-    return launch_round_direct<uint16_t>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
-  return launch_round_scalar<uint16_t>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
 }
 
 static int cos_kind(int64_t I, int64_t B) { return I == 1 ? kCosElem : (B == 1 ? kCosRow : kCosCol); }

@@ -922,8 +922,8 @@ WIDE_ROWS = 16  # rows per group of the bf16 wide-row form (k_round_wide, kWideR
 
 def round_kernel_name(plan, bf16: bool = False) -> str:
     """Which K3 kernel tal_agg_round_f32 (bf16: tal_agg_round_bf16) launches for this plan or plan
-    info (mirrors launch_round_vec); clique plans name the K3c kernel (their rest rows run a
-    second one)."""
+    info, asked from the library (tal_round_kernel_name: the function its launch dispatches on);
+    clique plans name the K3c kernel (their rest rows run a second one)."""
     if isinstance(plan, CliquePlan):
         return "k_round_clique"
     if isinstance(plan, RegPlan):
@@ -931,14 +931,7 @@ def round_kernel_name(plan, bf16: bool = False) -> str:
     if isinstance(plan, RowCallPlan):
         return "k_agg (one call per row)"
     info = plan.info if isinstance(plan, RoundPlan) else plan
-    if info.stream_cs:
-        return "k_round_wide" if bf16 else "k_round_stream"
-    if info.c4 < 64:
-        return "k_round_f32_narrow"
-    threads = 1024 if info.c4 == 64 else 512
-    j_max = 20 if threads <= 512 else 8
-    loads = info.max_src * info.c4
-    return "k_round_f32_persistent" if loads <= j_max * threads else "k_round_f32_tiled"
+    return _lib.load().tal_round_kernel_name(ctypes.byref(info), int(bf16)).decode()
 
 
 def _blocks_per_cu(info: RoundPlanInfo) -> int:
