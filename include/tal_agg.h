@@ -453,6 +453,36 @@ int32_t tal_prox_grad(const float* w, const float* const* wt_host, int32_t k,
                       const int64_t* plan_dev, int32_t n_chunks, int32_t n_seg,
                       const float* norms, const float* scale_dev, float* gw,
                       float* const* gwt_host, void* stream);
+/* K4 on bf16 models (ABI 29): w, wt, gw and gwt are bf16 rows (uint16_t bit patterns; a device
+ * ModelPool's b16 segment), offsets and lengths in elements; plans, tal_prox_scratch_bytes and
+ * the error codes are the fp32 entry points'.  This is the project's definition (the reference
+ * has no pinned bf16 arithmetic for the term): every value x is the bf16 parameter widened
+ * exactly to fp32 (bits u << 16).
+ * tal_prox_norms_bf16: norms_out[t*n_seg + p] = ||w_p - wt_p||_2 in fp32: squares accumulated
+ * per lane in fp32 with fmaf, lanes, wavefronts and chunks combined in double in a fixed order,
+ * one sqrt, one cast.  Deterministic; not bit for bit tal_prox_norms on the widened rows (the
+ * packed loads give a lane other elements).
+ * tal_prox_grad_bf16: per element exactly tal_prox_grad's fp32 operations in its order
+ * (c_t = norm_t > 0 ? s / norm_t : 0; d_t = (w - wt_t) * c_t; g = ((0 + d_0) + d_1) + ...);
+ * g and -d_t are rounded to bf16 once, to nearest even, at the store.  For the same `norms` the
+ * result is the nearest-even bf16 rounding of what tal_prox_grad writes for the widened rows, for
+ * any k.  With k > 64 (more than one launch) the running sum stays fp32 between the launches in
+ * acc_scratch, acc_elems fp32 elements indexed like the rows, which must cover every plan chunk's
+ * [begin, begin + length); it may be NULL when k <= 64, and k > 64 with NULL or with fewer
+ * elements than the plan has chunks is TAL_ERR_INVALID (a chunk past acc_elems is never
+ * touched).  Only the parameter segments of gw / gwt are written.
+ * Rows that are all 8-byte aligned (pool rows are) are read and written 8 bytes per lane, the up
+ * to 3 elements before and after a chunk's whole 8-byte groups one by one; other rows go element
+ * by element (the same gradient bit for bit; the norms by the same definition, summed in that
+ * path's own fixed order). */
+int32_t tal_prox_norms_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k,
+                            const int64_t* plan_dev, int32_t n_chunks, int32_t n_seg,
+                            void* scratch, float* norms_out, void* stream);
+int32_t tal_prox_grad_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k,
+                           const int64_t* plan_dev, int32_t n_chunks, int32_t n_seg,
+                           const float* norms, const float* scale_dev, uint16_t* gw,
+                           uint16_t* const* gwt_host, float* acc_scratch, int64_t acc_elems,
+                           void* stream);
 
 /* ---- Host reduction: processes that see no GPU ------------------------------------------
  * BASELINE config 1 runs the reference's driver with CPU models and no GPU

@@ -1,0 +1,369 @@
+"""K4 on bf16 models (tal_prox_norms_bf16, tal_prox_grad_bf16) on the GPU.
+
+The FedProx term of bf16 models is this project's definition (include/tal_agg.h "K4 on bf16
+models"; the reference, tasks.py:277-286, has no pinned bf16 arithmetic for it): the norms are
+fp32 norms of the parameters widened exactly to fp32, the gradient is tal_prox_grad's fp32
+arithmetic on the widened rows rounded to bf16 once, at the store.
+
+Kernel level, through ctypes on flat bf16 rows with a plan of explicit (offset, length) segments
+that reach every position of a chunk's first element in its 8-byte group, every head and tail
+length and more than one chunk: the norms against float64 (relative 1e-5, the (f)3 bar; one
+lane's fp32 chain is at most 32 fmaf of non-negative terms plus one edge element, under 2e-6)
+and bit-identical on a second call; the gradient bit for bit the fp32 entry point's on the widened
+rows, converted to bf16 by torch, for 1, 8, 9 (past one 8-neighbor tile), 64 and 65 (past one
+launch: the fp32 running sum) neighbors; the same with rows that start 2 bytes into their
+buffers (the element-by-element path).
+Interface level: prox_term on bf16 pool-bound models against the torch loop on fp32 leaf copies,
+selective neighbor gradients, one local_train epoch, and the fp32 path's kind.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+from torch.utils.data import Subset, TensorDataset
+
+from _models import TinyNet
+from topology_aware_learning_amd import _lib
+from topology_aware_learning_amd.aggregate import layout_of_module
+from topology_aware_learning_amd.arena import ModelPool
+from topology_aware_learning_amd.prox import _plan_for, prox_term
+
+pytestmark = pytest.mark.gpu
+
+CHUNK = 8192
+_LENS = [1, 3, 4, 5, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 7]
+_OFF_MOD = [1, 2, 3, 0, 3, 1, 2, 0]  # offset % 4 of each segment: every position of an 8-byte group
+
+
+def _segments():
+    segs, off = [], 0
+    for n, m in zip(_LENS, _OFF_MOD):
+        off += 2  # a gap, then up to the wanted position
+        while off % 4 != m:
+            off += 1
+        segs.append((off, n))
+        off += n
+    return segs
+
+
+SEGS = _segments()
+N = SEGS[-1][0] + SEGS[-1][1] + 5
+KS = [1, 8, 9, 64, 65]
+SENTINEL = 7.0
+SCALE = 0.37
+
+
+def test_segment_list_reaches_every_edge():
+    assert {o % 4 for o, _ in SEGS} == {0, 1, 2, 3}
+    assert all(b[0] >= a[0] + a[1] + 2 for a, b in zip(SEGS, SEGS[1:]))  # gaps
+    assert [n for _, n in SEGS] == _LENS
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16)
+
+
+def _mask(device):
+    m = torch.zeros(N, dtype=torch.bool, device=device)
+    for o, n in SEGS:
+        m[o: o + n] = True
+    return m
+
+
+class _Plan:
+    def __init__(self, device):
+        L = _lib.load()
+        seg = np.array([x for s in SEGS for x in s], dtype=np.int64)
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        words = L.tal_prox_plan_words(seg.ctypes.data_as(P64), len(SEGS))
+        blob = np.zeros(words, dtype=np.int64)
+        nc = ctypes.c_int32()
+        _lib.check(L.tal_prox_plan_build(seg.ctypes.data_as(P64), len(SEGS), blob.ctypes.data_as(P64), words,
+                                         ctypes.byref(nc)))
+        self.n_seg, self.n_chunks = len(SEGS), int(nc.value)
+        assert self.n_chunks == sum((n + CHUNK - 1) // CHUNK for n in _LENS)
+        self.dev = torch.from_numpy(blob).to(device)
+
+
+_cache = {}
+
+
+def _plan(device):
+    if "plan" not in _cache:
+        _cache["plan"] = _Plan(device)
+    return _cache["plan"]
+
+
+def _rows(device, k, mis, wide):
+    """k + 1 bf16 rows of N elements, each `mis` elements into its own 8-byte aligned buffer row;
+    row 0 is the client, neighbor 1 (where there is one) equals it."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(1000 * k + 10 * mis + int(wide))
+    x = torch.randn(k + 1, N, generator=g)
+    if wide:  # magnitudes, and so differences, from 2^-20 to 2^20
+        x = x * torch.exp2(torch.randint(-20, 21, (k + 1, N), generator=g).float())
+    buf = torch.zeros(k + 1, N + 8 - N % 4, dtype=torch.bfloat16, device=device)
+    assert buf.data_ptr() % 8 == 0 and buf.stride(0) % 4 == 0
+    rows = buf[:, mis: mis + N]
+    rows.copy_(x.to(torch.bfloat16))
+    if k >= 2:
+        rows[2].copy_(rows[0])
+    assert rows[0].data_ptr() % 8 == 2 * mis
+    return rows
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _norms_bf16(rows, plan):
+    L = _lib.load()
+    k = rows.shape[0] - 1
+    scratch = torch.empty(int(L.tal_prox_scratch_bytes(plan.n_chunks, k)), dtype=torch.uint8, device=rows.device)
+    out = torch.full((k, plan.n_seg), float("nan"), dtype=torch.float32, device=rows.device)
+    wt = _lib.ptr_array([rows[1 + t].data_ptr() for t in range(k)])
+    _lib.check(L.tal_prox_norms_bf16(_ptr(rows[0]), wt, k, _ptr(plan.dev), plan.n_chunks, plan.n_seg, _ptr(scratch),
+                                     _ptr(out), _stream()))
+    return out
+
+
+def _case(device, k, mis, wide=False):
+    key = (k, mis, wide)
+    if key not in _cache:
+        rows = _rows(device, k, mis, wide)
+        _cache[key] = (rows, _norms_bf16(rows, _plan(device)))
+    return _cache[key]
+
+
+def _check_norms(device, k, mis, wide=False):
+    rows, norms = _case(device, k, mis, wide)
+    plan = _plan(device)
+    again = _norms_bf16(rows, plan)
+    assert torch.equal(norms.view(torch.int32), again.view(torch.int32))  # deterministic
+    d = rows[0:1].double() - rows[1:].double()
+    want = torch.stack([d[:, o: o + n].pow(2).sum(1).sqrt() for o, n in SEGS], dim=1)
+    got = norms.double()
+    err = ((got - want).abs() / want.clamp_min(1e-300)).max().item()
+    print(f"k={k} mis={mis} wide={wide}: largest relative norm error {err:.3e}")
+    assert torch.isfinite(got).all()
+    assert ((got - want).abs() <= 1e-5 * want).all()
+    if k >= 2:
+        assert (norms[1] == 0).all()  # the identical neighbor: exactly 0
+
+
+def _want_t(k):
+    """Neighbors whose gradient is asked for: the identical one, every third one and the last."""
+    return [t == 1 or t % 3 == 0 or t == k - 1 for t in range(k)]
+
+
+def _check_grad(device, k, mis, wide=False):
+    L = _lib.load()
+    rows, norms = _case(device, k, mis, wide)
+    plan = _plan(device)
+    scale = torch.tensor([SCALE], dtype=torch.float32, device=device)
+    want_t = _want_t(k)
+    assert (not all(want_t) or k == 1) and any(want_t)
+    # the fp32 entry point on the widened rows, with the bf16 call's own norms
+    wide_rows = rows.float().contiguous()
+    gw32 = torch.full((N,), SENTINEL, dtype=torch.float32, device=device)
+    gwt32 = [torch.full((N,), SENTINEL, dtype=torch.float32, device=device) if w else None for w in want_t]
+    wt32 = _lib.ptr_array([wide_rows[1 + t].data_ptr() for t in range(k)])
+    gwt32_p = _lib.ptr_array([x.data_ptr() if x is not None else 0 for x in gwt32])
+    _lib.check(L.tal_prox_grad(_ptr(wide_rows[0]), wt32, k, _ptr(plan.dev), plan.n_chunks, plan.n_seg, _ptr(norms),
+                               _ptr(scale), _ptr(gw32), gwt32_p, _stream()))
+    # the bf16 entry point; gw `mis` elements into its buffer like the rows
+    gbuf = torch.full((N + 8,), SENTINEL, dtype=torch.bfloat16, device=device)
+    gw = gbuf[mis: mis + N]
+    gwt = [torch.full((N,), SENTINEL, dtype=torch.bfloat16, device=device) if w else None for w in want_t]
+    acc = torch.full((N,), float("nan"), dtype=torch.float32, device=device) if k > 64 else None
+    wt = _lib.ptr_array([rows[1 + t].data_ptr() for t in range(k)])
+    gwt_p = _lib.ptr_array([x.data_ptr() if x is not None else 0 for x in gwt])
+    _lib.check(L.tal_prox_grad_bf16(_ptr(rows[0]), wt, k, _ptr(plan.dev), plan.n_chunks, plan.n_seg, _ptr(norms),
+                                    _ptr(scale), _ptr(gw), gwt_p, ctypes.c_void_p(acc.data_ptr() if k > 64 else 0),
+                                    N if k > 64 else 0, _stream()))
+    torch.cuda.synchronize()
+    inside = _mask(device)
+    sentinel = _bits(torch.tensor([SENTINEL], dtype=torch.bfloat16, device=device))[0]
+
+    def same(got, ref32, what):
+        got_b, want_b = _bits(got), _bits(ref32.to(torch.bfloat16))
+        assert not torch.isnan(got.float()[inside]).any(), what
+        bad = (got_b != want_b) & inside
+        assert not bad.any(), (what, int(bad.sum()), int(bad.nonzero()[0]))
+        assert (got_b[~inside] == sentinel).all(), what + ": written outside the segments"
+
+    same(gw, gw32, "gw")
+    assert (_bits(gbuf[:mis]) == sentinel).all() and (_bits(gbuf[mis + N:]) == sentinel).all()
+    for t in range(k):
+        if gwt[t] is not None:
+            same(gwt[t], gwt32[t], f"gwt[{t}]")
+    if k >= 2:  # the identical neighbor contributes exactly nothing
+        assert (gwt[1].float()[inside] == 0).all()
+    assert gw.float()[inside].abs().max() > 0 or k == 2
+
+
+@pytest.mark.parametrize("k", KS)
+def test_norms_vs_float64(cuda, k):
+    _check_norms(cuda, k, 0)
+
+
+@pytest.mark.parametrize("k", KS)
+def test_grad_is_the_fp32_twins_rounded_once(cuda, k):
+    _check_grad(cuda, k, 0)
+
+
+def test_wide_range_values(cuda):
+    _check_norms(cuda, 8, 0, wide=True)
+    _check_grad(cuda, 8, 0, wide=True)
+
+
+@pytest.mark.parametrize("k", KS)
+def test_unaligned_rows(cuda, k):
+    """Rows and gw one element (2 bytes) into their buffers: the element-by-element path."""
+    _check_norms(cuda, k, 1)
+    _check_grad(cuda, k, 1)
+
+
+# ---- interface level ------------------------------------------------------------------------
+DUMMY = TensorDataset(torch.zeros(4, 1), torch.zeros(4, dtype=torch.long))
+
+
+def _past_one_chunk():
+    """A parameter past one chunk (130 x 127 = 16510 elements) and odd offsets after it."""
+    return torch.nn.Sequential(torch.nn.Linear(130, 127), torch.nn.Linear(127, 3))
+
+
+def _bound(cuda, make, n, seed, dtype=torch.bfloat16, identical=True):
+    """n models of one architecture bound to rows of a device pool, close to each other as
+    trained neighbors are; with `identical`, model 1's parameters equal model 0's."""
+    models = []
+    for i in range(n):
+        torch.manual_seed(seed + i)
+        models.append(make().to(dtype).to(cuda))
+    pool = ModelPool(layout_of_module(models[0]), n, cuda)
+    for i, m in enumerate(models):
+        pool.bind(m, n - 1 - i)  # rows in another order than the models
+    with torch.no_grad():
+        for m in models:
+            for p in m.parameters():
+                p.add_(torch.randn_like(p) * 0.1)
+        if identical:
+            ref = dict(models[0].named_parameters())
+            for name, p in models[1].named_parameters():
+                p.copy_(ref[name])
+    return models, pool
+
+
+def _torch_loop(models):
+    """The reference's loop on fp32 leaf copies: value and gradients, model by model."""
+    leaves = [[p.detach().float().requires_grad_() for p in m.parameters()] for m in models]
+    ref = 0.0
+    for nb in leaves[1:]:
+        for w, wt in zip(leaves[0], nb):
+            ref = ref + (w - wt).norm(2)
+    ref.backward()
+    return float(ref.detach()), [[p.grad for p in ps] for ps in leaves]
+
+
+@pytest.mark.parametrize("make", [TinyNet, _past_one_chunk], ids=["tinynet", "past_one_chunk"])
+@pytest.mark.parametrize("k,identical", [(1, False), (1, True), (3, True), (70, True)])
+def test_prox_term_on_bf16_pool_models(cuda, make, k, identical):
+    models, pool = _bound(cuda, make, k + 1, seed=50 + k, identical=identical)
+    names = [n for n, _ in models[0].named_parameters()]
+    assert _plan_for(pool.layout, names, pool.device).kind == "b16"
+    fused = prox_term(models[0], models[1:])
+    assert fused is not None and fused.dtype == torch.float32
+    fused.backward()
+    ref_v, ref_g = _torch_loop(models)
+    v = float(fused.detach())
+    print(f"k={k}: value {v!r} reference {ref_v!r}")
+    assert abs(v - ref_v) <= 1e-5 * abs(ref_v) + 1e-6
+    worst = 0.0
+    for m, gs in zip(models, ref_g):
+        for p, r in zip(m.parameters(), gs):
+            assert p.grad is not None and p.grad.dtype == torch.bfloat16 and p.grad.shape == p.shape
+            err = (p.grad.float() - r).abs()
+            bound = 2.0 ** -8 * r.abs() + 1e-4 * r.abs() + 1e-6
+            worst = max(worst, float((err / bound).max()))
+            assert (err <= bound).all()
+    print(f"k={k}: largest gradient error over its bound {worst:.3f}")
+    if identical:
+        assert all((p.grad == 0).all() for p in models[1].parameters())
+
+
+def test_selective_neighbor_gradients(cuda):
+    models, pool = _bound(cuda, TinyNet, 4, seed=7)
+    prox_term(models[0], models[1:]).backward()
+    full = [p.grad.clone() for p in models[0].parameters()]
+    full_3 = [p.grad.clone() for p in models[3].parameters()]
+    for m in models:
+        m.zero_grad(set_to_none=True)
+    for p in models[2].parameters():
+        p.requires_grad_(False)
+    prox_term(models[0], models[1:]).backward()
+    assert all(p.grad is None for p in models[2].parameters())
+    for p, g in zip(models[0].parameters(), full):
+        assert torch.equal(_bits(p.grad), _bits(g))
+    for p, g in zip(models[3].parameters(), full_3):
+        assert torch.equal(_bits(p.grad), _bits(g))
+
+
+def _classifier():
+    return torch.nn.Sequential(torch.nn.Linear(6, 5), torch.nn.ReLU(), torch.nn.Linear(5, 3))
+
+
+def test_local_train_epoch_with_prox(cuda):
+    """src.tasks.local_train's _train on bf16 pool-bound clients, prox_coeff 0.1, two neighbors,
+    one epoch of a 4-sample dataset: runs to the end on the fused term, trains the client's pool
+    row and leaves the neighbors' rows as they were."""
+    from src import tasks
+    from src.decentralized_client import DecentralClient
+
+    models, pool = _bound(cuda, _classifier, 3, seed=21, identical=False)
+    g = torch.Generator().manual_seed(3)
+    data = TensorDataset(torch.randn(4, 6, generator=g).to(torch.bfloat16), torch.tensor([0, 1, 2, 1]))
+    clients = [DecentralClient(idx=i, prox_coeff=0.1, model=m, train_data=Subset(data, [0, 1, 2, 3]), test_data=None,
+                               valid_data=None, global_test_data=data, global_backdoor_test_data=None, neighbors=[],
+                               neighbor_probs=[]) for i, m in enumerate(models)]
+    calls = []
+    real = tasks.prox_term
+
+    def spy(model, neighbors):
+        out = real(model, neighbors)
+        calls.append(out)
+        return out
+
+    before = _bits(pool.b16).clone()
+    tasks.prox_term = spy
+    try:
+        results, client = tasks._train((["r"], clients[0]), 0, 1, 4, 0.1, 0.9, 0.1, 0, False, None, "sgd", 0.0, 0.9,
+                                       0.98, [(["r"], c) for c in clients[1:]], True)
+    finally:
+        tasks.prox_term = real
+    assert client is clients[0] and len(results) == 1 and np.isfinite(results[0]["train_loss"])
+    assert len(calls) == 1 and calls[0] is not None  # the fused term, not the torch loop
+    after = _bits(pool.b16)
+    rows = [pool.row_of(m) for m in models]
+    assert not torch.equal(after[rows[0]], before[rows[0]])
+    assert torch.equal(after[rows[1]], before[rows[1]]) and torch.equal(after[rows[2]], before[rows[2]])
+    assert all(torch.isfinite(p.float()).all() for p in models[0].parameters())
+
+
+def test_fp32_models_keep_the_fp32_entry_points(cuda):
+    models, pool = _bound(cuda, TinyNet, 3, seed=11, dtype=torch.float32)
+    names = [n for n, _ in models[0].named_parameters()]
+    assert _plan_for(pool.layout, names, pool.device).kind == "f32"
+    fused = prox_term(models[0], models[1:])
+    fused.backward()
+    ref_v, ref_g = _torch_loop(models)
+    assert abs(float(fused.detach()) - ref_v) <= 1e-5 * abs(ref_v) + 1e-6
+    for m, gs in zip(models, ref_g):
+        for p, r in zip(m.parameters(), gs):
+            assert p.grad.dtype == torch.float32 and torch.allclose(p.grad, r, rtol=1e-4, atol=1e-6)

@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 EXPORTED = (
     "tal_last_error",
@@ -63,6 +63,8 @@ EXPORTED = (
     "tal_prox_scratch_bytes",
     "tal_prox_norms",
     "tal_prox_grad",
+    "tal_prox_norms_bf16",
+    "tal_prox_grad_bf16",
     "tal_comm_unique_id",
     "tal_comm_init",
     "tal_comm_destroy",
@@ -207,6 +209,8 @@ _SIGS = {
     "tal_prox_scratch_bytes": (_I64, [_I32, _I32]),
     "tal_prox_norms": (_I32, [_P, _PP, _I32, _P, _I32, _I32, _P, _P, _P]),
     "tal_prox_grad": (_I32, [_P, _PP, _I32, _P, _I32, _I32, _P, _P, _P, _PP, _P]),
+    "tal_prox_norms_bf16": (_I32, [_P, _PP, _I32, _P, _I32, _I32, _P, _P, _P]),
+    "tal_prox_grad_bf16": (_I32, [_P, _PP, _I32, _P, _I32, _I32, _P, _P, _P, _PP, _P, _I64, _P]),
     "tal_comm_unique_id": (_I32, [_P]),
     "tal_comm_init": (_I32, [_PP, _I32, _I32, _P, _I32]),
     "tal_comm_destroy": (_I32, [_P]),

@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 28;
+constexpr int kAbiVersion = 29;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -4170,6 +4170,162 @@ __global__ __launch_bounds__(kBlock) void k_prox_grad(const float* __restrict__ 
   }
 }
 
+// K4 on bf16 rows (ABI 29).  The values are the bf16 parameters widened exactly to fp32; the
+// arithmetic is k_prox_sumsq's / k_prox_grad's.  A chunk [beg, beg + len) of a row whose base is
+// 8-B aligned is cut into a head of up to 3 elements, up to the first element at a multiple of 4,
+// a body of whole 8-B groups (one u32x2 per lane per load and per store) and a tail of up to 3
+// elements; head and tail go element by element, so no wide access is ever misaligned.  Rows
+// that are not 8-B aligned (`packed` = 0, chosen on the host) go element by element throughout.
+struct ProxPtrsB16 {
+  const uint16_t* wt[kProxMaxNb];
+  uint16_t* gwt[kProxMaxNb];
+};
+
+struct ProxCut {
+  int64_t head, groups, edge;  // edge = head + tail elements
+  // edge element i of the chunk -> its element index in the chunk
+  __device__ __forceinline__ int64_t edge_elem(int64_t i) const { return i < head ? i : i + 4 * groups; }
+};
+
+__device__ __forceinline__ ProxCut prox_cut(int64_t beg, int64_t len, int packed) {
+  ProxCut c;
+  c.head = packed ? min(len, (4 - (beg & 3)) & 3) : len;
+  c.groups = (len - c.head) >> 2;
+  c.edge = len - 4 * c.groups;
+  return c;
+}
+
+// one 8-B group of a neighbor row that is read once
+__device__ __forceinline__ float4 prox_ld4_once(const uint16_t* row, int64_t e) {
+  return Io<uint16_t>::f4(__builtin_nontemporal_load(reinterpret_cast<const u32x2*>(row + e)));
+}
+
+__device__ __forceinline__ float prox_sq4(float4 a, float4 b, float acc) {
+  float d = a.x - b.x;
+  acc = fmaf(d, d, acc);
+  d = a.y - b.y;
+  acc = fmaf(d, d, acc);
+  d = a.z - b.z;
+  acc = fmaf(d, d, acc);
+  d = a.w - b.w;
+  return fmaf(d, d, acc);
+}
+
+__global__ __launch_bounds__(kBlock) void k_prox_sumsq_bf16(const uint16_t* __restrict__ w, ProxPtrsB16 pp, int k,
+                                                            const int64_t* __restrict__ plan, int n_seg,
+                                                            int n_chunks, double* __restrict__ partial,
+                                                            int packed) {
+  __shared__ double s_red[kBlock / 64];
+  const int c = blockIdx.x;
+  const int64_t* ch = plan + (n_seg + 1) + 3 * static_cast<int64_t>(c);
+  const int64_t beg = ch[1], len = ch[2];
+  const ProxCut cut = prox_cut(beg, len, packed);
+  const int64_t body = beg + cut.head;  // a multiple of 4 where there are groups
+  for (int t0 = 0; t0 < k; t0 += kProxTile) {
+    const int nt = min(kProxTile, k - t0);
+    float acc[kProxTile];
+#pragma unroll
+    for (int j = 0; j < kProxTile; ++j) acc[j] = 0.f;
+    for (int64_t g = threadIdx.x; g < cut.groups; g += kBlock) {
+      const int64_t e = body + 4 * g;
+      const float4 wv = Io<uint16_t>::f4(*reinterpret_cast<const u32x2*>(w + e));
+      if (nt == kProxTile) {
+        float4 v[kProxTile];
+#pragma unroll
+        for (int j = 0; j < kProxTile; ++j) v[j] = prox_ld4_once(pp.wt[t0 + j], e);
+#pragma unroll
+        for (int j = 0; j < kProxTile; ++j) acc[j] = prox_sq4(wv, v[j], acc[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < kProxTile; ++j)
+          if (j < nt) acc[j] = prox_sq4(wv, prox_ld4_once(pp.wt[t0 + j], e), acc[j]);
+      }
+    }
+    for (int64_t i = threadIdx.x; i < cut.edge; i += kBlock) {
+      const int64_t e = beg + cut.edge_elem(i);
+      const float wv = Io<uint16_t>::ld1(w, e);
+#pragma unroll
+      for (int j = 0; j < kProxTile; ++j) {
+        if (j < nt) {
+          const float d = wv - Io<uint16_t>::ld1(pp.wt[t0 + j], e);
+          acc[j] = fmaf(d, d, acc[j]);
+        }
+      }
+    }
+    for (int j = 0; j < nt; ++j) {
+      const double tot = block_sum_f64(static_cast<double>(acc[j]), s_red);
+      if (threadIdx.x == 0) partial[static_cast<int64_t>(t0 + j) * n_chunks + c] = tot;
+    }
+  }
+}
+
+// one neighbor's step of k_prox_grad on a group: d = (w - wt) * c, g += d, and -d to gwt
+__device__ __forceinline__ void prox_grad4(float4 wv, float4 v, float c, float4& g, uint16_t* gwt, int64_t e) {
+  const float4 d = make_float4((wv.x - v.x) * c, (wv.y - v.y) * c, (wv.z - v.z) * c, (wv.w - v.w) * c);
+  g.x += d.x;
+  g.y += d.y;
+  g.z += d.z;
+  g.w += d.w;
+  if (gwt) Io<uint16_t>::st(gwt, e >> 2, make_float4(-d.x, -d.y, -d.z, -d.w));
+}
+
+// k_prox_grad's fp32 operations in its order on the widened values; g and -d are rounded to bf16
+// once, at the store.  More than kProxMaxNb neighbors take several launches: the running sum goes
+// through `acc` (fp32, the rows' element offsets) - read when `first` is 0, written instead of
+// gw when `last` is 0 - and never through a bf16 gw.  A chunk that acc_elems does not cover is
+// left alone (the host entry refuses such a call where it can tell).
+__global__ __launch_bounds__(kBlock) void k_prox_grad_bf16(const uint16_t* __restrict__ w, ProxPtrsB16 pp, int k,
+                                                           const int64_t* __restrict__ plan, int n_seg,
+                                                           const float* __restrict__ norms,
+                                                           const float* __restrict__ scale,
+                                                           uint16_t* __restrict__ gw, float* __restrict__ acc,
+                                                           int64_t acc_elems, int first, int last, int packed) {
+  __shared__ float s_c[kProxMaxNb];
+  const int c = blockIdx.x;
+  const int64_t* ch = plan + (n_seg + 1) + 3 * static_cast<int64_t>(c);
+  const int64_t sg = ch[0], beg = ch[1], len = ch[2];
+  if (!(first && last) && beg + len > acc_elems) return;
+  if (threadIdx.x < k) {
+    const float nrm = norms[static_cast<int64_t>(threadIdx.x) * n_seg + sg];
+    s_c[threadIdx.x] = nrm > 0.f ? *scale / nrm : 0.f;
+  }
+  __syncthreads();
+  const ProxCut cut = prox_cut(beg, len, packed);
+  const int64_t body = beg + cut.head;
+  for (int64_t gi = threadIdx.x; gi < cut.groups; gi += kBlock) {
+    const int64_t e = body + 4 * gi;
+    const float4 wv = prox_ld4_once(w, e);
+    float4 g = first ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(acc + e);
+    int t = 0;
+    for (; t + kProxTile <= k; t += kProxTile) {
+      float4 v[kProxTile];
+#pragma unroll
+      for (int j = 0; j < kProxTile; ++j) v[j] = prox_ld4_once(pp.wt[t + j], e);
+#pragma unroll
+      for (int j = 0; j < kProxTile; ++j) prox_grad4(wv, v[j], s_c[t + j], g, pp.gwt[t + j], e);
+    }
+    for (; t < k; ++t) prox_grad4(wv, prox_ld4_once(pp.wt[t], e), s_c[t], g, pp.gwt[t], e);
+    if (last)
+      Io<uint16_t>::st(gw, e >> 2, g);
+    else
+      *reinterpret_cast<float4*>(acc + e) = g;
+  }
+  for (int64_t i = threadIdx.x; i < cut.edge; i += kBlock) {
+    const int64_t e = beg + cut.edge_elem(i);
+    const float wv = Io<uint16_t>::ld1(w, e);
+    float g = first ? 0.f : acc[e];
+    for (int t = 0; t < k; ++t) {
+      const float d = (wv - Io<uint16_t>::ld1(pp.wt[t], e)) * s_c[t];
+      g += d;
+      if (pp.gwt[t]) Io<uint16_t>::st1(pp.gwt[t], e, -d);
+    }
+    if (last)
+      Io<uint16_t>::st1(gw, e, g);
+    else
+      acc[e] = g;
+  }
+}
+
 }  // namespace
 
 // ==========================================================================================
@@ -5758,6 +5914,69 @@ int32_t tal_prox_grad(const float* w, const float* const* wt_host, int32_t k, co
                                            norms + static_cast<int64_t>(base) * n_seg, scale_dev, gw,
                                            base > 0 ? 1 : 0);
     int32_t rc = check_launch("prox grad");
+    if (rc) return rc;
+  }
+  g_err.clear();
+  return TAL_OK;
+}
+
+static bool prox_aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+int32_t tal_prox_norms_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k, const int64_t* plan_dev,
+                            int32_t n_chunks, int32_t n_seg, void* scratch, float* norms_out, void* stream) {
+  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !scratch || !norms_out)
+    return fail(TAL_ERR_INVALID, "tal_prox_norms_bf16: bad arguments");
+  bool packed = prox_aligned(w, 8);
+  for (int j = 0; j < k; ++j) {
+    if (!wt_host[j]) return fail(TAL_ERR_INVALID, "tal_prox_norms_bf16: null neighbor pointer");
+    packed = packed && prox_aligned(wt_host[j], 8);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int base = 0; base < k; base += kProxMaxNb) {
+    const int cnt = std::min(kProxMaxNb, k - base);
+    ProxPtrsB16 pp{};
+    for (int j = 0; j < cnt; ++j) pp.wt[j] = wt_host[base + j];
+    double* part = static_cast<double*>(scratch);
+    k_prox_sumsq_bf16<<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg, n_chunks, part, packed ? 1 : 0);
+    const int64_t outs = static_cast<int64_t>(cnt) * n_seg;
+    k_prox_finish<<<static_cast<unsigned>((outs + 255) / 256), 256, 0, s>>>(
+        plan_dev, n_seg, n_chunks, cnt, part, norms_out + static_cast<int64_t>(base) * n_seg);
+    int32_t rc = check_launch("prox norms bf16");
+    if (rc) return rc;
+  }
+  g_err.clear();
+  return TAL_OK;
+}
+
+int32_t tal_prox_grad_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k, const int64_t* plan_dev,
+                           int32_t n_chunks, int32_t n_seg, const float* norms, const float* scale_dev,
+                           uint16_t* gw, uint16_t* const* gwt_host, float* acc_scratch, int64_t acc_elems,
+                           void* stream) {
+  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !norms || !scale_dev || !gw)
+    return fail(TAL_ERR_INVALID, "tal_prox_grad_bf16: bad arguments");
+  const bool batched = k > kProxMaxNb;
+  // every chunk holds an element and no two overlap: fewer elements than chunks cannot cover them
+  if (batched && (!acc_scratch || acc_elems < n_chunks))
+    return fail(TAL_ERR_INVALID, "tal_prox_grad_bf16: more than " + std::to_string(kProxMaxNb) +
+                                     " neighbors need an fp32 acc_scratch that covers every chunk");
+  bool packed = prox_aligned(w, 8) && prox_aligned(gw, 8) && (!batched || prox_aligned(acc_scratch, 16));
+  for (int j = 0; j < k; ++j) {
+    if (!wt_host[j]) return fail(TAL_ERR_INVALID, "tal_prox_grad_bf16: null neighbor pointer");
+    packed = packed && prox_aligned(wt_host[j], 8) && (!gwt_host || prox_aligned(gwt_host[j], 8));
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int base = 0; base < k; base += kProxMaxNb) {
+    const int cnt = std::min(kProxMaxNb, k - base);
+    ProxPtrsB16 pp{};
+    for (int j = 0; j < cnt; ++j) {
+      pp.wt[j] = wt_host[base + j];
+      pp.gwt[j] = gwt_host ? gwt_host[base + j] : nullptr;
+    }
+    k_prox_grad_bf16<<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg,
+                                                norms + static_cast<int64_t>(base) * n_seg, scale_dev, gw,
+                                                batched ? acc_scratch : nullptr, batched ? acc_elems : 0,
+                                                base == 0 ? 1 : 0, base + cnt == k ? 1 : 0, packed ? 1 : 0);
+    int32_t rc = check_launch("prox grad bf16");
     if (rc) return rc;
   }
   g_err.clear();
