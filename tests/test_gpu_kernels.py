@@ -136,12 +136,14 @@ def test_agg_model_f32_one_launch(cuda, m, n, n_i):
         assert np.array_equal(out_i.cpu().numpy(), oracle.agg_i64(xis, w))
 
 
+@pytest.mark.parametrize("m", [9, 18])
 @pytest.mark.parametrize("mode", [ops.MODE_EXACT, ops.MODE_FMA])
-def test_agg_model_f32_in_place_and_fma(cuda, mode):
+def test_agg_model_f32_in_place_and_fma(cuda, mode, m):
     """The aggregating model is the last operand and the output (both segments), and FMA mode
-    equals agg_f32's FMA mode bit for bit."""
+    equals agg_f32's FMA mode bit for bit; m = 18 is past the operand counts with kernels of
+    their own (the run-time count)."""
     rng = np.random.default_rng(3)
-    n, n_i, m = 100003, 53, 9
+    n, n_i = 100003, 53
     xs = [torch.from_numpy(_rand_f32(rng, n)).to(cuda) for _ in range(m)]
     xis = [torch.from_numpy(rng.integers(0, 10 ** 6, size=n_i)).to(cuda) for _ in range(m)]
     w = [1 / m] * m

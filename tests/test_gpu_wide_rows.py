@@ -91,6 +91,45 @@ def test_k1_past_256_operands(cuda, kind, m):
     assert np.array_equal(got, exp)
 
 
+def test_k1_f32_fma_past_256_operands(cuda):
+    """fp32 K1 in FMA mode past one operand table (m = 257; n = 1027: 256 float4 chunks and a
+    3-element tail), in three layouts: aligned with `out` apart (the second pass continues from
+    `out`: chunk kernel and tail), everything 4 bytes into its buffer (the scalar kernel), and
+    `out` the last operand (the chain through the fp32 scratch).  Each is the host reduction's
+    std::fma chain bit for bit, so the three are each other's too.  Standard-normal inputs and
+    weights in (0, 2/m): no subnormals."""
+    m, n = 257, 1027
+    rng = np.random.default_rng(257)
+    x = rng.standard_normal((m, n)).astype(np.float32)
+    w = rng.uniform(0.0, 2.0 / m, m).tolist()
+    exp = torch.empty(n)
+    ops.host_agg([torch.from_numpy(x[j]) for j in range(m)], w, exp, mode=ops.MODE_FMA)
+    exp = exp.numpy().view(np.uint32)
+
+    dev = torch.from_numpy(x).to(cuda)
+    got = {}
+    out = torch.empty(n, device=cuda)
+    rows = [dev[j].clone() for j in range(m)]  # an allocation each: dev's odd rows are not 16-B aligned
+    assert all(r.data_ptr() % 16 == 0 for r in rows + [out])
+    ops.agg_f32(rows, w, out, mode=ops.MODE_FMA)
+    got["aligned"] = out.cpu().numpy().view(np.uint32)
+
+    bufs = [torch.empty(n + 1, device=cuda) for _ in range(m + 1)]
+    shifted = [b[1:] for b in bufs]
+    assert all(s.data_ptr() % 16 == 4 for s in shifted)
+    for j in range(m):
+        shifted[j].copy_(dev[j])
+    ops.agg_f32(shifted[:m], w, shifted[m], mode=ops.MODE_FMA)
+    got["shifted"] = shifted[m].cpu().numpy().view(np.uint32)
+
+    ops.agg_f32(rows, w, rows[m - 1], mode=ops.MODE_FMA)
+    got["in_place"] = rows[m - 1].cpu().numpy().view(np.uint32)
+
+    for name, g in got.items():
+        assert np.array_equal(g, exp), name
+    assert np.array_equal(got["aligned"], got["shifted"]) and np.array_equal(got["aligned"], got["in_place"])
+
+
 def test_pool_rows_app_past_256_operands(cuda):
     """The per-call app path on pool rows (agg_pool_rows) with 300 operands of a ResNet-like
     fp32 + int64 layout: bitwise the oracle (fp32 chain and int64 truncation)."""

@@ -1,4 +1,4 @@
-// K1 launch-shape probe (not part of the product): the library's k_agg_f32_vec<9> on 9 ResNet-50
+// K1 launch-shape probe (not part of the product): the library's k_agg_vec<float, 9> on 9 ResNet-50
 // operand rows of a 64-row pool (rows rotated per launch), grid-stride with capped grids vs one
 // pass over a full grid; each checked bit for bit against the library launch.
 #include "../../topology_aware_learning_amd/csrc/tal_agg.hip"
@@ -17,7 +17,7 @@ __global__ void k_fill(float4* p, long n4, unsigned seed) {
 
 // one float4 chunk per lane per operand, U chunks per lane, no grid-stride loop
 template <int M, int U>
-__global__ __launch_bounds__(256) void k_flat(OpTableF32 t, float* out, int64_t n4) {
+__global__ __launch_bounds__(256) void k_flat(OpTable<float> t, float* out, int64_t n4) {
   const int64_t i0 = (static_cast<int64_t>(blockIdx.x) * U) * 256 + threadIdx.x;
   float4 v[U][M];
 #pragma unroll
@@ -46,7 +46,7 @@ int main() {
   float *pool, *ref, *out;
   CK(hipMalloc(&pool, (size_t)R * ld * 4)); CK(hipMalloc(&ref, ld * 4)); CK(hipMalloc(&out, ld * 4));
   k_fill<<<4096, 256>>>((float4*)pool, (long)R * ld / 4, 777u); CK(hipDeviceSynchronize());
-  std::vector<OpTableF32> tabs(16);
+  std::vector<OpTable<float>> tabs(16);
   for (int r = 0; r < 16; ++r) {
     for (int k = 0; k < kMaxOps; ++k) { tabs[r].x[k] = nullptr; tabs[r].w[k] = 0.f; }
     for (int k = 0; k < M; ++k) { tabs[r].x[k] = pool + (size_t)((r * 4 + k * 7) % R) * ld; tabs[r].w[k] = 1.f / 9.f; }
@@ -60,18 +60,18 @@ int main() {
     float sum = 0; const int reps = 32;
     for (int i = 0; i < reps; ++i) { CK(hipEventRecord(e0)); launch(tabs[i % 16]); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1)); sum += ms; }
     launch(tabs[5]); CK(hipDeviceSynchronize());
-    launch_pass<true>(tabs[5], M, false, true, ref, n4 * 4, 0); CK(hipDeviceSynchronize());
+    launch_k1<float, M, true, false>(tabs[5], M, ref, n4, n4 * 4, 0); CK(hipDeviceSynchronize());
     CK(hipMemcpy(a.data(), ref, n4 * 16, hipMemcpyDeviceToHost)); CK(hipMemcpy(b.data(), out, n4 * 16, hipMemcpyDeviceToHost));
     printf("%-34s avg %.4f ms  %6.0f GB/s  %s\n", name, sum / reps, bytes / (sum / reps * 1e-3) / 1e9, memcmp(a.data(), b.data(), n4 * 16) ? "MISMATCH" : "OK");
     fflush(stdout);
   };
-  timeit("library launch (cap 4096, U=2)", [&](const OpTableF32& t) { launch_pass<true>(t, M, false, true, out, n4 * 4, 0); });
+  timeit("library launch (cap 4096, U=2)", [&](const OpTable<float>& t) { launch_k1<float, M, true, false>(t, M, out, n4, n4 * 4, 0); });
   for (int g : {2048, 8192, 16384}) {
     char nm[64]; snprintf(nm, sizeof nm, "grid-stride U=2 grid %d", g);
-    timeit(nm, [&](const OpTableF32& t) { k_agg_f32_vec<9, true, false><<<g, kBlock>>>(t, M, out, n4); });
+    timeit(nm, [&](const OpTable<float>& t) { k_agg_vec<float, 9, true, false><<<g, kBlock>>>(t, M, out, n4); });
   }
-  timeit("full grid U=1", [&](const OpTableF32& t) { k_flat<9, 1><<<(n4 + 255) / 256, 256>>>(t, out, n4); });
-  timeit("full grid U=2", [&](const OpTableF32& t) { k_flat<9, 2><<<(n4 + 511) / 512, 256>>>(t, out, n4); });
-  timeit("full grid U=4", [&](const OpTableF32& t) { k_flat<9, 4><<<(n4 + 1023) / 1024, 256>>>(t, out, n4); });
+  timeit("full grid U=1", [&](const OpTable<float>& t) { k_flat<9, 1><<<(n4 + 255) / 256, 256>>>(t, out, n4); });
+  timeit("full grid U=2", [&](const OpTable<float>& t) { k_flat<9, 2><<<(n4 + 511) / 512, 256>>>(t, out, n4); });
+  timeit("full grid U=4", [&](const OpTable<float>& t) { k_flat<9, 4><<<(n4 + 1023) / 1024, 256>>>(t, out, n4); });
   return 0;
 }
