@@ -268,6 +268,16 @@ int32_t tal_agg_round_clique_f32(const float* pool_in, int64_t ld_in, float* poo
                                  int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                  int32_t mode, void* stream);
 
+/* The clique round on bf16 pools (ABI 30): the same table and the same checks, arithmetic as
+ * tal_agg_bf16 per mode.  EXACT: the shared products are bf16(fl(w * x_j)) and every step of a
+ * row's chain rounds its fp32 sum to bf16, so each row stays the reference's own left-to-right
+ * chain on bf16 tensors; FMA: the fp32 entry's fused chains on the widened values, rounded once
+ * by the store (NaN stored as 0xFFFF).  A column pair is one 32-bit word: pools 4-B aligned
+ * with even ld, else TAL_ERR_INVALID. */
+int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,
+                                  int64_t ld_out, int64_t n, const int32_t* table_dev,
+                                  int32_t n_cliques, int32_t mmax, int32_t mode, void* stream);
+
 /* The same round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or
  * streamed plans.  A staged tile holds the sources' values as fp32 (c4 float4 per source). */

@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 29;
+constexpr int kAbiVersion = 30;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -327,6 +327,13 @@ struct Io<float> {
   static __device__ __forceinline__ void st(float* b, int64_t i4, float4 v) { st_stream(b, i4, v); }
   static __device__ __forceinline__ float ld1(const float* b, int64_t e) { return b[e]; }
   static __device__ __forceinline__ void st1(float* b, int64_t e, float v) { b[e] = v; }
+  // the column pair (e, e + 1), e even (K3c)
+  static __device__ __forceinline__ bf_v2f ld2(const float* b, int64_t e) {
+    return __builtin_nontemporal_load(reinterpret_cast<const bf_v2f*>(b + e));
+  }
+  static __device__ __forceinline__ void st2(float* b, int64_t e, bf_v2f v) {
+    __builtin_nontemporal_store(v, reinterpret_cast<bf_v2f*>(b + e));
+  }
 };
 
 template <>
@@ -357,6 +364,16 @@ struct Io<uint16_t> {
   }
   static __device__ __forceinline__ void st1(uint16_t* b, int64_t e, float v) {
     b[e] = static_cast<uint16_t>(store_bf16x2(v, 0.f) & 0xffffu);
+  }
+  // the column pair (e, e + 1), e even: one 32-bit word (K3c)
+  static __device__ __forceinline__ bf_v2f ld2(const uint16_t* b, int64_t e) {
+    const uint32_t u = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(b + e));
+    return bf_v2f{bf16_lo(u), bf16_hi(u)};
+  }
+  static __device__ __forceinline__ void st2(uint16_t* b, int64_t e, bf_v2f v) {
+    uint32_t u = cvt_bf16x2(v.x, v.y);
+    if (__builtin_isunordered(v.x, v.y)) u = store_bf16x2(v.x, v.y);  // as pack: only where a lane holds a NaN
+    __builtin_nontemporal_store(u, reinterpret_cast<uint32_t*>(b + e));
   }
 };
 
@@ -2186,6 +2203,10 @@ int32_t launch_round_narrow(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
 // its own left-to-right chain (the prefix is shared, not reassociated); padding terms are -0.0
 // (x + -0.0 == x for every x), S_0 = -0.0 (-0.0 + p == p).  FMA mode keeps x_j and fuses
 // fma(w, x_j, acc); its padding is the zero whose product with w is -0.0.
+// Storage type T: fp32, or bf16 bits (one 32-bit word per column pair, widened on the load).
+// bf16 EXACT rounds the products and every sum of a chain to bf16 (tal_agg_bf16's arithmetic;
+// -0.0 + p == p and rounding a bf16 value is the identity, so S_0 and the padding stay exact);
+// bf16 FMA runs the fp32 chains and rounds once, at the store.
 // ------------------------------------------------------------------------------------------
 constexpr int kCliqueMax = 64;
 constexpr int kCliqueExtra = 4;        // attached rows per clique block
@@ -2195,18 +2216,23 @@ static_assert(4 + 2 * kCliqueMax + kCliqueExtra * kCliqueExtraWords == TAL_CLIQU
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-template <bool EXACT>
+template <typename T, bool EXACT>
 __device__ __forceinline__ v2f clique_term(v2f acc, float w, v2f p) {
-  if constexpr (EXACT) return v2f{__fadd_rn(acc.x, p.x), __fadd_rn(acc.y, p.y)};
+  if constexpr (kIsBf16<T> && EXACT) return round_bf16x2(acc + p);
+  else if constexpr (EXACT) return v2f{__fadd_rn(acc.x, p.x), __fadd_rn(acc.y, p.y)};
   else return v2f{__builtin_fmaf(w, p.x, acc.x), __builtin_fmaf(w, p.y, acc.y)};
 }
 
 typedef float v8f __attribute__((ext_vector_type(8)));
 
 // Four clique chains stepped at once (k-th pair of lanes = chain k): one IR operation per step.
-template <bool EXACT>
+template <typename T, bool EXACT>
 __device__ __forceinline__ v8f clique_term4(v8f acc, float w, v8f p) {
-  if constexpr (EXACT) return acc + p;  // IEEE adds, one rounding each (no contraction: -ffp-contract=off)
+  if constexpr (kIsBf16<T> && EXACT) {
+    const v8f s = acc + p;
+    return v8f{round_bf16(s[0]), round_bf16(s[1]), round_bf16(s[2]), round_bf16(s[3]),
+               round_bf16(s[4]), round_bf16(s[5]), round_bf16(s[6]), round_bf16(s[7])};
+  } else if constexpr (EXACT) return acc + p;  // IEEE adds, one rounding each (no contraction: -ffp-contract=off)
   else return __builtin_elementwise_fma(v8f{w, w, w, w, w, w, w, w}, p, acc);
 }
 
@@ -2221,15 +2247,16 @@ __device__ __forceinline__ int opaque_zero() {
 
 // Columns e and e + 1 of every row of clique block `t`.
 // acc (+)= fl(v * x) for an attached row's operand (raw value x)
-template <bool EXACT>
+template <typename T, bool EXACT>
 __device__ __forceinline__ v2f clique_xterm(v2f acc, float v, v2f x) {
-  if constexpr (EXACT) return v2f{__fadd_rn(acc.x, __fmul_rn(v, x.x)), __fadd_rn(acc.y, __fmul_rn(v, x.y))};
+  if constexpr (kIsBf16<T> && EXACT) return round_bf16x2(acc + round_bf16x2(v2f{v, v} * x));
+  else if constexpr (EXACT) return v2f{__fadd_rn(acc.x, __fmul_rn(v, x.x)), __fadd_rn(acc.y, __fmul_rn(v, x.y))};
   else return v2f{__builtin_fmaf(v, x.x, acc.x), __builtin_fmaf(v, x.y, acc.y)};
 }
 
-template <int MMAX, bool EXACT>
-__global__ __launch_bounds__(kBlock) void k_round_clique(const float* __restrict__ pin, int64_t ld_in,
-                                                         float* __restrict__ pout, int64_t ld_out,
+template <int MMAX, bool EXACT, typename T>
+__global__ __launch_bounds__(kBlock) void k_round_clique(const T* __restrict__ pin, int64_t ld_in,
+                                                         T* __restrict__ pout, int64_t ld_out,
                                                          int64_t n2, const int32_t* __restrict__ table) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_WORDS;
   const int64_t c2 = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -2243,8 +2270,7 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const float* __restrict
   v2f p[MMAX];
 #pragma unroll
   for (int j = 0; j < MMAX; ++j) {
-    const float* src = pin + static_cast<int64_t>(t[4 + (j < m ? j : 0) + opaque_zero()]) * ld_in + e;
-    p[j] = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(src));
+    p[j] = Io<T>::ld2(pin + static_cast<int64_t>(t[4 + (j < m ? j : 0) + opaque_zero()]) * ld_in, e);
     // batches of 8: the scheduler would otherwise compute all row addresses first
     if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
   }
@@ -2258,28 +2284,27 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const float* __restrict
     const uint32_t lo = static_cast<uint32_t>(xr[2]), hi = static_cast<uint32_t>(xr[3]);
     const int self_m = xr[4], self_e = xr[5], n_ext = xr[6];
     const int pos0 = n_ext > 0 ? xr[9] : -1, pos1 = n_ext > 1 ? xr[10] : -1;
-    auto ld_row = [&](int r) {
-      return __builtin_nontemporal_load(reinterpret_cast<const v2f*>(pin + static_cast<int64_t>(r) * ld_in + e));
-    };
+    auto ld_row = [&](int r) { return Io<T>::ld2(pin + static_cast<int64_t>(r) * ld_in, e); };
     const v2f e0 = n_ext > 0 ? ld_row(xr[7]) : v2f{0.f, 0.f};
     const v2f e1 = n_ext > 1 ? ld_row(xr[8]) : v2f{0.f, 0.f};
     v2f xs = self_e >= 0 ? ld_row(self_e) : v2f{0.f, 0.f};
     v2f acc = v2f{-0.f, -0.f};
 #pragma unroll
     for (int j = 0; j <= MMAX; ++j) {
-      if (pos0 == j) acc = clique_xterm<EXACT>(acc, v, e0);
-      if (pos1 == j) acc = clique_xterm<EXACT>(acc, v, e1);
+      if (pos0 == j) acc = clique_xterm<T, EXACT>(acc, v, e0);
+      if (pos1 == j) acc = clique_xterm<T, EXACT>(acc, v, e1);
       if (j < MMAX) {
-        if (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u) acc = clique_xterm<EXACT>(acc, v, p[j]);
+        if (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u) acc = clique_xterm<T, EXACT>(acc, v, p[j]);
         if (self_m == j) xs = p[j];
       }
     }
-    acc = clique_xterm<EXACT>(acc, v, xs);
-    __builtin_nontemporal_store(acc, reinterpret_cast<v2f*>(pout + static_cast<int64_t>(xr[0]) * ld_out + e));
+    acc = clique_xterm<T, EXACT>(acc, v, xs);
+    Io<T>::st2(pout + static_cast<int64_t>(xr[0]) * ld_out, e, acc);
   }
 #pragma unroll
   for (int j = 0; j < MMAX; ++j) {
-    if constexpr (EXACT) p[j] = v2f{__fmul_rn(w, p[j].x), __fmul_rn(w, p[j].y)};
+    if constexpr (kIsBf16<T> && EXACT) p[j] = round_bf16x2(v2f{w, w} * p[j]);
+    else if constexpr (EXACT) p[j] = v2f{__fmul_rn(w, p[j].x), __fmul_rn(w, p[j].y)};
     if (j >= m) p[j] = v2f{pad, pad};
   }
   // Rows four at a time: row r = ((S_r + p[r+1]) + ... + p[MMAX-1]) + p[r], S_{r+1} = S_r + p[r]
@@ -2297,7 +2322,7 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const float* __restrict
     v2f sp[4];  // S_i .. S_{i+3}
     sp[0] = s;
 #pragma unroll
-    for (int k = 1; k < 4; ++k) sp[k] = clique_term<EXACT>(sp[k - 1], w, p[i + k - 1]);
+    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], w, p[i + k - 1]);
     if (orow[0] >= 0 || orow[1] >= 0 || orow[2] >= 0 || orow[3] >= 0) {
       // heads: row i+k takes p[i+k+1 .. i+3] before the four chains run in step
       v2f a[4];
@@ -2305,33 +2330,32 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const float* __restrict
       for (int k = 0; k < 4; ++k) {
         a[k] = sp[k];
 #pragma unroll
-        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<EXACT>(a[k], w, p[j]);
+        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], w, p[j]);
       }
       // the four chains as one 8-wide vector: each step is one IR operation (four packed adds
       // on natural register pairs), which the compiler can neither split into four loops nor
       // sink into the stores' branches
       v8f q = {a[0].x, a[0].y, a[1].x, a[1].y, a[2].x, a[2].y, a[3].x, a[3].y};
 #pragma unroll
-      for (int j = i + 4; j < MMAX; ++j) q = clique_term4<EXACT>(q, w, v8f{p[j].x, p[j].y, p[j].x, p[j].y,
+      for (int j = i + 4; j < MMAX; ++j) q = clique_term4<T, EXACT>(q, w, v8f{p[j].x, p[j].y, p[j].x, p[j].y,
                                                                            p[j].x, p[j].y, p[j].x, p[j].y});
-      q = clique_term4<EXACT>(q, w, v8f{p[i].x, p[i].y, p[i + 1].x, p[i + 1].y, p[i + 2].x, p[i + 2].y,
+      q = clique_term4<T, EXACT>(q, w, v8f{p[i].x, p[i].y, p[i + 1].x, p[i + 1].y, p[i + 2].x, p[i + 2].y,
                                         p[i + 3].x, p[i + 3].y});
 #pragma unroll
       for (int k = 0; k < 4; ++k) a[k] = v2f{q[2 * k], q[2 * k + 1]};
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (orow[k] >= 0)
-          __builtin_nontemporal_store(a[k], reinterpret_cast<v2f*>(pout + static_cast<int64_t>(orow[k]) * ld_out + e));
+        if (orow[k] >= 0) Io<T>::st2(pout + static_cast<int64_t>(orow[k]) * ld_out, e, a[k]);
     }
-    s = clique_term<EXACT>(sp[3], w, p[i + 3]);
+    s = clique_term<T, EXACT>(sp[3], w, p[i + 3]);
   }
 }
 
 // The last column of an odd-width round: one thread per member row, its chain in reference
 // order (every other member ascending, then itself).
-template <bool EXACT>
-__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const float* __restrict__ pin, int64_t ld_in,
-                                                                  float* __restrict__ pout, int64_t ld_out,
+template <bool EXACT, typename T>
+__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const T* __restrict__ pin, int64_t ld_in,
+                                                                  T* __restrict__ pout, int64_t ld_out,
                                                                   int64_t e, const int32_t* __restrict__ table) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
   const int m = t[0];
@@ -2344,16 +2368,15 @@ __global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const float* _
   for (int j = 0; j <= m; ++j) {
     if (j == i) continue;
     const int k = j < m ? j : i;
-    const float x = pin[static_cast<int64_t>(t[4 + k]) * ld_in + e];
-    acc = EXACT ? __fadd_rn(acc, __fmul_rn(w, x)) : __builtin_fmaf(w, x, acc);
+    acc = next1t<T, EXACT>(acc, w, Io<T>::ld1(pin, static_cast<int64_t>(t[4 + k]) * ld_in + e));
   }
-  pout[static_cast<int64_t>(orow) * ld_out + e] = acc;
+  Io<T>::st1(pout, static_cast<int64_t>(orow) * ld_out + e, acc);
 }
 
 // The last column for a block's attached rows: one thread per attached row.
-template <bool EXACT>
-__global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const float* __restrict__ pin,
-                                                                          int64_t ld_in, float* __restrict__ pout,
+template <bool EXACT, typename T>
+__global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const T* __restrict__ pin,
+                                                                          int64_t ld_in, T* __restrict__ pout,
                                                                           int64_t ld_out, int64_t e,
                                                                           const int32_t* __restrict__ table) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
@@ -2363,8 +2386,8 @@ __global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const 
   const float v = __int_as_float(xr[1]);
   const uint32_t lo = static_cast<uint32_t>(xr[2]), hi = static_cast<uint32_t>(xr[3]);
   const int n_ext = xr[6];
-  auto x_of = [&](int r) { return pin[static_cast<int64_t>(r) * ld_in + e]; };
-  auto term = [&](float a, float x) { return EXACT ? __fadd_rn(a, __fmul_rn(v, x)) : __builtin_fmaf(v, x, a); };
+  auto x_of = [&](int r) { return Io<T>::ld1(pin, static_cast<int64_t>(r) * ld_in + e); };
+  auto term = [&](float a, float x) { return next1t<T, EXACT>(a, v, x); };
   float acc = -0.f;
   for (int j = 0; j <= kCliqueMax; ++j) {
     for (int k = 0; k < n_ext; ++k)
@@ -2372,11 +2395,11 @@ __global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const 
     if (j < kCliqueMax && (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u)) acc = term(acc, x_of(t[4 + j]));
   }
   acc = term(acc, x_of(xr[4] >= 0 ? t[4 + xr[4]] : xr[5]));
-  pout[static_cast<int64_t>(xr[0]) * ld_out + e] = acc;
+  Io<T>::st1(pout, static_cast<int64_t>(xr[0]) * ld_out + e, acc);
 }
 
-template <bool EXACT>
-int32_t launch_round_clique(const float* pin, int64_t ld_in, float* pout, int64_t ld_out, int64_t n,
+template <bool EXACT, typename T>
+int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
                             const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s) {
   const int64_t n2 = n / 2;
   const int64_t blocks = (n2 + kBlock - 1) / kBlock;
@@ -2386,21 +2409,21 @@ int32_t launch_round_clique(const float* pin, int64_t ld_in, float* pout, int64_
     // the chains run over MMAX slots, the ones past the largest clique adding -0.0: MMAX close
     // to the clique size keeps those no-op adds few (a 60-member barbell clique under MMAX 64
     // spent 13 % of its adds on padding)
-    if (mmax <= 16) k_round_clique<16, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 32) k_round_clique<32, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 40) k_round_clique<40, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 48) k_round_clique<48, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 56) k_round_clique<56, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 60) k_round_clique<60, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else k_round_clique<64, EXACT><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    if (mmax <= 16) k_round_clique<16, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    else if (mmax <= 32) k_round_clique<32, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    else if (mmax <= 40) k_round_clique<40, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    else if (mmax <= 48) k_round_clique<48, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    else if (mmax <= 56) k_round_clique<56, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    else if (mmax <= 60) k_round_clique<60, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    else k_round_clique<64, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
     int32_t rc = check_launch("clique round kernel");
     if (rc) return rc;
   }
   if (n % 2) {
-    k_round_clique_tail<EXACT><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
+    k_round_clique_tail<EXACT, T><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
     int32_t rc = check_launch("clique round tail kernel");
     if (rc) return rc;
-    k_round_clique_tail_extra<EXACT><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
+    k_round_clique_tail_extra<EXACT, T><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
     return check_launch("clique round tail kernel (attached rows)");
   }
   return TAL_OK;
@@ -5078,6 +5101,27 @@ int32_t agg_round(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, 
   return launch_round_scalar<T>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
 }
 
+// tal_agg_round_clique_<T>: a column pair is one 8-B (fp32) or 4-B (bf16) access, which sets the
+// alignment rule.
+template <typename T>
+int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
+                         const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream) {
+  const std::string name(fn);
+  if (!pool_in || !pool_out || !table_dev) return fail(TAL_ERR_INVALID, name + ": null pointer");
+  if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
+  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
+  if (n_cliques < 0 || mmax < 1 || mmax > kCliqueMax)
+    return fail(TAL_ERR_INVALID, name + ": n_cliques >= 0, 1 <= mmax <= 64");
+  const uintptr_t mask = 2 * sizeof(T) - 1;
+  if (((reinterpret_cast<uintptr_t>(pool_in) | reinterpret_cast<uintptr_t>(pool_out)) & mask) || ld_in % 2 || ld_out % 2)
+    return fail(TAL_ERR_INVALID, name + ": pools must be " + std::to_string(2 * sizeof(T)) + "-B aligned with even ld");
+  if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return mode == TAL_MODE_EXACT
+             ? launch_round_clique<true, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s)
+             : launch_round_clique<false, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -5170,20 +5214,15 @@ const char* tal_round_kernel_name(const tal_round_plan_info* info, int32_t bf16)
 int32_t tal_agg_round_clique_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                  int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                  int32_t mode, void* stream) {
-  if (!pool_in || !pool_out || !table_dev)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_clique_f32: null pointer");
-  if (pool_in == pool_out)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_clique_f32: the clique round runs out of place");
-  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, "tal_agg_round_clique_f32: bad n / ld");
-  if (n_cliques < 0 || mmax < 1 || mmax > kCliqueMax)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_clique_f32: n_cliques >= 0, 1 <= mmax <= 64");
-  if (!aligned8(pool_in) || !aligned8(pool_out) || ld_in % 2 || ld_out % 2)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_clique_f32: pools must be 8-B aligned with even ld");
-  if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return mode == TAL_MODE_EXACT
-             ? launch_round_clique<true>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s)
-             : launch_round_clique<false>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s);
+  return agg_round_clique<float>("tal_agg_round_clique_f32", pool_in, ld_in, pool_out, ld_out, n, table_dev,
+                                 n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                  int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                  int32_t mode, void* stream) {
+  return agg_round_clique<uint16_t>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n, table_dev,
+                                    n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_reg(const void* pool_in, int64_t ld_in, void* pool_out, int64_t ld_out, int64_t n,

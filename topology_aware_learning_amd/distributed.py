@@ -152,7 +152,7 @@ def float_segments(layout: StateLayout):
 
 def tune_segment(layout: StateLayout) -> str:
     """The segment a round plan is tuned on: bf16 when there is one (its plan forms - sparse,
-    narrow - also run fp32 and int64), else fp32."""
+    narrow, clique - also run fp32 and int64), else fp32."""
     return "b16" if layout.n_b16 else "f32"
 
 

@@ -416,8 +416,9 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS):
 @dataclass
 class CliquePlan:
     """A round split into clique blocks (K3c, one launch) and the remaining rows (a regular
-    RoundPlan, None if there are none).  `full` is a sparse plan over all rows, used for the
-    int64 and bf16 segments (the clique kernel is fp32)."""
+    RoundPlan, None if there are none).  The clique kernel takes fp32 and bf16 pools; `full` is a
+    sparse plan over all rows, used for the int64 segment and for pools that miss K3c's
+    column-pair alignment (8 B fp32, 4 B bf16, even row stride)."""
     table: np.ndarray
     n_cliques: int
     mmax: int
@@ -453,8 +454,10 @@ class CliquePlan:
 
 
 def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
-                      rest_spec: Optional[dict] = None) -> Optional[CliquePlan]:
-    """CliquePlan of a round, or None when it has no clique block (find_cliques)."""
+                      rest_spec: Optional[dict] = None, bf16: bool = False) -> Optional[CliquePlan]:
+    """CliquePlan of a round, or None when it has no clique block (find_cliques).  bf16: the
+    plan runs on bf16 pools, so its rest plan must be a form tal_agg_round_bf16 takes (sparse or
+    narrow: dense_rb 0, stream_cs 0); a rest_spec that asks for another form is a ValueError."""
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
     cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows)
     if not cliques:
@@ -482,6 +485,8 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
     if rest:
         sub = _sub_csr(row_ptr, col, w, out_row, rest)
         rest_plan = plan_from_spec(*sub, rest_spec) if rest_spec else build_plan(*sub)
+        if bf16 and (not isinstance(rest_plan, RoundPlan) or rest_plan.info.dense_rb or rest_plan.info.stream_cs):
+            raise ValueError("a bf16 clique plan's other rows take a sparse or narrow plan (dense_rb 0, stream_cs 0)")
     mmax = max(len(c[0]) for c in cliques)
     return CliquePlan(table=table.reshape(-1), n_cliques=len(cliques), mmax=mmax,
                       clique_sources=sum(len(c[0]) for c in cliques) + n_ext_loads,
@@ -764,8 +769,8 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
         key = ("bcast", c4, waves, wg)
         if all(key != k for k, _ in cands) and p.spec != base.spec:
             cands.append((key, p))
-    if not bf16 and not isinstance(base, CliquePlan):
-        cp = build_clique_plan(row_ptr, col, w, out_row)
+    if not isinstance(base, CliquePlan):
+        cp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16)
         if cp is not None:
             cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
             cands.append((("clique",), cp))
@@ -794,7 +799,7 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     pool_in."""
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("tune_plan needs distinct input / output pools")
-    bf16 = pool_in.dtype == torch.bfloat16  # bf16 rounds: sparse and narrow plans only
+    bf16 = pool_in.dtype == torch.bfloat16  # bf16 rounds: sparse, narrow and clique plans
     run = round_bf16 if bf16 else round_f32
     cands = tune_candidates(row_ptr, col, w, out_row, bf16=bf16, mode=mode)
     base = cands[0][1]
@@ -861,10 +866,16 @@ def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
 
 def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT):
     """The plan the round components build when they do not time candidates (tune=False):
-    the round's uniform-weight clique blocks by K3c when it has any (fp32 pools; the other rows
-    by their own sparse plan), else build_plan's sparse form at the tile width and LDS budget
-    its cost model picks.  On the round-1 A/B tables this is the measured winner's form for
-    configs 2-5 (tests/test_host_logic.py::test_default_plan_forms).  One exception, from
+    the round's uniform-weight clique blocks by K3c when it has any (the other rows by their own
+    sparse plan), else build_plan's sparse form at the tile width and LDS budget its cost model
+    picks.  On the round-1 A/B tables this is the measured winner's form for configs 2-5
+    (tests/test_host_logic.py::test_default_plan_forms).  bf16 pools take the clique plan in
+    both modes: against the sparse form they ran before (medians of 20 interleaved runs,
+    tools/clique_bf16_rate.py, profiles/r12) config 4 on bf16 - barbell(60, 8), 128 x ResNet-50 -
+    took 7.38 ms against 19.05 in EXACT mode and 6.11 against 8.48 in FMA mode, and the complete
+    graph of 64 (`unweighted_fl`, CIFAR-CNN width) 0.869 against 5.23 and 0.729 against 2.26; each
+    is past tune_plan's 1 % margin and the forms agree bit for bit (block sizes other than 60
+    and 64 were not timed on bf16; they follow the fp32 rule).  One exception, from
     round 4's measurements: a round whose narrow plan needs per-operand weights (the pairs
     form: centrality weights on a graph whose degrees differ) runs the narrow kernel's
     broadcast form with the whole source set in one LDS tile — for bf16 in FMA mode the
@@ -880,11 +891,10 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     bf16 pools the wide-row kernel - or, rows out of reference order, one K1 call per row
     (RowCallPlan)."""
     try:
-        if not bf16:
-            cp = build_clique_plan(row_ptr, col, w, out_row)
-            if cp is not None:
-                cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
-                return cp
+        cp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16)
+        if cp is not None:
+            cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
+            return cp
         p = build_plan(row_ptr, col, w, out_row, dense=0)
     except _lib.TalError as exc:
         if exc.code != _lib.TAL_ERR_CAPACITY:
@@ -956,7 +966,7 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
     """K3 on [models, ld] fp32 pools (snapshot semantics; see tal_agg.h).  A CliquePlan runs
     its clique blocks with K3c and its other rows with their regular plan (out of place)."""
     if isinstance(plan, CliquePlan):
-        return _round_clique(pool_in, pool_out, plan, n, mode, stream)
+        return _round_clique(pool_in, pool_out, plan, n, torch.float32, mode, stream)
     if isinstance(plan, RegPlan):
         return _round_reg(pool_in, pool_out, plan, n, torch.float32, mode, stream)
     if isinstance(plan, RowCallPlan):
@@ -964,9 +974,12 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
     return _round(pool_in, pool_out, plan, n, torch.float32, mode, stream)
 
 
-def _round_clique(pool_in, pool_out, plan: CliquePlan, n, mode, stream):
-    _require_gpu(pool_in, "pool_in", torch.float32)
-    _require_gpu(pool_out, "pool_out", torch.float32)
+_CLIQUE_FN = {torch.float32: "tal_agg_round_clique_f32", torch.bfloat16: "tal_agg_round_clique_bf16"}
+
+
+def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
+    _require_gpu(pool_in, "pool_in", dtype)
+    _require_gpu(pool_out, "pool_out", dtype)
     if pool_in.dim() != 2 or pool_out.dim() != 2:
         raise ValueError("pools must be 2-D [models, ld]")
     if pool_in.device != pool_out.device:
@@ -976,9 +989,10 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, mode, stream):
     if plan.device is None or plan.device.device != pool_in.device:
         plan.to(pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
-    if (pool_in.stride(0) | pool_out.stride(0)) % 2 or (pool_in.data_ptr() | pool_out.data_ptr()) % 8:
-        # K3c reads and writes 8-B column pairs: rows that are not 8-B aligned take the full plan
-        return _round(pool_in, pool_out, plan.full, n, torch.float32, mode, stream)
+    pair = 2 * pool_in.element_size()
+    if (pool_in.stride(0) | pool_out.stride(0)) % 2 or (pool_in.data_ptr() | pool_out.data_ptr()) % pair:
+        # K3c reads and writes column pairs (8 B fp32, 4 B bf16): rows not aligned to one take the full plan
+        return _round(pool_in, pool_out, plan.full, n, dtype, mode, stream)
     t = plan.table.reshape(plan.n_cliques, CLIQUE_WORDS)
     att = t[:, 4 + 2 * CLIQUE_MAX:].reshape(plan.n_cliques, CLIQUE_EXTRA, CLIQUE_EXTRA_WORDS)
     used = np.arange(CLIQUE_EXTRA)[None, :] < t[:, 2:3]  # attached records in use
@@ -987,12 +1001,12 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, mode, stream):
     if max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(), att[used][:, 0].max(initial=-1)) >= pool_out.shape[0]:
         raise ValueError("plan writes a pool row beyond pool_out")
     L = _lib.load()
-    check(L.tal_agg_round_clique_f32(ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0),
-                                     ctypes.c_void_p(pool_out.data_ptr()), pool_out.stride(0), n,
-                                     ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax,
-                                     int(mode), _stream(pool_in.device, stream)))
+    check(getattr(L, _CLIQUE_FN[dtype])(ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0),
+                                        ctypes.c_void_p(pool_out.data_ptr()), pool_out.stride(0), n,
+                                        ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax,
+                                        int(mode), _stream(pool_in.device, stream)))
     if plan.rest is not None:
-        _round(pool_in, pool_out, plan.rest, n, torch.float32, mode, stream)
+        _round(pool_in, pool_out, plan.rest, n, dtype, mode, stream)
     return pool_out
 
 
@@ -1008,9 +1022,12 @@ def round_i64(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n:
 def round_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n: Optional[int] = None,
                mode: int = MODE_EXACT, stream=None) -> torch.Tensor:
     """K3 on [models, ld] bf16 pools (sparse, narrow or - rows wider than one LDS tile - streamed
-    plans of at most 16 rows per group, the wide-row kernel; modes as agg_bf16)."""
+    plans of at most 16 rows per group, the wide-row kernel; modes as agg_bf16).  A CliquePlan
+    runs its clique blocks with K3c on bf16 (tal_agg_round_clique_bf16) and its other rows with
+    their regular plan, out of place; pools that miss the 4-B column-pair alignment take
+    `plan.full`."""
     if isinstance(plan, CliquePlan):
-        plan = plan.full
+        return _round_clique(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
     if isinstance(plan, RegPlan):
         return _round_reg(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
     if isinstance(plan, RowCallPlan):
