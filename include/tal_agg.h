@@ -278,6 +278,34 @@ int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16
                                   int64_t ld_out, int64_t n, const int32_t* table_dev,
                                   int32_t n_cliques, int32_t mmax, int32_t mode, void* stream);
 
+/* Clique rounds with per-source weights (ABI 31): the weighted and centrality apps on a clique.
+ * Source s_j carries the same fp32 weight w_j in every row of the block (all members aggregate
+ * over the same models, so the normaliser is common), hence the products p_j = fl(w_j * x_j) are
+ * still shared and every row is the same in-order chain as above; only the multiply reads w_j.
+ * EXACT: p_j = fl(w_j * x_j) (bf16: rounded to bf16, as is every step of a chain); FMA:
+ * acc = fma(w_j, x_j, acc) along the same chains from -0.0.  Zero and negative weights are
+ * ordinary values.  table_dev is the record above; its two weight words (bits of w, bits of v)
+ * are ignored.  wtab_dev: n_cliques records of TAL_CLIQUE_WWORDS floats on the device,
+ *   {w[64], attached[4]{v_member[64], v_ext[2], v_self}}
+ * w[j] = the weight of s_j; for attached row q, v_member[j] = its weight for member position j
+ * (used where its mask selects j), v_ext[k] = for ext_row[k], v_self = for its own model.  Every
+ * slot not in use holds 1.0f: a padding step multiplies -0.0 by it (fl(1 * -0.0) = -0.0,
+ * fma(1, -0.0, acc) = acc for every acc, -0.0 included).  Same checks and errors as the entries
+ * above, and TAL_ERR_INVALID for a null wtab_dev. */
+#define TAL_CLIQUE_WWORDS 332
+#if defined(__cplusplus)
+static_assert(TAL_CLIQUE_WWORDS == 64 + 4 * (64 + 2 + 1), "weight record: 64 members + 4 attached rows");
+#else
+_Static_assert(TAL_CLIQUE_WWORDS == 64 + 4 * (64 + 2 + 1), "weight record: 64 members + 4 attached rows");
+#endif
+int32_t tal_agg_round_clique_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                   int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                   int32_t mode, void* stream, const float* wtab_dev);
+int32_t tal_agg_round_clique_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,
+                                    int64_t ld_out, int64_t n, const int32_t* table_dev,
+                                    int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
+                                    const float* wtab_dev);
+
 /* The same round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or
  * streamed plans.  A staged tile holds the sources' values as fp32 (c4 float4 per source). */

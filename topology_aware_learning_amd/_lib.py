@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 EXPORTED = (
     "tal_last_error",
@@ -47,6 +47,8 @@ EXPORTED = (
     "tal_round_kernel_name",
     "tal_agg_round_clique_f32",
     "tal_agg_round_clique_bf16",
+    "tal_agg_round_clique_w_f32",
+    "tal_agg_round_clique_w_bf16",
     "tal_agg_round_reg",
     "tal_cosine_plan_words",
     "tal_cosine_plan_build",
@@ -188,6 +190,8 @@ _SIGS = {
     "tal_round_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(RoundPlanInfo), _I32]),
     "tal_agg_round_clique_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_clique_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
+    "tal_agg_round_clique_w_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
+    "tal_agg_round_clique_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_agg_round_reg": (_I32, [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "tal_cosine_plan_words": (_I64, [_PI64, _I32]),
     "tal_cosine_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),

@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 30;
+constexpr int kAbiVersion = 31;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -2207,12 +2207,22 @@ int32_t launch_round_narrow(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
 // bf16 EXACT rounds the products and every sum of a chain to bf16 (tal_agg_bf16's arithmetic;
 // -0.0 + p == p and rounding a bf16 value is the identity, so S_0 and the padding stay exact);
 // bf16 FMA runs the fp32 chains and rounds once, at the store.
+// WSRC: per-source weights (the weighted and centrality apps on a clique: source j carries the
+// same fp32 weight w_j in every row of the block, so p_j = fl(w_j * x_j) is still shared and the
+// chains are unchanged; only the multiply reads w_j).  The weights come from a second table of
+// TAL_CLIQUE_WWORDS floats per block; lane j of every wavefront holds w_j in one VGPR and a
+// step reads it with a constant-lane v_readlane_b32 (an SGPR for the one instruction that
+// needs it: 64 weights live in SGPRs would not fit beside the row indices).  Padding slots
+// are x = -0.0 with the table's weight 1.0f: fl(1 * -0.0) = -0.0 and fma(1, -0.0, acc) = acc.
+// The kernels without WSRC are the ones above, instruction for instruction.
 // ------------------------------------------------------------------------------------------
 constexpr int kCliqueMax = 64;
 constexpr int kCliqueExtra = 4;        // attached rows per clique block
 constexpr int kCliqueExtraWords = 12;  // {out, v bits, mask lo, mask hi, self member, self row,
                                        //  n_ext, ext row 0, ext row 1, ext pos 0, ext pos 1, 0}
 static_assert(4 + 2 * kCliqueMax + kCliqueExtra * kCliqueExtraWords == TAL_CLIQUE_WORDS, "table layout");
+constexpr int kCliqueExtraW = kCliqueMax + 3;  // an attached row's weights: 64 member positions, 2 ext, self
+static_assert(kCliqueMax + kCliqueExtra * kCliqueExtraW == TAL_CLIQUE_WWORDS, "weight table layout");
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -2236,6 +2246,18 @@ __device__ __forceinline__ v8f clique_term4(v8f acc, float w, v8f p) {
   else return __builtin_elementwise_fma(v8f{w, w, w, w, w, w, w, w}, p, acc);
 }
 
+// The chains' last step under per-source weights: chain k takes its own term with its own weight.
+template <typename T, bool EXACT>
+__device__ __forceinline__ v8f clique_term4(v8f acc, float w0, float w1, float w2, float w3, v8f p) {
+  if constexpr (EXACT) return clique_term4<T, EXACT>(acc, w0, p);
+  else return __builtin_elementwise_fma(v8f{w0, w0, w1, w1, w2, w2, w3, w3}, p, acc);
+}
+
+// Lane `lane` (a constant) of v as a wave-uniform value.
+__device__ __forceinline__ float lane_value(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
 // A zero the compiler cannot see through: table reads indexed with it stay where they are
 // instead of being hoisted to the top of the kernel, where 128 live row indices would spill
 // the scalar register file.
@@ -2254,17 +2276,37 @@ __device__ __forceinline__ v2f clique_xterm(v2f acc, float v, v2f x) {
   else return v2f{__builtin_fmaf(v, x.x, acc.x), __builtin_fmaf(v, x.y, acc.y)};
 }
 
-template <int MMAX, bool EXACT, typename T>
+// wtab (WSRC): TAL_CLIQUE_WWORDS floats per block beside the table's record, else unused (null)
+template <int MMAX, bool EXACT, typename T, bool WSRC = false>
 __global__ __launch_bounds__(kBlock) void k_round_clique(const T* __restrict__ pin, int64_t ld_in,
                                                          T* __restrict__ pout, int64_t ld_out,
-                                                         int64_t n2, const int32_t* __restrict__ table) {
+                                                         int64_t n2, const int32_t* __restrict__ table,
+                                                         const float* __restrict__ wtab) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_WORDS;
-  const int64_t c2 = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (c2 >= n2) return;
+  int64_t c2 = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if constexpr (WSRC) {
+    // no lane leaves: lane j's weight register is read by every lane (lane_value), so lane j
+    // must have run its load.  Lanes past the last column pair repeat it, stores included
+    // (the same bits to the same address).
+    c2 = c2 < n2 ? c2 : n2 - 1;
+  } else {
+    if (c2 >= n2) return;
+  }
   const int64_t e = 2 * c2;
   const int m = t[0];
-  const float w = __int_as_float(t[1]);
-  const float pad = EXACT ? -0.f : (__float_as_uint(w) >> 31 ? 0.f : -0.f);
+  const float w = WSRC ? 1.f : __int_as_float(t[1]);
+  const float pad = EXACT || WSRC ? -0.f : (__float_as_uint(w) >> 31 ? 0.f : -0.f);
+  const float* wt = nullptr;
+  float wv = 0.f;  // WSRC: lane j holds w_j
+  if constexpr (WSRC) {
+    wt = wtab + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_WWORDS;
+    wv = wt[threadIdx.x % kCliqueMax];
+  }
+  // source j's weight where a chain step multiplies (FMA); EXACT multiplies once, below
+  auto W = [&](int j) -> float {
+    if constexpr (WSRC && !EXACT) return lane_value(wv, j);
+    else return w;
+  };
   // every load is issued unconditionally (a padding slot re-reads member 0, an L2 hit) so all
   // MMAX loads are in flight before the first use; the padding value is selected afterwards
   v2f p[MMAX];
@@ -2288,23 +2330,35 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const T* __restrict__ p
     const v2f e0 = n_ext > 0 ? ld_row(xr[7]) : v2f{0.f, 0.f};
     const v2f e1 = n_ext > 1 ? ld_row(xr[8]) : v2f{0.f, 0.f};
     v2f xs = self_e >= 0 ? ld_row(self_e) : v2f{0.f, 0.f};
+    // WSRC: the row's own weights - lane j holds member position j's, then ext 0, ext 1, self
+    float xv = 0.f, v0 = v, v1 = v, vs = v;
+    if constexpr (WSRC) {
+      const float* xw = wt + kCliqueMax + q * kCliqueExtraW + opaque_zero();
+      xv = xw[threadIdx.x % kCliqueMax];
+      v0 = xw[kCliqueMax], v1 = xw[kCliqueMax + 1], vs = xw[kCliqueMax + 2];
+    }
+    auto V = [&](int j) -> float {
+      if constexpr (WSRC) return lane_value(xv, j);
+      else return v;
+    };
     v2f acc = v2f{-0.f, -0.f};
 #pragma unroll
     for (int j = 0; j <= MMAX; ++j) {
-      if (pos0 == j) acc = clique_xterm<T, EXACT>(acc, v, e0);
-      if (pos1 == j) acc = clique_xterm<T, EXACT>(acc, v, e1);
+      if (pos0 == j) acc = clique_xterm<T, EXACT>(acc, v0, e0);
+      if (pos1 == j) acc = clique_xterm<T, EXACT>(acc, v1, e1);
       if (j < MMAX) {
-        if (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u) acc = clique_xterm<T, EXACT>(acc, v, p[j]);
+        if (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u) acc = clique_xterm<T, EXACT>(acc, V(j), p[j]);
         if (self_m == j) xs = p[j];
       }
     }
-    acc = clique_xterm<T, EXACT>(acc, v, xs);
+    acc = clique_xterm<T, EXACT>(acc, vs, xs);
     Io<T>::st2(pout + static_cast<int64_t>(xr[0]) * ld_out, e, acc);
   }
 #pragma unroll
   for (int j = 0; j < MMAX; ++j) {
-    if constexpr (kIsBf16<T> && EXACT) p[j] = round_bf16x2(v2f{w, w} * p[j]);
-    else if constexpr (EXACT) p[j] = v2f{__fmul_rn(w, p[j].x), __fmul_rn(w, p[j].y)};
+    const float wj = WSRC ? lane_value(wv, j) : w;
+    if constexpr (kIsBf16<T> && EXACT) p[j] = round_bf16x2(v2f{wj, wj} * p[j]);
+    else if constexpr (EXACT) p[j] = v2f{__fmul_rn(wj, p[j].x), __fmul_rn(wj, p[j].y)};
     if (j >= m) p[j] = v2f{pad, pad};
   }
   // Rows four at a time: row r = ((S_r + p[r+1]) + ... + p[MMAX-1]) + p[r], S_{r+1} = S_r + p[r]
@@ -2322,7 +2376,7 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const T* __restrict__ p
     v2f sp[4];  // S_i .. S_{i+3}
     sp[0] = s;
 #pragma unroll
-    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], w, p[i + k - 1]);
+    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], W(i + k - 1), p[i + k - 1]);
     if (orow[0] >= 0 || orow[1] >= 0 || orow[2] >= 0 || orow[3] >= 0) {
       // heads: row i+k takes p[i+k+1 .. i+3] before the four chains run in step
       v2f a[4];
@@ -2330,77 +2384,123 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const T* __restrict__ p
       for (int k = 0; k < 4; ++k) {
         a[k] = sp[k];
 #pragma unroll
-        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], w, p[j]);
+        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], W(j), p[j]);
       }
       // the four chains as one 8-wide vector: each step is one IR operation (four packed adds
       // on natural register pairs), which the compiler can neither split into four loops nor
       // sink into the stores' branches
       v8f q = {a[0].x, a[0].y, a[1].x, a[1].y, a[2].x, a[2].y, a[3].x, a[3].y};
 #pragma unroll
-      for (int j = i + 4; j < MMAX; ++j) q = clique_term4<T, EXACT>(q, w, v8f{p[j].x, p[j].y, p[j].x, p[j].y,
-                                                                           p[j].x, p[j].y, p[j].x, p[j].y});
-      q = clique_term4<T, EXACT>(q, w, v8f{p[i].x, p[i].y, p[i + 1].x, p[i + 1].y, p[i + 2].x, p[i + 2].y,
-                                        p[i + 3].x, p[i + 3].y});
+      for (int j = i + 4; j < MMAX; ++j) q = clique_term4<T, EXACT>(q, W(j), v8f{p[j].x, p[j].y, p[j].x, p[j].y,
+                                                                              p[j].x, p[j].y, p[j].x, p[j].y});
+      const v8f own = {p[i].x, p[i].y, p[i + 1].x, p[i + 1].y, p[i + 2].x, p[i + 2].y, p[i + 3].x, p[i + 3].y};
+      if constexpr (WSRC) q = clique_term4<T, EXACT>(q, W(i), W(i + 1), W(i + 2), W(i + 3), own);
+      else q = clique_term4<T, EXACT>(q, w, own);
 #pragma unroll
       for (int k = 0; k < 4; ++k) a[k] = v2f{q[2 * k], q[2 * k + 1]};
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (orow[k] >= 0) Io<T>::st2(pout + static_cast<int64_t>(orow[k]) * ld_out, e, a[k]);
     }
-    s = clique_term<T, EXACT>(sp[3], w, p[i + 3]);
+    s = clique_term<T, EXACT>(sp[3], W(i + 3), p[i + 3]);
   }
 }
 
 // The last column of an odd-width round: one thread per member row, its chain in reference
 // order (every other member ascending, then itself).
-template <bool EXACT, typename T>
-__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const T* __restrict__ pin, int64_t ld_in,
-                                                                  T* __restrict__ pout, int64_t ld_out,
-                                                                  int64_t e, const int32_t* __restrict__ table) {
+template <bool EXACT, typename T, bool WSRC>
+__device__ __forceinline__ void round_clique_tail_row(const T* __restrict__ pin, int64_t ld_in,
+                                                      T* __restrict__ pout, int64_t ld_out, int64_t e,
+                                                      const int32_t* __restrict__ table,
+                                                      const float* __restrict__ wtab) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
   const int m = t[0];
   const int i = threadIdx.x;
   if (i >= m) return;
   const int orow = t[4 + kCliqueMax + i];
   if (orow < 0) return;
-  const float w = __int_as_float(t[1]);
+  const float w = WSRC ? 1.f : __int_as_float(t[1]);
+  const float* wt = WSRC ? wtab + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WWORDS : nullptr;
   float acc = -0.f;
   for (int j = 0; j <= m; ++j) {
     if (j == i) continue;
     const int k = j < m ? j : i;
-    acc = next1t<T, EXACT>(acc, w, Io<T>::ld1(pin, static_cast<int64_t>(t[4 + k]) * ld_in + e));
+    acc = next1t<T, EXACT>(acc, WSRC ? wt[k] : w, Io<T>::ld1(pin, static_cast<int64_t>(t[4 + k]) * ld_in + e));
   }
   Io<T>::st1(pout, static_cast<int64_t>(orow) * ld_out + e, acc);
 }
 
+template <bool EXACT, typename T>
+__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const T* __restrict__ pin, int64_t ld_in,
+                                                                  T* __restrict__ pout, int64_t ld_out,
+                                                                  int64_t e, const int32_t* __restrict__ table) {
+  round_clique_tail_row<EXACT, T, false>(pin, ld_in, pout, ld_out, e, table, nullptr);
+}
+
+template <bool EXACT, typename T>
+__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail_w(const T* __restrict__ pin, int64_t ld_in,
+                                                                    T* __restrict__ pout, int64_t ld_out,
+                                                                    int64_t e, const int32_t* __restrict__ table,
+                                                                    const float* __restrict__ wtab) {
+  round_clique_tail_row<EXACT, T, true>(pin, ld_in, pout, ld_out, e, table, wtab);
+}
+
 // The last column for a block's attached rows: one thread per attached row.
+template <bool EXACT, typename T, bool WSRC>
+__device__ __forceinline__ void round_clique_tail_extra_row(const T* __restrict__ pin, int64_t ld_in,
+                                                            T* __restrict__ pout, int64_t ld_out, int64_t e,
+                                                            const int32_t* __restrict__ table,
+                                                            const float* __restrict__ wtab) {
+  const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
+  const int q = threadIdx.x;
+  if (q >= t[2]) return;
+  const int32_t* xr = t + 4 + 2 * kCliqueMax + q * kCliqueExtraWords;
+  const float v = WSRC ? 1.f : __int_as_float(xr[1]);
+  // WSRC: the row's weights {member position [64], ext [2], self}
+  const float* xw =
+      WSRC ? wtab + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WWORDS + kCliqueMax + q * kCliqueExtraW : nullptr;
+  const uint32_t lo = static_cast<uint32_t>(xr[2]), hi = static_cast<uint32_t>(xr[3]);
+  const int n_ext = xr[6];
+  auto x_of = [&](int r) { return Io<T>::ld1(pin, static_cast<int64_t>(r) * ld_in + e); };
+  auto term = [&](float a, int slot, float x) { return next1t<T, EXACT>(a, WSRC ? xw[slot] : v, x); };
+  float acc = -0.f;
+  for (int j = 0; j <= kCliqueMax; ++j) {
+    for (int k = 0; k < n_ext; ++k)
+      if (xr[9 + k] == j) acc = term(acc, kCliqueMax + k, x_of(xr[7 + k]));
+    if (j < kCliqueMax && (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u)) acc = term(acc, j, x_of(t[4 + j]));
+  }
+  acc = term(acc, kCliqueMax + 2, x_of(xr[4] >= 0 ? t[4 + xr[4]] : xr[5]));
+  Io<T>::st1(pout, static_cast<int64_t>(xr[0]) * ld_out + e, acc);
+}
+
 template <bool EXACT, typename T>
 __global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const T* __restrict__ pin,
                                                                           int64_t ld_in, T* __restrict__ pout,
                                                                           int64_t ld_out, int64_t e,
                                                                           const int32_t* __restrict__ table) {
-  const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
-  const int q = threadIdx.x;
-  if (q >= t[2]) return;
-  const int32_t* xr = t + 4 + 2 * kCliqueMax + q * kCliqueExtraWords;
-  const float v = __int_as_float(xr[1]);
-  const uint32_t lo = static_cast<uint32_t>(xr[2]), hi = static_cast<uint32_t>(xr[3]);
-  const int n_ext = xr[6];
-  auto x_of = [&](int r) { return Io<T>::ld1(pin, static_cast<int64_t>(r) * ld_in + e); };
-  auto term = [&](float a, float x) { return next1t<T, EXACT>(a, v, x); };
-  float acc = -0.f;
-  for (int j = 0; j <= kCliqueMax; ++j) {
-    for (int k = 0; k < n_ext; ++k)
-      if (xr[9 + k] == j) acc = term(acc, x_of(xr[7 + k]));
-    if (j < kCliqueMax && (((j < 32 ? lo >> j : hi >> (j - 32)) & 1u) != 0u)) acc = term(acc, x_of(t[4 + j]));
-  }
-  acc = term(acc, x_of(xr[4] >= 0 ? t[4 + xr[4]] : xr[5]));
-  Io<T>::st1(pout, static_cast<int64_t>(xr[0]) * ld_out + e, acc);
+  round_clique_tail_extra_row<EXACT, T, false>(pin, ld_in, pout, ld_out, e, table, nullptr);
 }
 
 template <bool EXACT, typename T>
+__global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra_w(const T* __restrict__ pin,
+                                                                            int64_t ld_in, T* __restrict__ pout,
+                                                                            int64_t ld_out, int64_t e,
+                                                                            const int32_t* __restrict__ table,
+                                                                            const float* __restrict__ wtab) {
+  round_clique_tail_extra_row<EXACT, T, true>(pin, ld_in, pout, ld_out, e, table, wtab);
+}
+
+template <int MMAX, bool EXACT, typename T, bool WSRC>
+void launch_clique_block(dim3 grid, const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n2,
+                         const int32_t* table, const float* wtab, hipStream_t s) {
+  k_round_clique<MMAX, EXACT, T, WSRC><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table, wtab);
+}
+
+// wtab: the per-source weight table (WSRC), else unused
+template <bool EXACT, typename T, bool WSRC>
 int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
-                            const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s) {
+                            const int32_t* table, const float* wtab, int32_t n_cliques, int32_t mmax,
+                            hipStream_t s) {
   const int64_t n2 = n / 2;
   const int64_t blocks = (n2 + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffffLL || n_cliques > 65535) return fail(TAL_ERR_INVALID, "clique round: grid too large");
@@ -2409,21 +2509,30 @@ int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
     // the chains run over MMAX slots, the ones past the largest clique adding -0.0: MMAX close
     // to the clique size keeps those no-op adds few (a 60-member barbell clique under MMAX 64
     // spent 13 % of its adds on padding)
-    if (mmax <= 16) k_round_clique<16, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 32) k_round_clique<32, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 40) k_round_clique<40, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 48) k_round_clique<48, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 56) k_round_clique<56, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else if (mmax <= 60) k_round_clique<60, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
-    else k_round_clique<64, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table);
+    auto go = [&](auto M) {
+      launch_clique_block<decltype(M)::value, EXACT, T, WSRC>(grid, pin, ld_in, pout, ld_out, n2, table, wtab, s);
+    };
+    if (mmax <= 16) go(std::integral_constant<int, 16>{});
+    else if (mmax <= 32) go(std::integral_constant<int, 32>{});
+    else if (mmax <= 40) go(std::integral_constant<int, 40>{});
+    else if (mmax <= 48) go(std::integral_constant<int, 48>{});
+    else if (mmax <= 56) go(std::integral_constant<int, 56>{});
+    else if (mmax <= 60) go(std::integral_constant<int, 60>{});
+    else go(std::integral_constant<int, 64>{});
     int32_t rc = check_launch("clique round kernel");
     if (rc) return rc;
   }
   if (n % 2) {
-    k_round_clique_tail<EXACT, T><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
+    if constexpr (WSRC)
+      k_round_clique_tail_w<EXACT, T><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table, wtab);
+    else k_round_clique_tail<EXACT, T><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
     int32_t rc = check_launch("clique round tail kernel");
     if (rc) return rc;
-    k_round_clique_tail_extra<EXACT, T><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
+    if constexpr (WSRC)
+      k_round_clique_tail_extra_w<EXACT, T><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table,
+                                                                             wtab);
+    else
+      k_round_clique_tail_extra<EXACT, T><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
     return check_launch("clique round tail kernel (attached rows)");
   }
   return TAL_OK;
@@ -5101,13 +5210,14 @@ int32_t agg_round(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, 
   return launch_round_scalar<T>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
 }
 
-// tal_agg_round_clique_<T>: a column pair is one 8-B (fp32) or 4-B (bf16) access, which sets the
-// alignment rule.
-template <typename T>
+// tal_agg_round_clique_<T> and tal_agg_round_clique_w_<T> (WSRC: per-source weights from
+// wtab_dev): a column pair is one 8-B (fp32) or 4-B (bf16) access, which sets the alignment rule.
+template <typename T, bool WSRC = false>
 int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
-                         const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream) {
+                         const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
+                         const float* wtab_dev = nullptr) {
   const std::string name(fn);
-  if (!pool_in || !pool_out || !table_dev) return fail(TAL_ERR_INVALID, name + ": null pointer");
+  if (!pool_in || !pool_out || !table_dev || (WSRC && !wtab_dev)) return fail(TAL_ERR_INVALID, name + ": null pointer");
   if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
   if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
   if (n_cliques < 0 || mmax < 1 || mmax > kCliqueMax)
@@ -5118,8 +5228,10 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
   if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   return mode == TAL_MODE_EXACT
-             ? launch_round_clique<true, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s)
-             : launch_round_clique<false, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s);
+             ? launch_round_clique<true, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
+                                                  mmax, s)
+             : launch_round_clique<false, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
+                                                   mmax, s);
 }
 
 }  // namespace
@@ -5223,6 +5335,20 @@ int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16
                                   int32_t mode, void* stream) {
   return agg_round_clique<uint16_t>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n, table_dev,
                                     n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                   int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                   int32_t mode, void* stream, const float* wtab_dev) {
+  return agg_round_clique<float, true>("tal_agg_round_clique_w_f32", pool_in, ld_in, pool_out, ld_out, n, table_dev,
+                                       n_cliques, mmax, mode, stream, wtab_dev);
+}
+
+int32_t tal_agg_round_clique_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                    int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                    int32_t mode, void* stream, const float* wtab_dev) {
+  return agg_round_clique<uint16_t, true>("tal_agg_round_clique_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                          table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_reg(const void* pool_in, int64_t ld_in, void* pool_out, int64_t ld_out, int64_t n,

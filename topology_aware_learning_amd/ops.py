@@ -351,51 +351,75 @@ CLIQUE_EXTRA_WORDS = 12
 CLIQUE_WORDS = 4 + 2 * CLIQUE_MAX + CLIQUE_EXTRA * CLIQUE_EXTRA_WORDS  # TAL_CLIQUE_WORDS (180)
 CLIQUE_MIN_ROWS = 8       # smaller blocks stay in the regular plan
 CLIQUE_MIN_SHARED = 8     # an attached row takes at least this many operands from the block
+# (bf16, mode): whether default_plan takes the per-source clique plan where the round has such
+# blocks and no uniform ones: where it beat the earlier default by more than tune_plan's margin on
+# both measured config-4 rounds (default_plan's docstring; profiles/r13) - all four
+WCLIQUE_DEFAULT = {(False, MODE_EXACT): True, (False, MODE_FMA): True,
+                   (True, MODE_EXACT): True, (True, MODE_FMA): True}
 
 
-def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS):
+def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_source: bool = False):
     """Uniform-weight clique blocks of a round (the K3c kernel's rows, tal_agg.h): rows whose
     operands are strictly ascending sources and then their own model (not among them), all with
     one finite fp32 weight, grouped by (operand set, weight); a group of >= min_rows rows with
     distinct own models and <= 64 sources is a clique block.  Other such rows that take at
     least CLIQUE_MIN_SHARED neighbors from a block and have at most two more are attached to it
     (up to CLIQUE_EXTRA per block).  Returns (cliques, rest): cliques = [(sources ascending, fp32
-    weight, {member index: out_row}, [attached row records])], rest = the other row indices."""
+    weight, {member index: out_row}, [attached row records])], rest = the other row indices.
+
+    per_source: blocks with one weight per source instead (the weighted and centrality apps on a
+    clique; tal_agg_round_clique_w_*).  Rows are in the same reference order with all-finite fp32
+    weights, grouped by operand set and by the fp32 bits every source carries: two rows share a
+    block only when each source has the same weight in both.  The second element of a block is
+    then the float32 array of its sources' weights, and an attached row's record carries its own
+    per-operand weights: wm = {member index: weight}, wext = [weights of ext], wself."""
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
+
+    def reference_row(r):
+        """(operands, fp32 weights) of row r when a block can carry it, else None."""
+        ops_ = col[row_ptr[r]: row_ptr[r + 1]]
+        if len(ops_) < 2:
+            return None
+        w32 = w[row_ptr[r]: row_ptr[r + 1]].astype(np.float32)
+        if per_source:
+            if not np.all(np.isfinite(w32)):
+                return None
+        elif not np.isfinite(w32[0]) or np.any(w32.view(np.uint32) != w32[:1].view(np.uint32)):
+            return None
+        nb, own = ops_[:-1], int(ops_[-1])
+        if np.any(np.diff(nb) <= 0) or own in nb:
+            return None
+        return ops_, w32
+
     groups: dict = {}
     for r in range(len(out_row)):
-        ops_ = col[row_ptr[r]: row_ptr[r + 1]]
-        m = len(ops_)
-        if m < 2 or m > CLIQUE_MAX:
+        row = reference_row(r)
+        if row is None or len(row[0]) > CLIQUE_MAX:
             continue
-        w32 = w[row_ptr[r]: row_ptr[r + 1]].astype(np.float32)
-        if not np.isfinite(w32[0]) or np.any(w32.view(np.uint32) != w32[:1].view(np.uint32)):
-            continue
-        rest, own = ops_[:-1], int(ops_[-1])
-        if np.any(np.diff(rest) <= 0) or own in rest:
-            continue
-        groups.setdefault((tuple(sorted(ops_.tolist())), int(w32[:1].view(np.uint32)[0])), []).append(r)
+        ops_, w32 = row
+        by_src = np.argsort(ops_)
+        wkey = tuple(w32[by_src].view(np.uint32).tolist()) if per_source else int(w32[:1].view(np.uint32)[0])
+        groups.setdefault((tuple(ops_[by_src].tolist()), wkey), []).append(r)
     cliques, used = [], set()
     for (srcs, wbits), rows in groups.items():
         owns = [int(col[row_ptr[r + 1] - 1]) for r in rows]
         if len(rows) < min_rows or len(set(owns)) != len(rows):
             continue
         idx = {s: i for i, s in enumerate(srcs)}
-        cliques.append((list(srcs), np.array([wbits], np.uint32).view(np.float32)[0],
+        w32 = np.array(wbits if per_source else [wbits], np.uint32).view(np.float32)
+        cliques.append((list(srcs), w32 if per_source else w32[0],
                         {idx[o]: int(out_row[r]) for o, r in zip(owns, rows)}, []))
         used.update(rows)
-    # attached rows: uniform-weight rows in reference order that take most operands from one
-    # block (a barbell's bridge nodes) - at most two other neighbors, own model anywhere
+    # attached rows: rows in reference order that take most operands from one block (a barbell's
+    # bridge nodes) - at most two other neighbors, own model anywhere
     for r in range(len(out_row)):
         if r in used or not cliques:
             continue
-        ops_ = col[row_ptr[r]: row_ptr[r + 1]]
-        w32 = w[row_ptr[r]: row_ptr[r + 1]].astype(np.float32)
-        if len(ops_) < 2 or not np.isfinite(w32[0]) or np.any(w32.view(np.uint32) != w32[:1].view(np.uint32)):
+        row = reference_row(r)
+        if row is None:
             continue
+        ops_, w32 = row
         nb, own = ops_[:-1], int(ops_[-1])
-        if np.any(np.diff(nb) <= 0) or own in nb:
-            continue
         best = max(range(len(cliques)), key=lambda c: len(set(cliques[c][0]).intersection(nb.tolist())))
         srcs, _, _, att = cliques[best]
         idx = {s: i for i, s in enumerate(srcs)}
@@ -406,11 +430,19 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS):
         mask = 0
         for x in mem:
             mask |= 1 << idx[x]
-        att.append(dict(out=int(out_row[r]), w=w32[0], mask=mask, self_member=idx.get(own, -1),
-                        self_row=-1 if own in idx else own,
-                        ext=[(x, sum(1 for s_ in srcs if s_ < x)) for x in ext]))
+        rec = dict(out=int(out_row[r]), w=w32[0], mask=mask, self_member=idx.get(own, -1),
+                   self_row=-1 if own in idx else own,
+                   ext=[(x, sum(1 for s_ in srcs if s_ < x)) for x in ext])
+        if per_source:
+            w_of = {int(x): w32[k] for k, x in enumerate(nb)}
+            rec.update(wm={idx[x]: w_of[x] for x in mem}, wext=[w_of[x] for x in ext], wself=w32[-1])
+        att.append(rec)
         used.add(r)
     return cliques, [r for r in range(len(out_row)) if r not in used]
+
+
+CLIQUE_EXTRA_W = CLIQUE_MAX + 3                            # an attached row's weights: 64 member positions, 2 ext, self
+CLIQUE_WWORDS = CLIQUE_MAX + CLIQUE_EXTRA * CLIQUE_EXTRA_W  # TAL_CLIQUE_WWORDS (332)
 
 
 @dataclass
@@ -418,7 +450,8 @@ class CliquePlan:
     """A round split into clique blocks (K3c, one launch) and the remaining rows (a regular
     RoundPlan, None if there are none).  The clique kernel takes fp32 and bf16 pools; `full` is a
     sparse plan over all rows, used for the int64 segment and for pools that miss K3c's
-    column-pair alignment (8 B fp32, 4 B bf16, even row stride)."""
+    column-pair alignment (8 B fp32, 4 B bf16, even row stride).  `wtable` (per-source blocks:
+    CLIQUE_WWORDS float32 per block, tal_agg.h) selects the tal_agg_round_clique_w_* entries."""
     table: np.ndarray
     n_cliques: int
     mmax: int
@@ -432,6 +465,8 @@ class CliquePlan:
     tuned_ms: Optional[float] = None
     candidates: Optional[list] = None
     spec: Optional[dict] = None
+    wtable: Optional[np.ndarray] = None
+    wdevice: Optional[torch.Tensor] = None
 
     @property
     def info(self) -> RoundPlanInfo:
@@ -441,12 +476,19 @@ class CliquePlan:
     def single_group(self) -> bool:
         return False  # clique blocks read other blocks' sources: never in place
 
+    @property
+    def spec_key(self) -> str:
+        """The plan's name in a spec: "wclique" with per-source weights, else "clique"."""
+        return "wclique" if self.wtable is not None else "clique"
+
     def staged_rows(self) -> int:
         """Source rows read from HBM per column (clique sources + the rest plan's)."""
         return self.clique_sources + (self.rest.staged_rows() if self.rest is not None else 0)
 
     def to(self, device) -> "CliquePlan":
         self.device = torch.from_numpy(self.table).to(device)
+        if self.wtable is not None:
+            self.wdevice = torch.from_numpy(self.wtable).to(device)
         if self.rest is not None:
             self.rest.to(device)
         self.full.to(device)
@@ -454,19 +496,26 @@ class CliquePlan:
 
 
 def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
-                      rest_spec: Optional[dict] = None, bf16: bool = False) -> Optional[CliquePlan]:
+                      rest_spec: Optional[dict] = None, bf16: bool = False,
+                      per_source: bool = False) -> Optional[CliquePlan]:
     """CliquePlan of a round, or None when it has no clique block (find_cliques).  bf16: the
     plan runs on bf16 pools, so its rest plan must be a form tal_agg_round_bf16 takes (sparse or
-    narrow: dense_rb 0, stream_cs 0); a rest_spec that asks for another form is a ValueError."""
+    narrow: dense_rb 0, stream_cs 0); a rest_spec that asks for another form is a ValueError.
+    per_source: blocks with one weight per source (find_cliques(per_source=True)); the plan then
+    carries `wtable`, and the table's two weight words stay 0."""
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
-    cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows)
+    cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows, per_source=per_source)
     if not cliques:
         return None
     table = np.zeros((len(cliques), CLIQUE_WORDS), np.int32)
+    wtable = np.ones((len(cliques), CLIQUE_WWORDS), np.float32) if per_source else None
     n_ext_loads = 0
     for k, (srcs, w32, outs, att) in enumerate(cliques):
         table[k, 0] = len(srcs)
-        table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
+        if per_source:
+            wtable[k, : len(srcs)] = w32
+        else:
+            table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
         table[k, 2] = len(att)
         table[k, 4: 4 + len(srcs)] = srcs
         table[k, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX] = -1
@@ -475,7 +524,14 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
         for q, a in enumerate(att):
             rec = table[k, 4 + 2 * CLIQUE_MAX + q * CLIQUE_EXTRA_WORDS:][:CLIQUE_EXTRA_WORDS]
             rec[0] = a["out"]
-            rec[1] = np.array([a["w"]], np.float32).view(np.int32)[0]
+            if per_source:
+                wrec = wtable[k, CLIQUE_MAX + q * CLIQUE_EXTRA_W:][:CLIQUE_EXTRA_W]
+                for i, v in a["wm"].items():
+                    wrec[i] = v
+                wrec[CLIQUE_MAX: CLIQUE_MAX + len(a["wext"])] = a["wext"]
+                wrec[CLIQUE_MAX + 2] = a["wself"]
+            else:
+                rec[1] = np.array([a["w"]], np.float32).view(np.int32)[0]
             rec[2:4] = np.array([a["mask"] & 0xFFFFFFFF, a["mask"] >> 32], np.uint32).view(np.int32)
             rec[4], rec[5], rec[6] = a["self_member"], a["self_row"], len(a["ext"])
             for e_, (row, pos) in enumerate(a["ext"]):
@@ -491,7 +547,8 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
     return CliquePlan(table=table.reshape(-1), n_cliques=len(cliques), mmax=mmax,
                       clique_sources=sum(len(c[0]) for c in cliques) + n_ext_loads,
                       clique_rows=sum(len(c[2]) + len(c[3]) for c in cliques), rest=rest_plan,
-                      full=build_plan(row_ptr, col, w, out_row, dense=0), rows=len(out_row), rest_rows=rest)
+                      full=build_plan(row_ptr, col, w, out_row, dense=0), rows=len(out_row), rest_rows=rest,
+                      wtable=wtable.reshape(-1) if per_source else None)
 
 
 REG_MAX_SRC = 64   # sources per register group (v[32:160): 64 x 2 fp32 per lane)
@@ -769,11 +826,19 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
         key = ("bcast", c4, waves, wg)
         if all(key != k for k, _ in cands) and p.spec != base.spec:
             cands.append((key, p))
-    if not isinstance(base, CliquePlan):
+    cp = base if isinstance(base, CliquePlan) else None
+    if cp is None:
         cp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16)
         if cp is not None:
             cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
             cands.append((("clique",), cp))
+    if cp is None or cp.wtable is None:
+        # per-source blocks (weighted / centrality apps on cliques): offered when they take rows
+        # no uniform-weight plan of the round takes
+        wp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True)
+        if wp is not None and wp.clique_rows > (cp.clique_rows if cp is not None else 0):
+            wp.spec = dict(wclique=1, rest=wp.rest.spec if wp.rest is not None else None)
+            cands.append((("wclique",), wp))
     return cands
 
 
@@ -806,7 +871,7 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     if isinstance(base, CliquePlan) and base.rest is not None:  # the rows outside the cliques: tuned too
         r_rp, r_col, r_w, r_out = _sub_csr(row_ptr, col, w, out_row, base.rest_rows)
         base.rest = tune_plan(r_rp, r_col, r_w, r_out, pool_in, pool_out, n=n, reps=reps, mode=mode, margin=margin)
-        base.spec = dict(clique=1, rest=base.rest.spec)
+        base.spec = {base.spec_key: 1, "rest": base.rest.spec}
     if len(cands) == 1:
         return base.to(pool_in.device)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -841,8 +906,9 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
 def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
     """Rebuild a plan tune_plan chose (its `spec`): profiling runs then time the same plan
     without re-tuning."""
-    if spec.get("clique"):
-        p = build_clique_plan(row_ptr, col, w, out_row, rest_spec=spec.get("rest"))
+    if spec.get("clique") or spec.get("wclique"):
+        p = build_clique_plan(row_ptr, col, w, out_row, rest_spec=spec.get("rest"),
+                              per_source=not spec.get("clique"))
         if p is None:
             raise ValueError("plan spec asks for clique blocks but the round has none")
         p.spec = dict(spec)
@@ -875,7 +941,16 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     took 7.38 ms against 19.05 in EXACT mode and 6.11 against 8.48 in FMA mode, and the complete
     graph of 64 (`unweighted_fl`, CIFAR-CNN width) 0.869 against 5.23 and 0.729 against 2.26; each
     is past tune_plan's 1 % margin and the forms agree bit for bit (block sizes other than 60
-    and 64 were not timed on bf16; they follow the fp32 rule).  One exception, from
+    and 64 were not timed on bf16; they follow the fp32 rule).  A round without uniform blocks
+    whose clique rows carry one weight per source (`weighted_module_avg`, `centrality_module_avg`
+    on a barbell or a complete graph) takes the per-source clique plan (K3c with per-source
+    weights, spec {"wclique": 1}) for fp32 and bf16 in both modes (WCLIQUE_DEFAULT): against the
+    sparse c4 = 128 plan this function returned before (medians of 20 interleaved runs,
+    tools/clique_weighted_rate.py, profiles/r13) config 4 under degree-centrality softmax /
+    data-size weights took, fp32 EXACT 4.54 / 4.60 ms against 11.42 / 11.48, fp32 FMA 4.66 / 4.66
+    against 9.46 / 9.47, bf16 EXACT 7.57 / 7.55 against 19.13 / 19.14, bf16 FMA 7.89 / 7.88 against
+    8.65 / 8.66 (the closest: 9 %), each past tune_plan's 1 % margin on both rounds, the forms
+    agreeing bit for bit; a round that has uniform blocks keeps exactly the plan above.  One exception, from
     round 4's measurements: a round whose narrow plan needs per-operand weights (the pairs
     form: centrality weights on a graph whose degrees differ) runs the narrow kernel's
     broadcast form with the whole source set in one LDS tile — for bf16 in FMA mode the
@@ -895,6 +970,11 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
         if cp is not None:
             cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
             return cp
+        if WCLIQUE_DEFAULT[bool(bf16), int(mode)]:
+            wp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True)
+            if wp is not None:
+                wp.spec = dict(wclique=1, rest=wp.rest.spec if wp.rest is not None else None)
+                return wp
         p = build_plan(row_ptr, col, w, out_row, dense=0)
     except _lib.TalError as exc:
         if exc.code != _lib.TAL_ERR_CAPACITY:
@@ -975,6 +1055,7 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
 
 
 _CLIQUE_FN = {torch.float32: "tal_agg_round_clique_f32", torch.bfloat16: "tal_agg_round_clique_bf16"}
+_CLIQUE_W_FN = {torch.float32: "tal_agg_round_clique_w_f32", torch.bfloat16: "tal_agg_round_clique_w_bf16"}
 
 
 def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
@@ -986,7 +1067,7 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
         raise ValueError("pools on different devices")
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("a clique round runs out of place (snapshot semantics)")
-    if plan.device is None or plan.device.device != pool_in.device:
+    if plan.device is None or plan.device.device != pool_in.device or (plan.wtable is not None and plan.wdevice is None):
         plan.to(pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
     pair = 2 * pool_in.element_size()
@@ -1001,10 +1082,13 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
     if max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(), att[used][:, 0].max(initial=-1)) >= pool_out.shape[0]:
         raise ValueError("plan writes a pool row beyond pool_out")
     L = _lib.load()
-    check(getattr(L, _CLIQUE_FN[dtype])(ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0),
-                                        ctypes.c_void_p(pool_out.data_ptr()), pool_out.stride(0), n,
-                                        ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax,
-                                        int(mode), _stream(pool_in.device, stream)))
+    args = (ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
+            pool_out.stride(0), n, ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax, int(mode),
+            _stream(pool_in.device, stream))
+    if plan.wtable is not None:  # per-source weights
+        check(getattr(L, _CLIQUE_W_FN[dtype])(*args, ctypes.c_void_p(plan.wdevice.data_ptr())))
+    else:
+        check(getattr(L, _CLIQUE_FN[dtype])(*args))
     if plan.rest is not None:
         _round(pool_in, pool_out, plan.rest, n, dtype, mode, stream)
     return pool_out
