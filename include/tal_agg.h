@@ -306,6 +306,34 @@ int32_t tal_agg_round_clique_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint
                                     int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
                                     const float* wtab_dev);
 
+/* Clique rounds for blocks of up to 128 members (K3c1, ABI 32): uniform-weight blocks as above,
+ * one element column per lane instead of a column pair, so the 128 product registers of a lane
+ * hold up to 128 members (`unweighted_fl` over 66 or 100 clients is one such block).  The
+ * arithmetic is the entries' above per column and per mode (EXACT: p_j = fl(w * x_j), on bf16
+ * rounded to bf16 as is every step of a chain; FMA: fma(w, x_j, acc) along the same chains from
+ * -0.0, bf16 rounded once at the store, NaN stored as 0xFFFF), each row its own in-order chain.
+ * table_dev: n_cliques records of TAL_CLIQUE_COL_WORDS int32
+ *   {m, bits of w, 0, 0, src_row[128], out_row[128]}
+ * (out_row -1: member without an output row) copied to the device; no attached rows and no
+ * per-source weights.  Blocks of any m <= 128 are legal (m <= 64 gives the bits of the entries
+ * above).  Any ld >= n and element-aligned pools (4 B fp32, 2 B bf16): there is no column-pair
+ * rule.  Out of place only.  TAL_ERR_INVALID, with no launch, for a null pointer, pool_out ==
+ * pool_in, mmax outside 1..TAL_CLIQUE_COL_MAX, n_cliques outside 0..65535 or ld < n.  mmax = the
+ * largest m (kernels for 68, 84, 100, 116 and 128 product registers per lane). */
+#define TAL_CLIQUE_COL_MAX 128
+#define TAL_CLIQUE_COL_WORDS 260
+#if defined(__cplusplus)
+static_assert(TAL_CLIQUE_COL_WORDS == 4 + 2 * TAL_CLIQUE_COL_MAX, "column-form record: header + 128 sources + 128 rows");
+#else
+_Static_assert(TAL_CLIQUE_COL_WORDS == 4 + 2 * TAL_CLIQUE_COL_MAX, "column-form record: header + 128 sources + 128 rows");
+#endif
+int32_t tal_agg_round_clique_col_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                     int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                     int32_t mode, void* stream);
+int32_t tal_agg_round_clique_col_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,
+                                      int64_t ld_out, int64_t n, const int32_t* table_dev,
+                                      int32_t n_cliques, int32_t mmax, int32_t mode, void* stream);
+
 /* The same round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or
  * streamed plans.  A staged tile holds the sources' values as fp32 (c4 float4 per source). */

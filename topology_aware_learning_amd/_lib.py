@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 EXPORTED = (
     "tal_last_error",
@@ -49,6 +49,8 @@ EXPORTED = (
     "tal_agg_round_clique_bf16",
     "tal_agg_round_clique_w_f32",
     "tal_agg_round_clique_w_bf16",
+    "tal_agg_round_clique_col_f32",
+    "tal_agg_round_clique_col_bf16",
     "tal_agg_round_reg",
     "tal_cosine_plan_words",
     "tal_cosine_plan_build",
@@ -192,6 +194,8 @@ _SIGS = {
     "tal_agg_round_clique_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_clique_w_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_agg_round_clique_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
+    "tal_agg_round_clique_col_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
+    "tal_agg_round_clique_col_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_reg": (_I32, [_P, _I64, _P, _I64, _I64, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "tal_cosine_plan_words": (_I64, [_PI64, _I32]),
     "tal_cosine_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),

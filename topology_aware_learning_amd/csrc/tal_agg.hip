@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 31;
+constexpr int kAbiVersion = 32;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -2536,6 +2536,120 @@ int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
     return check_launch("clique round tail kernel (attached rows)");
   }
   return TAL_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K3c1: K3c for uniform-weight blocks of up to 128 members, one column per lane.  K3c's lane
+// keeps the products of a column pair (v2f p[64]: 128 VGPRs); 128 members of a pair would need
+// 256 for the products alone.  Here a lane keeps the MMAX <= 128 products of one column - the
+// same 128 product registers - and runs K3c's chains per column: row i = ((S_i + p_{i+1}) +
+// ... + p_{m-1}) + p_i, each row its own left-to-right chain, S_0 and the padding -0.0 (FMA: the
+// zero whose product with w is -0.0).  The products sit two to a register pair (p_{2k}, p_{2k+1})
+// so that a step of four rows is two packed operations whose second source broadcasts one half
+// of a pair (op_sel); as float p[MMAX] the compiler gave every product an aligned pair of its
+// own (2 MMAX registers: one wave per SIMD and scratch at MMAX 128).  One column per lane needs
+// no column-pair alignment: any ld, element-aligned pools, no odd-width tail.  No attached rows
+// and no per-source weights.
+// A kernel of its own: k_round_clique's body is built on column pairs throughout (ld2 / st2,
+// the 8-wide chain vector, the attached rows' pair arithmetic and the lane-held weights).
+// ------------------------------------------------------------------------------------------
+constexpr int kCliqueColMax = TAL_CLIQUE_COL_MAX;
+static_assert(4 + 2 * kCliqueColMax == TAL_CLIQUE_COL_WORDS, "column-form table layout");
+
+template <typename T, bool EXACT>
+__device__ __forceinline__ float clique_term(float acc, float w, float p) {
+  if constexpr (kIsBf16<T> && EXACT) return round_bf16(__fadd_rn(acc, p));
+  else if constexpr (EXACT) return __fadd_rn(acc, p);
+  else return __builtin_fmaf(w, p, acc);
+}
+
+// Four clique chains of one column stepped at once (lane k = chain k): one IR operation per step.
+template <typename T, bool EXACT>
+__device__ __forceinline__ v4f clique_term4(v4f acc, float w, v4f p) {
+  if constexpr (kIsBf16<T> && EXACT) {
+    const v4f s = acc + p;
+    return v4f{round_bf16(s[0]), round_bf16(s[1]), round_bf16(s[2]), round_bf16(s[3])};
+  } else if constexpr (EXACT) return acc + p;  // IEEE adds, one rounding each (-ffp-contract=off)
+  else return __builtin_elementwise_fma(v4f{w, w, w, w}, p, acc);
+}
+
+// Column e of every row of clique block `t` (TAL_CLIQUE_COL_WORDS record).
+template <int MMAX, bool EXACT, typename T>
+__global__ __launch_bounds__(kBlock) void k_round_clique_col(const T* __restrict__ pin, int64_t ld_in,
+                                                             T* __restrict__ pout, int64_t ld_out, int64_t n,
+                                                             const int32_t* __restrict__ table) {
+  static_assert(MMAX % 4 == 0 && MMAX <= kCliqueColMax, "rows are taken in fours");
+  const int32_t* t = table + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_COL_WORDS;
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (e >= n) return;
+  const int m = t[0];
+  const float w = __int_as_float(t[1]);
+  const float pad = EXACT ? -0.f : (__float_as_uint(w) >> 31 ? 0.f : -0.f);
+  // as k_round_clique: every load issued unconditionally (a padding slot re-reads member 0, an
+  // L2 hit), all MMAX in flight before the first use, in batches of 8
+  v2f pp[MMAX / 2];  // p_j = pp[j / 2][j % 2]
+  auto p = [&](int j) -> float { return pp[j >> 1][j & 1]; };
+#pragma unroll
+  for (int j = 0; j < MMAX; ++j) {
+    pp[j >> 1][j & 1] = Io<T>::ld1(pin + static_cast<int64_t>(t[4 + (j < m ? j : 0) + opaque_zero()]) * ld_in, e);
+    if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int j = 0; j < MMAX; ++j) {
+    if constexpr (kIsBf16<T> && EXACT) pp[j >> 1][j & 1] = round_bf16(__fmul_rn(w, p(j)));
+    else if constexpr (EXACT) pp[j >> 1][j & 1] = __fmul_rn(w, p(j));
+    if (j >= m) pp[j >> 1][j & 1] = pad;
+  }
+  // rows four at a time, the four independent chains as one 4-wide vector per step (the
+  // compiler can neither split them into four loops nor sink them into the stores' branches)
+  float s = -0.f;
+#pragma unroll
+  for (int i = 0; i < MMAX; i += 4) {
+    int orow[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) orow[k] = i + k < m ? t[4 + kCliqueColMax + i + k + opaque_zero()] : -1;  // wave-uniform
+    float sp[4];  // S_i .. S_{i+3}
+    sp[0] = s;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], w, p(i + k - 1));
+    if (orow[0] >= 0 || orow[1] >= 0 || orow[2] >= 0 || orow[3] >= 0) {
+      // heads: row i+k takes p(i+k+1 .. i+3) before the four chains run in step
+      float a[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        a[k] = sp[k];
+#pragma unroll
+        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], w, p(j));
+      }
+      v4f q = {a[0], a[1], a[2], a[3]};
+#pragma unroll
+      for (int j = i + 4; j < MMAX; ++j) q = clique_term4<T, EXACT>(q, w, v4f{p(j), p(j), p(j), p(j)});
+      q = clique_term4<T, EXACT>(q, w, v4f{p(i), p(i + 1), p(i + 2), p(i + 3)});
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (orow[k] >= 0) Io<T>::st1(pout + static_cast<int64_t>(orow[k]) * ld_out, e, q[k]);
+    }
+    s = clique_term<T, EXACT>(sp[3], w, p(i + 3));
+  }
+}
+
+template <bool EXACT, typename T>
+int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
+                                const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s) {
+  const int64_t blocks = (n + kBlock - 1) / kBlock;
+  if (blocks > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "clique round (one column per lane): grid too large");
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_cliques));
+  // MMAX close to the block size keeps the -0.0 padding steps few: 68 for the reference's 66
+  // clients, 100 for its 100
+  auto go = [&](auto M) {
+    k_round_clique_col<decltype(M)::value, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n, table);
+  };
+  if (mmax <= 68) go(std::integral_constant<int, 68>{});
+  else if (mmax <= 84) go(std::integral_constant<int, 84>{});
+  else if (mmax <= 100) go(std::integral_constant<int, 100>{});
+  else if (mmax <= 116) go(std::integral_constant<int, 116>{});
+  else go(std::integral_constant<int, 128>{});
+  return check_launch("clique round kernel (one column per lane)");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -5234,6 +5348,23 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
                                                    mmax, s);
 }
 
+// tal_agg_round_clique_col_<T>: K3c1, one column per lane - any ld, element-aligned pools.
+template <typename T>
+int32_t agg_round_clique_col(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
+                             const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream) {
+  const std::string name(fn);
+  if (!pool_in || !pool_out || !table_dev) return fail(TAL_ERR_INVALID, name + ": null pointer");
+  if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
+  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
+  if (n_cliques < 0 || n_cliques > 65535 || mmax < 1 || mmax > kCliqueColMax)
+    return fail(TAL_ERR_INVALID, name + ": 0 <= n_cliques <= 65535, 1 <= mmax <= 128");
+  if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return mode == TAL_MODE_EXACT
+             ? launch_round_clique_col<true, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s)
+             : launch_round_clique_col<false, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -5335,6 +5466,20 @@ int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16
                                   int32_t mode, void* stream) {
   return agg_round_clique<uint16_t>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n, table_dev,
                                     n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_col_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                     int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                     int32_t mode, void* stream) {
+  return agg_round_clique_col<float>("tal_agg_round_clique_col_f32", pool_in, ld_in, pool_out, ld_out, n, table_dev,
+                                     n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_col_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                      int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                      int32_t mode, void* stream) {
+  return agg_round_clique_col<uint16_t>("tal_agg_round_clique_col_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                        table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,

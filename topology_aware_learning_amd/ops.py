@@ -356,9 +356,17 @@ CLIQUE_MIN_SHARED = 8     # an attached row takes at least this many operands fr
 # both measured config-4 rounds (default_plan's docstring; profiles/r13) - all four
 WCLIQUE_DEFAULT = {(False, MODE_EXACT): True, (False, MODE_FMA): True,
                    (True, MODE_EXACT): True, (True, MODE_FMA): True}
+CLIQUE_COL_MAX = 128      # TAL_CLIQUE_COL_MAX: members of a block of the one-column-per-lane form (K3c1)
+CLIQUE_COL_WORDS = 4 + 2 * CLIQUE_COL_MAX  # TAL_CLIQUE_COL_WORDS (260)
+# (bf16, mode): whether default_plan admits blocks of 65..128 members (K3c1): where the 128-member
+# plan beat the earlier default by more than tune_plan's margin on both the 66- and the
+# 100-client round (default_plan's docstring; profiles/r14) - all four, by 2.5x to 5.1x
+CLIQUE_COL_DEFAULT = {(False, MODE_EXACT): True, (False, MODE_FMA): True,
+                      (True, MODE_EXACT): True, (True, MODE_FMA): True}
 
 
-def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_source: bool = False):
+def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_source: bool = False,
+                 max_members: int = CLIQUE_MAX):
     """Uniform-weight clique blocks of a round (the K3c kernel's rows, tal_agg.h): rows whose
     operands are strictly ascending sources and then their own model (not among them), all with
     one finite fp32 weight, grouped by (operand set, weight); a group of >= min_rows rows with
@@ -372,7 +380,15 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_
     weights, grouped by operand set and by the fp32 bits every source carries: two rows share a
     block only when each source has the same weight in both.  The second element of a block is
     then the float32 array of its sources' weights, and an attached row's record carries its own
-    per-operand weights: wm = {member index: weight}, wext = [weights of ext], wself."""
+    per-operand weights: wm = {member index: weight}, wext = [weights of ext], wself.
+
+    max_members: the largest block, 64 (K3c) or up to 128: uniform-weight blocks of 65..128
+    sources run the one-column-per-lane form (K3c1, tal_agg_round_clique_col_*), which has no
+    attached rows - rows beside such a block stay in rest - and no per-source weights."""
+    if max_members > CLIQUE_COL_MAX:
+        raise ValueError(f"clique blocks have at most {CLIQUE_COL_MAX} members")
+    if per_source and max_members > CLIQUE_MAX:
+        raise ValueError(f"per-source clique blocks have at most {CLIQUE_MAX} members")
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
 
     def reference_row(r):
@@ -394,7 +410,7 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_
     groups: dict = {}
     for r in range(len(out_row)):
         row = reference_row(r)
-        if row is None or len(row[0]) > CLIQUE_MAX:
+        if row is None or len(row[0]) > max_members:
             continue
         ops_, w32 = row
         by_src = np.argsort(ops_)
@@ -411,16 +427,17 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_
                         {idx[o]: int(out_row[r]) for o, r in zip(owns, rows)}, []))
         used.update(rows)
     # attached rows: rows in reference order that take most operands from one block (a barbell's
-    # bridge nodes) - at most two other neighbors, own model anywhere
+    # bridge nodes) - at most two other neighbors, own model anywhere; K3c blocks only
+    attachable = [c for c in range(len(cliques)) if len(cliques[c][0]) <= CLIQUE_MAX]
     for r in range(len(out_row)):
-        if r in used or not cliques:
+        if r in used or not attachable:
             continue
         row = reference_row(r)
         if row is None:
             continue
         ops_, w32 = row
         nb, own = ops_[:-1], int(ops_[-1])
-        best = max(range(len(cliques)), key=lambda c: len(set(cliques[c][0]).intersection(nb.tolist())))
+        best = max(attachable, key=lambda c: len(set(cliques[c][0]).intersection(nb.tolist())))
         srcs, _, _, att = cliques[best]
         idx = {s: i for i, s in enumerate(srcs)}
         mem = [int(x) for x in nb if int(x) in idx]
@@ -451,7 +468,10 @@ class CliquePlan:
     RoundPlan, None if there are none).  The clique kernel takes fp32 and bf16 pools; `full` is a
     sparse plan over all rows, used for the int64 segment and for pools that miss K3c's
     column-pair alignment (8 B fp32, 4 B bf16, even row stride).  `wtable` (per-source blocks:
-    CLIQUE_WWORDS float32 per block, tal_agg.h) selects the tal_agg_round_clique_w_* entries."""
+    CLIQUE_WWORDS float32 per block, tal_agg.h) selects the tal_agg_round_clique_w_* entries.
+    Blocks of 65..128 members (build_clique_plan(max_members=128)) are `col_table`: n_col records
+    of CLIQUE_COL_WORDS for K3c1 (tal_agg_round_clique_col_*, one column per lane: no alignment
+    rule), launched after the K3c blocks of `table`; clique_sources and clique_rows count both."""
     table: np.ndarray
     n_cliques: int
     mmax: int
@@ -467,6 +487,10 @@ class CliquePlan:
     spec: Optional[dict] = None
     wtable: Optional[np.ndarray] = None
     wdevice: Optional[torch.Tensor] = None
+    col_table: Optional[np.ndarray] = None
+    n_col: int = 0
+    col_mmax: int = 0
+    col_device: Optional[torch.Tensor] = None
 
     @property
     def info(self) -> RoundPlanInfo:
@@ -489,6 +513,8 @@ class CliquePlan:
         self.device = torch.from_numpy(self.table).to(device)
         if self.wtable is not None:
             self.wdevice = torch.from_numpy(self.wtable).to(device)
+        if self.col_table is not None:
+            self.col_device = torch.from_numpy(self.col_table).to(device)
         if self.rest is not None:
             self.rest.to(device)
         self.full.to(device)
@@ -497,16 +523,29 @@ class CliquePlan:
 
 def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
                       rest_spec: Optional[dict] = None, bf16: bool = False,
-                      per_source: bool = False) -> Optional[CliquePlan]:
+                      per_source: bool = False, max_members: int = CLIQUE_MAX) -> Optional[CliquePlan]:
     """CliquePlan of a round, or None when it has no clique block (find_cliques).  bf16: the
     plan runs on bf16 pools, so its rest plan must be a form tal_agg_round_bf16 takes (sparse or
     narrow: dense_rb 0, stream_cs 0); a rest_spec that asks for another form is a ValueError.
     per_source: blocks with one weight per source (find_cliques(per_source=True)); the plan then
-    carries `wtable`, and the table's two weight words stay 0."""
+    carries `wtable`, and the table's two weight words stay 0.
+    max_members (find_cliques): up to 128 admits uniform-weight blocks of 65..128 sources, which
+    go to `col_table` (K3c1); blocks of <= 64 stay in `table` with their attached rows."""
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
-    cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows, per_source=per_source)
+    cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows, per_source=per_source,
+                                 max_members=max_members)
     if not cliques:
         return None
+    wide = [c for c in cliques if len(c[0]) > CLIQUE_MAX]
+    cliques = [c for c in cliques if len(c[0]) <= CLIQUE_MAX]
+    col_table = np.zeros((len(wide), CLIQUE_COL_WORDS), np.int32) if wide else None
+    for k, (srcs, w32, outs, _) in enumerate(wide):
+        col_table[k, 0] = len(srcs)
+        col_table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
+        col_table[k, 4: 4 + len(srcs)] = srcs
+        col_table[k, 4 + CLIQUE_COL_MAX:] = -1
+        for i, o in outs.items():
+            col_table[k, 4 + CLIQUE_COL_MAX + i] = o
     table = np.zeros((len(cliques), CLIQUE_WORDS), np.int32)
     wtable = np.ones((len(cliques), CLIQUE_WWORDS), np.float32) if per_source else None
     n_ext_loads = 0
@@ -543,12 +582,14 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
         rest_plan = plan_from_spec(*sub, rest_spec) if rest_spec else build_plan(*sub)
         if bf16 and (not isinstance(rest_plan, RoundPlan) or rest_plan.info.dense_rb or rest_plan.info.stream_cs):
             raise ValueError("a bf16 clique plan's other rows take a sparse or narrow plan (dense_rb 0, stream_cs 0)")
-    mmax = max(len(c[0]) for c in cliques)
+    mmax = max((len(c[0]) for c in cliques), default=0)
     return CliquePlan(table=table.reshape(-1), n_cliques=len(cliques), mmax=mmax,
-                      clique_sources=sum(len(c[0]) for c in cliques) + n_ext_loads,
-                      clique_rows=sum(len(c[2]) + len(c[3]) for c in cliques), rest=rest_plan,
+                      clique_sources=sum(len(c[0]) for c in cliques + wide) + n_ext_loads,
+                      clique_rows=sum(len(c[2]) + len(c[3]) for c in cliques + wide), rest=rest_plan,
                       full=build_plan(row_ptr, col, w, out_row, dense=0), rows=len(out_row), rest_rows=rest,
-                      wtable=wtable.reshape(-1) if per_source else None)
+                      wtable=wtable.reshape(-1) if per_source else None,
+                      col_table=col_table.reshape(-1) if wide else None, n_col=len(wide),
+                      col_mmax=max((len(c[0]) for c in wide), default=0))
 
 
 REG_MAX_SRC = 64   # sources per register group (v[32:160): 64 x 2 fp32 per lane)
@@ -839,6 +880,12 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
         if wp is not None and wp.clique_rows > (cp.clique_rows if cp is not None else 0):
             wp.spec = dict(wclique=1, rest=wp.rest.spec if wp.rest is not None else None)
             cands.append((("wclique",), wp))
+    if cp is None or cp.n_col == 0:
+        # blocks of 65..128 members (K3c1): offered when they take rows the <= 64 plan does not
+        xp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, max_members=CLIQUE_COL_MAX)
+        if xp is not None and xp.n_col > 0 and xp.clique_rows > (cp.clique_rows if cp is not None and cp.wtable is None else 0):
+            xp.spec = dict(clique=1, members=CLIQUE_COL_MAX, rest=xp.rest.spec if xp.rest is not None else None)
+            cands.append((("clique128",), xp))
     return cands
 
 
@@ -871,7 +918,7 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     if isinstance(base, CliquePlan) and base.rest is not None:  # the rows outside the cliques: tuned too
         r_rp, r_col, r_w, r_out = _sub_csr(row_ptr, col, w, out_row, base.rest_rows)
         base.rest = tune_plan(r_rp, r_col, r_w, r_out, pool_in, pool_out, n=n, reps=reps, mode=mode, margin=margin)
-        base.spec = {base.spec_key: 1, "rest": base.rest.spec}
+        base.spec = {base.spec_key: 1, **({"members": CLIQUE_COL_MAX} if base.n_col else {}), "rest": base.rest.spec}
     if len(cands) == 1:
         return base.to(pool_in.device)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -908,7 +955,8 @@ def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
     without re-tuning."""
     if spec.get("clique") or spec.get("wclique"):
         p = build_clique_plan(row_ptr, col, w, out_row, rest_spec=spec.get("rest"),
-                              per_source=not spec.get("clique"))
+                              per_source=not spec.get("clique"),
+                              max_members=int(spec.get("members", CLIQUE_MAX)))  # "members": 128 admits K3c1 blocks
         if p is None:
             raise ValueError("plan spec asks for clique blocks but the round has none")
         p.spec = dict(spec)
@@ -950,7 +998,16 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     data-size weights took, fp32 EXACT 4.54 / 4.60 ms against 11.42 / 11.48, fp32 FMA 4.66 / 4.66
     against 9.46 / 9.47, bf16 EXACT 7.57 / 7.55 against 19.13 / 19.14, bf16 FMA 7.89 / 7.88 against
     8.65 / 8.66 (the closest: 9 %), each past tune_plan's 1 % margin on both rounds, the forms
-    agreeing bit for bit; a round that has uniform blocks keeps exactly the plan above.  One exception, from
+    agreeing bit for bit; a round that has uniform blocks keeps exactly the plan above.  A round with a
+    uniform-weight block of 65..128 members (`unweighted_fl` over 66 or 100 clients: one complete
+    graph) takes the 128-member clique plan (K3c1, one column per lane, spec {"clique": 1,
+    "members": 128}) for fp32 and bf16 in both modes (CLIQUE_COL_DEFAULT): against the sparse
+    plan this function returned before (medians of 20 interleaved runs, tools/clique_col_rate.py,
+    profiles/r14; complete 66 / complete 100 at CIFAR-CNN width) fp32 EXACT took 0.598 / 0.999 ms
+    against 2.235 / 3.276, fp32 FMA 0.603 / 0.985 against 1.828 / 2.654, bf16 EXACT 0.835 / 1.858
+    against 4.275 / 5.885, bf16 FMA 0.488 / 0.907 against 1.755 / 2.279 (the closest: 2.5x), each
+    past tune_plan's 1 % margin on both rounds, the forms agreeing bit for bit; rounds whose blocks
+    all have <= 64 members keep exactly the plans above.  One exception, from
     round 4's measurements: a round whose narrow plan needs per-operand weights (the pairs
     form: centrality weights on a graph whose degrees differ) runs the narrow kernel's
     broadcast form with the whole source set in one LDS tile — for bf16 in FMA mode the
@@ -966,6 +1023,11 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     bf16 pools the wide-row kernel - or, rows out of reference order, one K1 call per row
     (RowCallPlan)."""
     try:
+        if CLIQUE_COL_DEFAULT[bool(bf16), int(mode)]:
+            xp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, max_members=CLIQUE_COL_MAX)
+            if xp is not None and xp.n_col > 0:  # a round without such a block keeps the plan below
+                xp.spec = dict(clique=1, members=CLIQUE_COL_MAX, rest=xp.rest.spec if xp.rest is not None else None)
+                return xp
         cp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16)
         if cp is not None:
             cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
@@ -1015,7 +1077,7 @@ def round_kernel_name(plan, bf16: bool = False) -> str:
     info, asked from the library (tal_round_kernel_name: the function its launch dispatches on);
     clique plans name the K3c kernel (their rest rows run a second one)."""
     if isinstance(plan, CliquePlan):
-        return "k_round_clique"
+        return "k_round_clique" if plan.n_cliques > 0 else "k_round_clique_col"
     if isinstance(plan, RegPlan):
         return "k_round_reg"
     if isinstance(plan, RowCallPlan):
@@ -1056,6 +1118,7 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
 
 _CLIQUE_FN = {torch.float32: "tal_agg_round_clique_f32", torch.bfloat16: "tal_agg_round_clique_bf16"}
 _CLIQUE_W_FN = {torch.float32: "tal_agg_round_clique_w_f32", torch.bfloat16: "tal_agg_round_clique_w_bf16"}
+_CLIQUE_COL_FN = {torch.float32: "tal_agg_round_clique_col_f32", torch.bfloat16: "tal_agg_round_clique_col_bf16"}
 
 
 def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
@@ -1067,28 +1130,40 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
         raise ValueError("pools on different devices")
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("a clique round runs out of place (snapshot semantics)")
-    if plan.device is None or plan.device.device != pool_in.device or (plan.wtable is not None and plan.wdevice is None):
+    if (plan.device is None or plan.device.device != pool_in.device or (plan.wtable is not None and plan.wdevice is None)
+            or (plan.col_table is not None and plan.col_device is None)):
         plan.to(pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
     pair = 2 * pool_in.element_size()
-    if (pool_in.stride(0) | pool_out.stride(0)) % 2 or (pool_in.data_ptr() | pool_out.data_ptr()) % pair:
+    if plan.n_cliques > 0 and ((pool_in.stride(0) | pool_out.stride(0)) % 2
+                               or (pool_in.data_ptr() | pool_out.data_ptr()) % pair):
         # K3c reads and writes column pairs (8 B fp32, 4 B bf16): rows not aligned to one take the full plan
+        # (K3c1 has no such rule: a plan of 65..128-member blocks alone never gets here)
         return _round(pool_in, pool_out, plan.full, n, dtype, mode, stream)
     t = plan.table.reshape(plan.n_cliques, CLIQUE_WORDS)
     att = t[:, 4 + 2 * CLIQUE_MAX:].reshape(plan.n_cliques, CLIQUE_EXTRA, CLIQUE_EXTRA_WORDS)
     used = np.arange(CLIQUE_EXTRA)[None, :] < t[:, 2:3]  # attached records in use
-    if max(t[:, 4: 4 + CLIQUE_MAX].max(), att[used][:, [5, 7, 8]].max(initial=-1)) >= pool_in.shape[0]:
+    ct = (plan.col_table if plan.col_table is not None else np.zeros(0, np.int32)).reshape(plan.n_col, CLIQUE_COL_WORDS)
+    if max(t[:, 4: 4 + CLIQUE_MAX].max(initial=-1), att[used][:, [5, 7, 8]].max(initial=-1),
+           ct[:, 4: 4 + CLIQUE_COL_MAX].max(initial=-1)) >= pool_in.shape[0]:
         raise ValueError("plan reads a pool row beyond pool_in")
-    if max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(), att[used][:, 0].max(initial=-1)) >= pool_out.shape[0]:
+    if max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(initial=-1), att[used][:, 0].max(initial=-1),
+           ct[:, 4 + CLIQUE_COL_MAX:].max(initial=-1)) >= pool_out.shape[0]:
         raise ValueError("plan writes a pool row beyond pool_out")
     L = _lib.load()
-    args = (ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
-            pool_out.stride(0), n, ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax, int(mode),
+    head = (ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
+            pool_out.stride(0), n)
+    args = (*head, ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax, int(mode),
             _stream(pool_in.device, stream))
-    if plan.wtable is not None:  # per-source weights
+    if plan.n_cliques == 0:
+        pass  # blocks of 65..128 members only
+    elif plan.wtable is not None:  # per-source weights
         check(getattr(L, _CLIQUE_W_FN[dtype])(*args, ctypes.c_void_p(plan.wdevice.data_ptr())))
     else:
         check(getattr(L, _CLIQUE_FN[dtype])(*args))
+    if plan.n_col > 0:  # blocks of 65..128 members: K3c1
+        check(getattr(L, _CLIQUE_COL_FN[dtype])(*head, ctypes.c_void_p(plan.col_device.data_ptr()), plan.n_col,
+                                                plan.col_mmax, int(mode), _stream(pool_in.device, stream)))
     if plan.rest is not None:
         _round(pool_in, pool_out, plan.rest, n, dtype, mode, stream)
     return pool_out
@@ -1109,7 +1184,8 @@ def round_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n
     plans of at most 16 rows per group, the wide-row kernel; modes as agg_bf16).  A CliquePlan
     runs its clique blocks with K3c on bf16 (tal_agg_round_clique_bf16) and its other rows with
     their regular plan, out of place; pools that miss the 4-B column-pair alignment take
-    `plan.full`."""
+    `plan.full`.  Blocks of 65..128 members (`col_table`) run K3c1 (tal_agg_round_clique_col_bf16),
+    which has no alignment rule."""
     if isinstance(plan, CliquePlan):
         return _round_clique(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
     if isinstance(plan, RegPlan):
