@@ -30,7 +30,12 @@
  *   - weights arrive as float64 (Python floats / numpy float64 in the reference) and are
  *     rounded to fp32 exactly as torch does for `python_float * fp32_tensor`.
  *   - mode: TAL_MODE_EXACT reproduces the reference bit for bit (ordered i=0..M-1,
- *     separate fp32 multiply and add); TAL_MODE_FMA fuses them (tolerance M*2^-24*sum|w x|).
+ *     separate fp32 multiply and add).  TAL_MODE_FMA is one fused chain per element, in the same
+ *     operand order: acc = fl32(w_0 * x_0), then acc = fma(w_i, x_i, acc) for i = 1..M-1 - the
+ *     product is not rounded, each step rounds once, IEEE arithmetic with subnormals kept.  It
+ *     is as deterministic as EXACT mode: every fp32 entry point and kernel form gives the same
+ *     bits, pinned by the test oracle's oracle.agg_f32(exact=False) / round_f32(exact=False).
+ *     Its distance to EXACT mode is at most M*2^-24*sum|w x|.
  */
 #ifndef TAL_AGG_H
 #define TAL_AGG_H

@@ -9,7 +9,8 @@ Contents
                            reduction order (`cosine_model`, bitwise; decentralized_client.py:661-681)
   agg_oracle.c / Makefile  plain-C restatement of the reference arithmetic
                            (src/decentralized_client.py:399-413) — `agg_f32`, `agg_i64`,
-                           `round_f32`, `round_i64`, and for bf16 tensors `agg_bf16`,
+                           `round_f32`, `round_i64` (`exact=False`: the library's fp32 FMA
+                           mode, pinned by tests/test_oracle_fma.py), and for bf16 tensors `agg_bf16`,
                            `round_bf16` (uint16 bit patterns) below are its numpy wrappers
   reference_alg.py         numpy restatement of the host-side logic on the path: weight
                            vectors of every app, cosine similarity, round semantics
@@ -48,9 +49,11 @@ def lib() -> ctypes.CDLL:
         L = ctypes.CDLL(str(LIB))
         P = ctypes.c_void_p
         L.oracle_agg_f32.argtypes = [P, P, ctypes.c_int32, P, ctypes.c_int64]
+        L.oracle_agg_f32_fma.argtypes = [P, P, ctypes.c_int32, P, ctypes.c_int64]
         L.oracle_agg_i64.argtypes = [P, P, ctypes.c_int32, P, ctypes.c_int64]
         rargs = [P, ctypes.c_int64, P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, P, P, P, P]
         L.oracle_round_f32.argtypes = rargs
+        L.oracle_round_f32_fma.argtypes = rargs
         L.oracle_round_i64.argtypes = rargs
         L.oracle_agg_bf16.argtypes = [P, P, ctypes.c_int32, P, ctypes.c_int64, ctypes.c_int32]
         L.oracle_round_bf16.argtypes = rargs + [ctypes.c_int32]
@@ -73,12 +76,15 @@ def _ptrs(arrs):
     return a
 
 
-def agg_f32(xs, w) -> np.ndarray:
-    """One call, fp32 operands (list of equal-length 1-D arrays), float64 weights."""
+def agg_f32(xs, w, exact: bool = True) -> np.ndarray:
+    """One call, fp32 operands (list of equal-length 1-D arrays), float64 weights.  exact: the
+    reference's separate fp32 multiply and add; else the library's FMA mode, one fused chain
+    (acc = fl(w_0 * x_0), then acc = fma(w_i, x_i, acc) in operand order)."""
     xs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in xs]
     w = np.ascontiguousarray(w, dtype=np.float64)
     out = np.empty_like(xs[0])
-    lib().oracle_agg_f32(_ptrs(xs), w.ctypes.data, len(xs), out.ctypes.data, out.size)
+    fn = lib().oracle_agg_f32 if exact else lib().oracle_agg_f32_fma
+    fn(_ptrs(xs), w.ctypes.data, len(xs), out.ctypes.data, out.size)
     return out
 
 
@@ -101,12 +107,14 @@ def _round(fn, pool_in, row_ptr, col, w, out_row, pool_out):
     return pool_out
 
 
-def round_f32(pool_in, row_ptr, col, w, out_row, pool_out=None) -> np.ndarray:
-    """Snapshot round over a [models, n] fp32 pool (pool_out defaults to a copy of pool_in)."""
+def round_f32(pool_in, row_ptr, col, w, out_row, pool_out=None, exact: bool = True) -> np.ndarray:
+    """Snapshot round over a [models, n] fp32 pool (pool_out defaults to a copy of pool_in).
+    exact as agg_f32: False runs every row as the FMA mode's fused chain."""
     pool_in = np.ascontiguousarray(pool_in, dtype=np.float32)
     if pool_out is None:
         pool_out = pool_in.copy()
-    return _round(lib().oracle_round_f32, pool_in, row_ptr, col, w, out_row, pool_out)
+    fn = lib().oracle_round_f32 if exact else lib().oracle_round_f32_fma
+    return _round(fn, pool_in, row_ptr, col, w, out_row, pool_out)
 
 
 def round_i64(pool_in, row_ptr, col, w, out_row, pool_out=None) -> np.ndarray:

@@ -45,6 +45,18 @@ void oracle_agg_f32(const float* const* x, const double* w, int32_t m, float* ou
   }
 }
 
+/* The library's FMA mode (TAL_MODE_FMA) of the same call, which the reference does not have: one
+ * fused chain per element, acc = fl32(fl32(w_0) * x_0); acc = fma(fl32(w_i), x_i, acc) in
+ * operand order, IEEE arithmetic with subnormals kept.  glibc's fmaf is correctly rounded;
+ * tests/test_oracle_fma.py pins this function against exact rational arithmetic. */
+void oracle_agg_f32_fma(const float* const* x, const double* w, int32_t m, float* out, int64_t n) {
+  for (int64_t e = 0; e < n; ++e) {
+    float acc = (float)w[0] * x[0][e];
+    for (int32_t i = 1; i < m; ++i) acc = fmaf((float)w[i], x[i][e], acc);
+    out[e] = acc;
+  }
+}
+
 /* int64 buffers of the same call (num_batches_tracked): :407-413. */
 void oracle_agg_i64(const int64_t* const* x, const double* w, int32_t m, int64_t* out,
                     int64_t n) {
@@ -74,6 +86,22 @@ void oracle_round_f32(const float* pool_in, int64_t ld_in, float* pool_out, int6
         float p = (float)w[k] * pool_in[(int64_t)col[k] * ld_in + e];
         acc = acc + p;
       }
+      o[e] = acc;
+    }
+  }
+}
+
+/* The same round in the library's FMA mode: every row the fused chain of oracle_agg_f32_fma. */
+void oracle_round_f32_fma(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                          int64_t n, int32_t rows, const int32_t* row_ptr, const int32_t* col,
+                          const double* w, const int32_t* out_row) {
+  for (int32_t r = 0; r < rows; ++r) {
+    float* o = pool_out + (int64_t)out_row[r] * ld_out;
+    for (int64_t e = 0; e < n; ++e) {
+      int32_t k = row_ptr[r];
+      float acc = (float)w[k] * pool_in[(int64_t)col[k] * ld_in + e];
+      for (++k; k < row_ptr[r + 1]; ++k)
+        acc = fmaf((float)w[k], pool_in[(int64_t)col[k] * ld_in + e], acc);
       o[e] = acc;
     }
   }

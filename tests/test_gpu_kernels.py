@@ -1,6 +1,8 @@
 """GPU parity of the HIP kernels (through the C-ABI) against the C oracle.
 
-Bar: bit-exact in EXACT mode (fp32 and int64), M*2^-24*sum|w x| in FMA mode.
+Bar: bit-exact in EXACT mode (fp32 and int64), M*2^-24*sum|w x| from EXACT in FMA mode.  FMA mode's
+own bits (the fused chain, oracle.round_f32(exact=False)) are pinned form by form in
+tests/test_gpu_fma_f32.py and asserted here where a test runs the mode.
 """
 import hashlib
 import json
@@ -262,6 +264,8 @@ def test_round_narrow_vs_oracle(cuda, graph, n, c4, lds, pad):
     tol = m * 2.0 ** -24 * np.abs(np.where(np.isfinite(pool), pool, 0)).max() + 1e-30
     got = host(pout, n)
     assert np.max(np.abs(got[fin] - ref[fin])) <= tol
+    # and the mode's own definition, all bits: the fused chain of the oracle
+    assert _bits_equal(got, oracle.round_f32(pool, row_ptr, col, w, out_rows, exact=False))
     if plan.single_group:
         ops.round_f32(pin, pin, plan, n=n)
         assert _bits_equal(host(pin, n), ref)
@@ -430,7 +434,14 @@ def test_round_stream_large_and_fma(cuda):
     ops.round_f32(pin, pout, plan, mode=ops.MODE_FMA)
     m = max(len(o) for o in orders)
     tol = m * 2.0 ** -24 * np.abs(pool).max() * 1.0 + 1e-30
-    assert np.max(np.abs(pout.cpu().numpy() - ref)) <= tol
+    got = pout.cpu().numpy()
+    assert np.max(np.abs(got - ref)) <= tol
+    # and the mode's own definition, all bits, on the first, a middle and the last 4096 columns
+    # (the fused oracle over all 2^20 would take the CPU most of a minute)
+    for c0 in (0, n // 2 - 2048 + 4, n - 4096):
+        cols = slice(c0, c0 + 4096)
+        fused = oracle.round_f32(np.ascontiguousarray(pool[:, cols]), row_ptr, col, w, out_rows, exact=False)
+        assert _bits_equal(got[:, cols], fused), c0
 
 
 def test_round_stream_padded_ld_tail_unaligned_i64(cuda):
