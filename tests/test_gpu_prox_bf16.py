@@ -7,12 +7,13 @@ arithmetic on the widened rows rounded to bf16 once, at the store.
 
 Kernel level, through ctypes on flat bf16 rows with a plan of explicit (offset, length) segments
 that reach every position of a chunk's first element in its 8-byte group, every head and tail
-length and more than one chunk: the norms against float64 (relative 1e-5, the (f)3 bar; one
-lane's fp32 chain is at most 32 fmaf of non-negative terms plus one edge element, under 2e-6)
-and bit-identical on a second call; the gradient bit for bit the fp32 entry point's on the widened
-rows, converted to bf16 by torch, for 1, 8, 9 (past one 8-neighbor tile), 64 and 65 (past one
-launch: the fp32 running sum) neighbors; the same with rows that start 2 bytes into their
-buffers (the element-by-element path).
+length and more than one chunk: the norms against float64 (relative 1e-5, the (f)3 bar, and
+32 * 2^-24, what the arithmetic allows: one lane's fp32 chain is at most 38 fmaf of non-negative
+terms) and bit-identical on a second call; the gradient bit for bit the fp32 entry point's on the
+widened rows, converted to bf16 by torch, and bit for bit the header's chain restated in numpy
+(tests/_prox_oracle.py) rounded to bf16 once - so no error shared by the two kernels passes - for
+1, 8, 9 (past one 8-neighbor tile), 64 and 65 (past one launch: the fp32 running sum) neighbors;
+the same with rows that start 2 bytes into their buffers (the element-by-element path).
 Interface level: prox_term on bf16 pool-bound models against the torch loop on fp32 leaf copies,
 selective neighbor gradients, one local_train epoch, and the fp32 path's kind.
 """
@@ -26,6 +27,7 @@ import torch
 from torch.utils.data import Subset, TensorDataset
 
 from _models import TinyNet
+from _prox_oracle import grad_chain, to_bf16_bits
 from topology_aware_learning_amd import _lib
 from topology_aware_learning_amd.aggregate import layout_of_module
 from topology_aware_learning_amd.arena import ModelPool
@@ -154,6 +156,9 @@ def _check_norms(device, k, mis, wide=False):
     print(f"k={k} mis={mis} wide={wide}: largest relative norm error {err:.3e}")
     assert torch.isfinite(got).all()
     assert ((got - want).abs() <= 1e-5 * want).all()
+    # u = 2^-24: 2u on d^2 from the subtraction, a lane's chain of at most 38 fmaf of non-negative
+    # terms 38u, the sums in double, halved by the sqrt, u for the cast: 21u to first order
+    assert ((got - want).abs() <= 32 * 2.0 ** -24 * want).all()
     if k >= 2:
         assert (norms[1] == 0).all()  # the identical neighbor: exactly 0
 
@@ -207,6 +212,21 @@ def _check_grad(device, k, mis, wide=False):
     if k >= 2:  # the identical neighbor contributes exactly nothing
         assert (gwt[1].float()[inside] == 0).all()
     assert gw.float()[inside].abs().max() > 0 or k == 2
+    # and independently of the fp32 kernels: the header's chain restated in numpy on the widened
+    # rows (tests/_prox_oracle.py), rounded to bf16 once
+    host = wide_rows.cpu().numpy()
+    ref_gw, ref_gwt = grad_chain(host[0], list(host[1:]), SEGS, norms.cpu().numpy(), np.float32(SCALE), want_t)
+    inside_h = inside.cpu().numpy()
+
+    def same_bits(got, ref, what):
+        got_b = _bits(got).cpu().numpy().view(np.uint16)
+        bad = (got_b != to_bf16_bits(ref)) & inside_h
+        assert not bad.any(), (what, int(bad.sum()), int(bad.nonzero()[0][0]))
+
+    same_bits(gw, ref_gw, "gw against the oracle")
+    for t in range(k):
+        if gwt[t] is not None:
+            same_bits(gwt[t], ref_gwt[t], f"gwt[{t}] against the oracle")
 
 
 @pytest.mark.parametrize("k", KS)
