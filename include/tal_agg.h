@@ -512,7 +512,9 @@ int32_t tal_cosine_round_bf16(const uint16_t* pool, int64_t ld, const int64_t* p
  * tal_prox_grad: gw = s * sum_t (w - wt) / ||w - wt||_p and, for each non-null gwt_host[t],
  * gwt[t] = -s * (w - wt) / ||w - wt||_p, with 0 where a norm is 0 (torch's norm backward);
  * s = *scale_dev (the upstream gradient, read on the device).  Only the parameter segments
- * of gw / gwt are written. */
+ * of gw / gwt are written.
+ * All four passes (these two and the _bf16 pair below) check every argument, each of the k
+ * neighbor pointers included, before the first launch. */
 int64_t tal_prox_plan_words(const int64_t* seg_host, int32_t n_seg);
 int32_t tal_prox_plan_build(const int64_t* seg_host, int32_t n_seg, int64_t* plan_host,
                             int64_t plan_capacity_words, int32_t* n_chunks);
@@ -545,7 +547,8 @@ int32_t tal_prox_grad(const float* w, const float* const* wt_host, int32_t k,
  * Rows that are all 8-byte aligned (pool rows are) are read and written 8 bytes per lane, the up
  * to 3 elements before and after a chunk's whole 8-byte groups one by one; other rows go element
  * by element (the same gradient bit for bit; the norms by the same definition, summed in that
- * path's own fixed order). */
+ * path's own fixed order).  That element path is the one the fp32 entry points run: the kernels
+ * are one template over the storage type. */
 int32_t tal_prox_norms_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k,
                             const int64_t* plan_dev, int32_t n_chunks, int32_t n_seg,
                             void* scratch, float* norms_out, void* stream);

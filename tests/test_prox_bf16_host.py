@@ -1,8 +1,8 @@
 """The FedProx term of bf16 models, host side (no GPU): the chunk plan of a bf16 layout and its
 kind, the refusal of a model with parameters of both dtypes, the plan cache (an entry holds its
 layout, so a layout's id can never come back on another layout while its plan is cached) and
-the argument errors of tal_prox_norms_bf16 / tal_prox_grad_bf16 (include/tal_agg.h "K4 on bf16
-models").  The kernels are tested in tests/test_gpu_prox_bf16.py."""
+the argument errors of tal_prox_norms / tal_prox_grad and their _bf16 twins (include/tal_agg.h
+"K4 on bf16 models").  The kernels are tested in tests/test_gpu_prox_bf16.py."""
 import ctypes
 import gc
 import weakref
@@ -104,11 +104,21 @@ def test_argument_errors():
     def grad(w=ok, wt=one, k=1, acc=None, acc_elems=0):
         return L.tal_prox_grad_bf16(w, wt, k, ok, 1, 1, ok, ok, ok, None, acc, acc_elems, None)
 
-    for call in (norms, grad):
-        name = b"tal_prox_norms_bf16" if call is norms else b"tal_prox_grad_bf16"
+    def norms_f32(w=ok, wt=one, k=1):
+        return L.tal_prox_norms(w, wt, k, ok, 1, 1, ok, ok, None)
+
+    def grad_f32(w=ok, wt=one, k=1):
+        return L.tal_prox_grad(w, wt, k, ok, 1, 1, ok, ok, ok, None, None)
+
+    # a null neighbor in the second launch's batch: refused with the rest, before the first launch
+    late = (ctypes.c_void_p * 65)(*([0x2000] * 64 + [None]))
+    for call, name in ((norms, b"tal_prox_norms_bf16"), (grad, b"tal_prox_grad_bf16"),
+                       (norms_f32, b"tal_prox_norms"), (grad_f32, b"tal_prox_grad")):
         assert call(w=None) == E and name in L.tal_last_error()
         assert call(k=0) == E and name in L.tal_last_error()
         assert call(wt=null1) == E and name in L.tal_last_error() and b"null neighbor" in L.tal_last_error()
+        more = dict(acc=ok, acc_elems=1) if call is grad else {}  # the scratch is fine: the pointer is refused
+        assert call(wt=late, k=65, **more) == E and name in L.tal_last_error() and b"null neighbor" in L.tal_last_error()
     many = (ctypes.c_void_p * 65)(*([0x2000] * 65))
     assert grad(wt=many, k=65, acc=None) == E and b"tal_prox_grad_bf16" in L.tal_last_error()
     assert grad(wt=many, k=65, acc=ok, acc_elems=0) == E  # too small for the plan's one chunk

@@ -4228,15 +4228,17 @@ __global__ void k_cosr_gather(const int32_t* __restrict__ table, const float* __
 // ------------------------------------------------------------------------------------------
 // FedProx proximal term (reference tasks.py:277-286): prox = sum_t sum_p ||w_p - wt_p||_2 over
 // neighbors t and parameter tensors p, and its gradient.  The parameters are segments of the
-// flat fp32 pool rows.  Plan (int64): seg_chunk_ptr[n_seg+1], then per chunk {seg, begin, len}.
+// flat pool rows, fp32 or bf16 (ABI 29); bf16 values are widened exactly to fp32, and the
+// arithmetic is one.  Plan (int64): seg_chunk_ptr[n_seg+1], then per chunk {seg, begin, len}.
 // ------------------------------------------------------------------------------------------
 constexpr int kProxMaxNb = 64;             // neighbors per launch (more: host batches)
 constexpr int64_t kProxChunk = 8192;       // elements per workgroup chunk
 constexpr int kProxTile = 8;               // neighbors accumulated per pass over w
 
+template <typename T>
 struct ProxPtrs {
-  const float* wt[kProxMaxNb];
-  float* gwt[kProxMaxNb];
+  const T* wt[kProxMaxNb];
+  T* gwt[kProxMaxNb];
 };
 
 __device__ __forceinline__ double block_sum_f64(double v, double* s_red) {
@@ -4251,84 +4253,11 @@ __device__ __forceinline__ double block_sum_f64(double v, double* s_red) {
   return tot;
 }
 
-__global__ __launch_bounds__(kBlock) void k_prox_sumsq(const float* __restrict__ w, ProxPtrs pp, int k,
-                                                       const int64_t* __restrict__ plan, int n_seg,
-                                                       int n_chunks, double* __restrict__ partial) {
-  __shared__ double s_red[kBlock / 64];
-  const int c = blockIdx.x;
-  const int64_t* ch = plan + (n_seg + 1) + 3 * static_cast<int64_t>(c);
-  const int64_t beg = ch[1], len = ch[2];
-  for (int t0 = 0; t0 < k; t0 += kProxTile) {
-    const int nt = min(kProxTile, k - t0);
-    float acc[kProxTile];
-#pragma unroll
-    for (int j = 0; j < kProxTile; ++j) acc[j] = 0.f;
-    for (int64_t e = threadIdx.x; e < len; e += kBlock) {
-      const float wv = w[beg + e];
-#pragma unroll
-      for (int j = 0; j < kProxTile; ++j) {
-        if (j < nt) {
-          const float d = wv - pp.wt[t0 + j][beg + e];
-          acc[j] = fmaf(d, d, acc[j]);
-        }
-      }
-    }
-    for (int j = 0; j < nt; ++j) {
-      const double tot = block_sum_f64(static_cast<double>(acc[j]), s_red);
-      if (threadIdx.x == 0) partial[static_cast<int64_t>(t0 + j) * n_chunks + c] = tot;
-    }
-  }
-}
-
-__global__ void k_prox_finish(const int64_t* __restrict__ plan, int n_seg, int n_chunks, int k,
-                              const double* __restrict__ partial, float* __restrict__ norms) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= static_cast<int64_t>(k) * n_seg) return;
-  const int t = static_cast<int>(i / n_seg), sg = static_cast<int>(i % n_seg);
-  double ss = 0.0;
-  for (int64_t c = plan[sg]; c < plan[sg + 1]; ++c) ss += partial[static_cast<int64_t>(t) * n_chunks + c];
-  norms[i] = static_cast<float>(sqrt(ss));
-}
-
-// g_w = s * sum_t (w - wt) / ||w - wt||,  g_wt = -s * (w - wt) / ||w - wt||  (0 where the
-// norm is 0, as torch's norm backward); s = *scale (the upstream gradient, on the device).
-__global__ __launch_bounds__(kBlock) void k_prox_grad(const float* __restrict__ w, ProxPtrs pp, int k,
-                                                      const int64_t* __restrict__ plan, int n_seg,
-                                                      const float* __restrict__ norms,
-                                                      const float* __restrict__ scale,
-                                                      float* __restrict__ gw, int accumulate) {
-  __shared__ float s_c[kProxMaxNb];
-  const int c = blockIdx.x;
-  const int64_t* ch = plan + (n_seg + 1) + 3 * static_cast<int64_t>(c);
-  const int64_t sg = ch[0], beg = ch[1], len = ch[2];
-  if (threadIdx.x < k) {
-    const float nrm = norms[static_cast<int64_t>(threadIdx.x) * n_seg + sg];
-    s_c[threadIdx.x] = nrm > 0.f ? *scale / nrm : 0.f;
-  }
-  __syncthreads();
-  for (int64_t e = threadIdx.x; e < len; e += kBlock) {
-    const float wv = w[beg + e];
-    float g = accumulate ? gw[beg + e] : 0.f;
-    for (int t = 0; t < k; ++t) {
-      const float d = (wv - pp.wt[t][beg + e]) * s_c[t];
-      g += d;
-      if (pp.gwt[t]) pp.gwt[t][beg + e] = -d;
-    }
-    gw[beg + e] = g;
-  }
-}
-
-// K4 on bf16 rows (ABI 29).  The values are the bf16 parameters widened exactly to fp32; the
-// arithmetic is k_prox_sumsq's / k_prox_grad's.  A chunk [beg, beg + len) of a row whose base is
-// 8-B aligned is cut into a head of up to 3 elements, up to the first element at a multiple of 4,
-// a body of whole 8-B groups (one u32x2 per lane per load and per store) and a tail of up to 3
-// elements; head and tail go element by element, so no wide access is ever misaligned.  Rows
-// that are not 8-B aligned (`packed` = 0, chosen on the host) go element by element throughout.
-struct ProxPtrsB16 {
-  const uint16_t* wt[kProxMaxNb];
-  uint16_t* gwt[kProxMaxNb];
-};
-
+// A chunk [beg, beg + len) of a bf16 row whose base is 8-B aligned is cut into a head of up to 3
+// elements, up to the first element at a multiple of 4, a body of whole 8-B groups (one u32x2 per
+// lane per load and per store) and a tail of up to 3 elements; head and tail go element by
+// element, so no wide access is ever misaligned.  bf16 rows that are not 8-B aligned (`packed`
+// = 0, chosen on the host) and fp32 rows go element by element throughout: head = len.
 struct ProxCut {
   int64_t head, groups, edge;  // edge = head + tail elements
   // edge element i of the chunk -> its element index in the chunk
@@ -4359,43 +4288,45 @@ __device__ __forceinline__ float prox_sq4(float4 a, float4 b, float acc) {
   return fmaf(d, d, acc);
 }
 
-__global__ __launch_bounds__(kBlock) void k_prox_sumsq_bf16(const uint16_t* __restrict__ w, ProxPtrsB16 pp, int k,
-                                                            const int64_t* __restrict__ plan, int n_seg,
-                                                            int n_chunks, double* __restrict__ partial,
-                                                            int packed) {
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_prox_sumsq(const T* __restrict__ w, ProxPtrs<T> pp, int k,
+                                                       const int64_t* __restrict__ plan, int n_seg,
+                                                       int n_chunks, double* __restrict__ partial, int packed) {
   __shared__ double s_red[kBlock / 64];
   const int c = blockIdx.x;
   const int64_t* ch = plan + (n_seg + 1) + 3 * static_cast<int64_t>(c);
   const int64_t beg = ch[1], len = ch[2];
-  const ProxCut cut = prox_cut(beg, len, packed);
-  const int64_t body = beg + cut.head;  // a multiple of 4 where there are groups
+  const ProxCut cut = prox_cut(beg, len, kIsBf16<T> && packed);
   for (int t0 = 0; t0 < k; t0 += kProxTile) {
     const int nt = min(kProxTile, k - t0);
     float acc[kProxTile];
 #pragma unroll
     for (int j = 0; j < kProxTile; ++j) acc[j] = 0.f;
-    for (int64_t g = threadIdx.x; g < cut.groups; g += kBlock) {
-      const int64_t e = body + 4 * g;
-      const float4 wv = Io<uint16_t>::f4(*reinterpret_cast<const u32x2*>(w + e));
-      if (nt == kProxTile) {
-        float4 v[kProxTile];
+    if constexpr (kIsBf16<T>) {
+      const int64_t body = beg + cut.head;  // a multiple of 4 where there are groups
+      for (int64_t g = threadIdx.x; g < cut.groups; g += kBlock) {
+        const int64_t e = body + 4 * g;
+        const float4 wv = Io<T>::f4(*reinterpret_cast<const u32x2*>(w + e));
+        if (nt == kProxTile) {
+          float4 v[kProxTile];
 #pragma unroll
-        for (int j = 0; j < kProxTile; ++j) v[j] = prox_ld4_once(pp.wt[t0 + j], e);
+          for (int j = 0; j < kProxTile; ++j) v[j] = prox_ld4_once(pp.wt[t0 + j], e);
 #pragma unroll
-        for (int j = 0; j < kProxTile; ++j) acc[j] = prox_sq4(wv, v[j], acc[j]);
-      } else {
+          for (int j = 0; j < kProxTile; ++j) acc[j] = prox_sq4(wv, v[j], acc[j]);
+        } else {
 #pragma unroll
-        for (int j = 0; j < kProxTile; ++j)
-          if (j < nt) acc[j] = prox_sq4(wv, prox_ld4_once(pp.wt[t0 + j], e), acc[j]);
+          for (int j = 0; j < kProxTile; ++j)
+            if (j < nt) acc[j] = prox_sq4(wv, prox_ld4_once(pp.wt[t0 + j], e), acc[j]);
+        }
       }
     }
     for (int64_t i = threadIdx.x; i < cut.edge; i += kBlock) {
       const int64_t e = beg + cut.edge_elem(i);
-      const float wv = Io<uint16_t>::ld1(w, e);
+      const float wv = Io<T>::ld1(w, e);
 #pragma unroll
       for (int j = 0; j < kProxTile; ++j) {
         if (j < nt) {
-          const float d = wv - Io<uint16_t>::ld1(pp.wt[t0 + j], e);
+          const float d = wv - Io<T>::ld1(pp.wt[t0 + j], e);
           acc[j] = fmaf(d, d, acc[j]);
         }
       }
@@ -4405,6 +4336,16 @@ __global__ __launch_bounds__(kBlock) void k_prox_sumsq_bf16(const uint16_t* __re
       if (threadIdx.x == 0) partial[static_cast<int64_t>(t0 + j) * n_chunks + c] = tot;
     }
   }
+}
+
+__global__ void k_prox_finish(const int64_t* __restrict__ plan, int n_seg, int n_chunks, int k,
+                              const double* __restrict__ partial, float* __restrict__ norms) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= static_cast<int64_t>(k) * n_seg) return;
+  const int t = static_cast<int>(i / n_seg), sg = static_cast<int>(i % n_seg);
+  double ss = 0.0;
+  for (int64_t c = plan[sg]; c < plan[sg + 1]; ++c) ss += partial[static_cast<int64_t>(t) * n_chunks + c];
+  norms[i] = static_cast<float>(sqrt(ss));
 }
 
 // one neighbor's step of k_prox_grad on a group: d = (w - wt) * c, g += d, and -d to gwt
@@ -4417,60 +4358,73 @@ __device__ __forceinline__ void prox_grad4(float4 wv, float4 v, float c, float4&
   if (gwt) Io<uint16_t>::st(gwt, e >> 2, make_float4(-d.x, -d.y, -d.z, -d.w));
 }
 
-// k_prox_grad's fp32 operations in its order on the widened values; g and -d are rounded to bf16
-// once, at the store.  More than kProxMaxNb neighbors take several launches: the running sum goes
-// through `acc` (fp32, the rows' element offsets) - read when `first` is 0, written instead of
-// gw when `last` is 0 - and never through a bf16 gw.  A chunk that acc_elems does not cover is
-// left alone (the host entry refuses such a call where it can tell).
-__global__ __launch_bounds__(kBlock) void k_prox_grad_bf16(const uint16_t* __restrict__ w, ProxPtrsB16 pp, int k,
-                                                           const int64_t* __restrict__ plan, int n_seg,
-                                                           const float* __restrict__ norms,
-                                                           const float* __restrict__ scale,
-                                                           uint16_t* __restrict__ gw, float* __restrict__ acc,
-                                                           int64_t acc_elems, int first, int last, int packed) {
+// g_w = s * sum_t (w - wt) / ||w - wt||,  g_wt = -s * (w - wt) / ||w - wt||  (0 where the
+// norm is 0, as torch's norm backward); s = *scale (the upstream gradient, on the device).
+// On bf16 rows g and -d are rounded to bf16 once, at the store.  More than kProxMaxNb neighbors
+// take several launches.  fp32 rows keep the running sum in gw itself (read when `first` is 0).
+// bf16 rows keep it in `acc` (fp32, the rows' element offsets) - read when `first` is 0, written
+// instead of gw when `last` is 0 - and never in a bf16 gw, which would round it once per launch.
+// A chunk that acc_elems does not cover is left alone (the host entry refuses such a call where
+// it can tell).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_prox_grad(const T* __restrict__ w, ProxPtrs<T> pp, int k,
+                                                      const int64_t* __restrict__ plan, int n_seg,
+                                                      const float* __restrict__ norms,
+                                                      const float* __restrict__ scale, T* __restrict__ gw,
+                                                      float* __restrict__ acc, int64_t acc_elems, int first,
+                                                      int last, int packed) {
   __shared__ float s_c[kProxMaxNb];
   const int c = blockIdx.x;
   const int64_t* ch = plan + (n_seg + 1) + 3 * static_cast<int64_t>(c);
   const int64_t sg = ch[0], beg = ch[1], len = ch[2];
-  if (!(first && last) && beg + len > acc_elems) return;
+  float* sum;  // the running sum between launches: acc for bf16 rows, gw itself for fp32 rows
+  if constexpr (kIsBf16<T>) {
+    if (!(first && last) && beg + len > acc_elems) return;
+    sum = acc;
+  } else {
+    sum = gw;
+  }
+  const bool to_gw = !kIsBf16<T> || last;
   if (threadIdx.x < k) {
     const float nrm = norms[static_cast<int64_t>(threadIdx.x) * n_seg + sg];
     s_c[threadIdx.x] = nrm > 0.f ? *scale / nrm : 0.f;
   }
   __syncthreads();
-  const ProxCut cut = prox_cut(beg, len, packed);
-  const int64_t body = beg + cut.head;
-  for (int64_t gi = threadIdx.x; gi < cut.groups; gi += kBlock) {
-    const int64_t e = body + 4 * gi;
-    const float4 wv = prox_ld4_once(w, e);
-    float4 g = first ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(acc + e);
-    int t = 0;
-    for (; t + kProxTile <= k; t += kProxTile) {
-      float4 v[kProxTile];
+  const ProxCut cut = prox_cut(beg, len, kIsBf16<T> && packed);
+  if constexpr (kIsBf16<T>) {
+    const int64_t body = beg + cut.head;
+    for (int64_t gi = threadIdx.x; gi < cut.groups; gi += kBlock) {
+      const int64_t e = body + 4 * gi;
+      const float4 wv = prox_ld4_once(w, e);
+      float4 g = first ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(sum + e);
+      int t = 0;
+      for (; t + kProxTile <= k; t += kProxTile) {
+        float4 v[kProxTile];
 #pragma unroll
-      for (int j = 0; j < kProxTile; ++j) v[j] = prox_ld4_once(pp.wt[t + j], e);
+        for (int j = 0; j < kProxTile; ++j) v[j] = prox_ld4_once(pp.wt[t + j], e);
 #pragma unroll
-      for (int j = 0; j < kProxTile; ++j) prox_grad4(wv, v[j], s_c[t + j], g, pp.gwt[t + j], e);
+        for (int j = 0; j < kProxTile; ++j) prox_grad4(wv, v[j], s_c[t + j], g, pp.gwt[t + j], e);
+      }
+      for (; t < k; ++t) prox_grad4(wv, prox_ld4_once(pp.wt[t], e), s_c[t], g, pp.gwt[t], e);
+      if (to_gw)
+        Io<T>::st(gw, e >> 2, g);
+      else
+        *reinterpret_cast<float4*>(sum + e) = g;
     }
-    for (; t < k; ++t) prox_grad4(wv, prox_ld4_once(pp.wt[t], e), s_c[t], g, pp.gwt[t], e);
-    if (last)
-      Io<uint16_t>::st(gw, e >> 2, g);
-    else
-      *reinterpret_cast<float4*>(acc + e) = g;
   }
   for (int64_t i = threadIdx.x; i < cut.edge; i += kBlock) {
     const int64_t e = beg + cut.edge_elem(i);
-    const float wv = Io<uint16_t>::ld1(w, e);
-    float g = first ? 0.f : acc[e];
+    const float wv = Io<T>::ld1(w, e);
+    float g = first ? 0.f : sum[e];
     for (int t = 0; t < k; ++t) {
-      const float d = (wv - Io<uint16_t>::ld1(pp.wt[t], e)) * s_c[t];
+      const float d = (wv - Io<T>::ld1(pp.wt[t], e)) * s_c[t];
       g += d;
-      if (pp.gwt[t]) Io<uint16_t>::st1(pp.gwt[t], e, -d);
+      if (pp.gwt[t]) Io<T>::st1(pp.gwt[t], e, -d);
     }
-    if (last)
-      Io<uint16_t>::st1(gw, e, g);
+    if (to_gw)
+      Io<T>::st1(gw, e, g);
     else
-      acc[e] = g;
+      sum[e] = g;
   }
 }
 
@@ -5976,6 +5930,74 @@ int32_t cosine_round(const char* fn, const T* pool, int64_t ld, const int64_t* p
   return check_launch(fn);
 }
 
+bool prox_aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+// K4 (FedProx), one host path per pass for fp32 and bf16 rows: every argument is checked before
+// the first launch; kProxMaxNb neighbors per launch.  `packed` (bf16 only): every row is 8-B
+// aligned, so the kernels may take whole groups.
+template <typename T>
+int32_t prox_norms(const char* fn, const T* w, const T* const* wt_host, int32_t k, const int64_t* plan_dev,
+                   int32_t n_chunks, int32_t n_seg, void* scratch, float* norms_out, void* stream) {
+  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !scratch || !norms_out)
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
+  bool packed = kIsBf16<T> && prox_aligned(w, 8);
+  for (int j = 0; j < k; ++j) {
+    if (!wt_host[j]) return fail(TAL_ERR_INVALID, std::string(fn) + ": null neighbor pointer");
+    packed = packed && prox_aligned(wt_host[j], 8);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int base = 0; base < k; base += kProxMaxNb) {
+    const int cnt = std::min(kProxMaxNb, k - base);
+    ProxPtrs<T> pp{};
+    for (int j = 0; j < cnt; ++j) pp.wt[j] = wt_host[base + j];
+    double* part = static_cast<double*>(scratch);
+    k_prox_sumsq<T><<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg, n_chunks, part, packed ? 1 : 0);
+    const int64_t outs = static_cast<int64_t>(cnt) * n_seg;
+    k_prox_finish<<<static_cast<unsigned>((outs + 255) / 256), 256, 0, s>>>(
+        plan_dev, n_seg, n_chunks, cnt, part, norms_out + static_cast<int64_t>(base) * n_seg);
+    int32_t rc = check_launch(fn);
+    if (rc) return rc;
+  }
+  g_err.clear();
+  return TAL_OK;
+}
+
+// acc_scratch / acc_elems: bf16 rows only (fp32 rows keep the running sum in gw; pass null, 0)
+template <typename T>
+int32_t prox_grad(const char* fn, const T* w, const T* const* wt_host, int32_t k, const int64_t* plan_dev,
+                  int32_t n_chunks, int32_t n_seg, const float* norms, const float* scale_dev, T* gw,
+                  T* const* gwt_host, float* acc_scratch, int64_t acc_elems, void* stream) {
+  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !norms || !scale_dev || !gw)
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": bad arguments");
+  const bool batched = kIsBf16<T> && k > kProxMaxNb;  // the running sum needs the fp32 scratch
+  // every chunk holds an element and no two overlap: fewer elements than chunks cannot cover them
+  if (batched && (!acc_scratch || acc_elems < n_chunks))
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": more than " + std::to_string(kProxMaxNb) +
+                                     " neighbors need an fp32 acc_scratch that covers every chunk");
+  bool packed = kIsBf16<T> && prox_aligned(w, 8) && prox_aligned(gw, 8) && (!batched || prox_aligned(acc_scratch, 16));
+  for (int j = 0; j < k; ++j) {
+    if (!wt_host[j]) return fail(TAL_ERR_INVALID, std::string(fn) + ": null neighbor pointer");
+    packed = packed && prox_aligned(wt_host[j], 8) && (!gwt_host || prox_aligned(gwt_host[j], 8));
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int base = 0; base < k; base += kProxMaxNb) {
+    const int cnt = std::min(kProxMaxNb, k - base);
+    ProxPtrs<T> pp{};
+    for (int j = 0; j < cnt; ++j) {
+      pp.wt[j] = wt_host[base + j];
+      pp.gwt[j] = gwt_host ? gwt_host[base + j] : nullptr;
+    }
+    k_prox_grad<T><<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg,
+                                              norms + static_cast<int64_t>(base) * n_seg, scale_dev, gw,
+                                              batched ? acc_scratch : nullptr, batched ? acc_elems : 0,
+                                              base == 0 ? 1 : 0, base + cnt == k ? 1 : 0, packed ? 1 : 0);
+    int32_t rc = check_launch(fn);
+    if (rc) return rc;
+  }
+  g_err.clear();
+  return TAL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -6037,113 +6059,28 @@ int64_t tal_prox_scratch_bytes(int32_t n_chunks, int32_t k) {
 
 int32_t tal_prox_norms(const float* w, const float* const* wt_host, int32_t k, const int64_t* plan_dev,
                        int32_t n_chunks, int32_t n_seg, void* scratch, float* norms_out, void* stream) {
-  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !scratch || !norms_out)
-    return fail(TAL_ERR_INVALID, "tal_prox_norms: bad arguments");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int base = 0; base < k; base += kProxMaxNb) {
-    const int cnt = std::min(kProxMaxNb, k - base);
-    ProxPtrs pp{};
-    for (int j = 0; j < cnt; ++j) {
-      if (!wt_host[base + j]) return fail(TAL_ERR_INVALID, "tal_prox_norms: null neighbor pointer");
-      pp.wt[j] = wt_host[base + j];
-    }
-    double* part = static_cast<double*>(scratch);
-    k_prox_sumsq<<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg, n_chunks, part);
-    const int64_t outs = static_cast<int64_t>(cnt) * n_seg;
-    k_prox_finish<<<static_cast<unsigned>((outs + 255) / 256), 256, 0, s>>>(
-        plan_dev, n_seg, n_chunks, cnt, part, norms_out + static_cast<int64_t>(base) * n_seg);
-    int32_t rc = check_launch("prox norms");
-    if (rc) return rc;
-  }
-  g_err.clear();
-  return TAL_OK;
+  return prox_norms<float>("tal_prox_norms", w, wt_host, k, plan_dev, n_chunks, n_seg, scratch, norms_out, stream);
 }
 
 int32_t tal_prox_grad(const float* w, const float* const* wt_host, int32_t k, const int64_t* plan_dev,
                       int32_t n_chunks, int32_t n_seg, const float* norms, const float* scale_dev,
                       float* gw, float* const* gwt_host, void* stream) {
-  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !norms || !scale_dev || !gw)
-    return fail(TAL_ERR_INVALID, "tal_prox_grad: bad arguments");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int base = 0; base < k; base += kProxMaxNb) {
-    const int cnt = std::min(kProxMaxNb, k - base);
-    ProxPtrs pp{};
-    for (int j = 0; j < cnt; ++j) {
-      if (!wt_host[base + j]) return fail(TAL_ERR_INVALID, "tal_prox_grad: null neighbor pointer");
-      pp.wt[j] = wt_host[base + j];
-      pp.gwt[j] = gwt_host ? gwt_host[base + j] : nullptr;
-    }
-    k_prox_grad<<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg,
-                                           norms + static_cast<int64_t>(base) * n_seg, scale_dev, gw,
-                                           base > 0 ? 1 : 0);
-    int32_t rc = check_launch("prox grad");
-    if (rc) return rc;
-  }
-  g_err.clear();
-  return TAL_OK;
+  return prox_grad<float>("tal_prox_grad", w, wt_host, k, plan_dev, n_chunks, n_seg, norms, scale_dev, gw, gwt_host,
+                          nullptr, 0, stream);
 }
-
-static bool prox_aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 int32_t tal_prox_norms_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k, const int64_t* plan_dev,
                             int32_t n_chunks, int32_t n_seg, void* scratch, float* norms_out, void* stream) {
-  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !scratch || !norms_out)
-    return fail(TAL_ERR_INVALID, "tal_prox_norms_bf16: bad arguments");
-  bool packed = prox_aligned(w, 8);
-  for (int j = 0; j < k; ++j) {
-    if (!wt_host[j]) return fail(TAL_ERR_INVALID, "tal_prox_norms_bf16: null neighbor pointer");
-    packed = packed && prox_aligned(wt_host[j], 8);
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int base = 0; base < k; base += kProxMaxNb) {
-    const int cnt = std::min(kProxMaxNb, k - base);
-    ProxPtrsB16 pp{};
-    for (int j = 0; j < cnt; ++j) pp.wt[j] = wt_host[base + j];
-    double* part = static_cast<double*>(scratch);
-    k_prox_sumsq_bf16<<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg, n_chunks, part, packed ? 1 : 0);
-    const int64_t outs = static_cast<int64_t>(cnt) * n_seg;
-    k_prox_finish<<<static_cast<unsigned>((outs + 255) / 256), 256, 0, s>>>(
-        plan_dev, n_seg, n_chunks, cnt, part, norms_out + static_cast<int64_t>(base) * n_seg);
-    int32_t rc = check_launch("prox norms bf16");
-    if (rc) return rc;
-  }
-  g_err.clear();
-  return TAL_OK;
+  return prox_norms<uint16_t>("tal_prox_norms_bf16", w, wt_host, k, plan_dev, n_chunks, n_seg, scratch, norms_out,
+                              stream);
 }
 
 int32_t tal_prox_grad_bf16(const uint16_t* w, const uint16_t* const* wt_host, int32_t k, const int64_t* plan_dev,
                            int32_t n_chunks, int32_t n_seg, const float* norms, const float* scale_dev,
                            uint16_t* gw, uint16_t* const* gwt_host, float* acc_scratch, int64_t acc_elems,
                            void* stream) {
-  if (!w || !wt_host || k <= 0 || !plan_dev || n_chunks <= 0 || n_seg <= 0 || !norms || !scale_dev || !gw)
-    return fail(TAL_ERR_INVALID, "tal_prox_grad_bf16: bad arguments");
-  const bool batched = k > kProxMaxNb;
-  // every chunk holds an element and no two overlap: fewer elements than chunks cannot cover them
-  if (batched && (!acc_scratch || acc_elems < n_chunks))
-    return fail(TAL_ERR_INVALID, "tal_prox_grad_bf16: more than " + std::to_string(kProxMaxNb) +
-                                     " neighbors need an fp32 acc_scratch that covers every chunk");
-  bool packed = prox_aligned(w, 8) && prox_aligned(gw, 8) && (!batched || prox_aligned(acc_scratch, 16));
-  for (int j = 0; j < k; ++j) {
-    if (!wt_host[j]) return fail(TAL_ERR_INVALID, "tal_prox_grad_bf16: null neighbor pointer");
-    packed = packed && prox_aligned(wt_host[j], 8) && (!gwt_host || prox_aligned(gwt_host[j], 8));
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int base = 0; base < k; base += kProxMaxNb) {
-    const int cnt = std::min(kProxMaxNb, k - base);
-    ProxPtrsB16 pp{};
-    for (int j = 0; j < cnt; ++j) {
-      pp.wt[j] = wt_host[base + j];
-      pp.gwt[j] = gwt_host ? gwt_host[base + j] : nullptr;
-    }
-    k_prox_grad_bf16<<<n_chunks, kBlock, 0, s>>>(w, pp, cnt, plan_dev, n_seg,
-                                                norms + static_cast<int64_t>(base) * n_seg, scale_dev, gw,
-                                                batched ? acc_scratch : nullptr, batched ? acc_elems : 0,
-                                                base == 0 ? 1 : 0, base + cnt == k ? 1 : 0, packed ? 1 : 0);
-    int32_t rc = check_launch("prox grad bf16");
-    if (rc) return rc;
-  }
-  g_err.clear();
-  return TAL_OK;
+  return prox_grad<uint16_t>("tal_prox_grad_bf16", w, wt_host, k, plan_dev, n_chunks, n_seg, norms, scale_dev, gw,
+                             gwt_host, acc_scratch, acc_elems, stream);
 }
 
 }  // extern "C"
