@@ -24,9 +24,8 @@
  *     thread-local message for the last failure on the calling thread.
  *   - all data pointers are DEVICE pointers owned by the caller; host arrays are named *_host.
  *   - `stream` is a hipStream_t (NULL = the default stream); calls are stream-ordered and
- *     never synchronize the device; the library allocates no device memory except 512 B of
- *     item counters per (device, stream) that tal_agg_round_reg launches on (made on first use,
- *     kept for the process: launches on different streams never share counters).
+ *     never synchronize the device; the library keeps no device memory of its own (the one
+ *     allocation it makes is the stream-ordered scratch of a K1 call, freed in that call).
  *   - weights arrive as float64 (Python floats / numpy float64 in the reference) and are
  *     rounded to fp32 exactly as torch does for `python_float * fp32_tensor`.
  *   - mode: TAL_MODE_EXACT reproduces the reference bit for bit (ordered i=0..M-1,
@@ -57,7 +56,9 @@ extern "C" {
 
 /* Thread-local text of the last error on this thread ("" if none). */
 const char* tal_last_error(void);
-/* ABI version (bumped on any signature change). */
+/* ABI version (bumped on any signature change).  ABI 33 removed the round over
+ * register-resident source groups (K3r) with its entry point: no plan the library picks ever
+ * selected it. */
 int32_t tal_abi_version(void);
 
 /* ---- K1: one aggregation call over M flattened operands --------------------------------
@@ -351,30 +352,6 @@ int32_t tal_agg_round_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* poo
  * "k_round_stream", "k_round_wide", "k_round_f32_narrow" (the broadcast form too),
  * "k_round_f32_persistent" or "k_round_f32_tiled"; "" for a null info.  A static string. */
 const char* tal_round_kernel_name(const tal_round_plan_info* info, int32_t bf16);
-
-/* ---- K3r: a round over register-resident source groups ----------------------------------
- * Community graphs (BASELINE config 5's stochastic block model): the rows are grouped so that
- * each group reads <= 64 distinct sources; one wavefront loads a group's sources for a 128-
- * element piece of the columns into VGPRs and emits every row of the group for that piece, an
- * operand read from the registers by the VGPR index mode (no LDS, no barrier).  Same results
- * as tal_agg_round_f32 (EXACT: bitwise the reference; FMA: bitwise K1-FMA); bf16 pools (bf16 !=
- * 0) in FMA mode only.  Out of place (pool_in != pool_out).  Pools 2-element aligned, even ld
- * >= n rounded up to even; table_dev 64-B aligned.  table_dev (int32): n_groups records {first
- * source, sources, first pair, pairs}; at off_src the source pool rows, every group's list
- * padded to 16 x NB entries, NB = ceil(max_src / 16) (src_off_dev: int64 byte offsets of those
- * entries, row x ld_in x element size); at off_pairs (a multiple of 4) row-pair records {out
- * row A, out row B or -1, trips, byte offset from table_dev of the pair's first trip record}, a
- * group's pairs consecutive; at off_rec (a multiple of 16) trip records of 16 dwords {A's four
- * operand register offsets (2 x the source's slot in the group), B's four, A's four fp32
- * weights, B's four}, a row padded to its pair's trips with the neutral operand (offset 32 x
- * NB, weight +0.0: a -0.0 product that leaves the sum unchanged), followed by one record of
- * padding.  max_src = the largest group's sources (<= 64).  Replaces
- * decentralized_client.py:399-413 for every row of the round at once (snapshot semantics, as
- * tal_agg_round_f32). */
-int32_t tal_agg_round_reg(const void* pool_in, int64_t ld_in, void* pool_out, int64_t ld_out,
-                          int64_t n, int32_t bf16, const int32_t* table_dev, const int64_t* src_off_dev,
-                          int32_t n_groups, int32_t off_src, int32_t off_pairs, int32_t off_rec,
-                          int32_t max_src, int32_t mode, void* stream);
 
 /* ---- K2: cosine similarity of two models' parameters, bit for bit -------------------------
  * Reference: cosine_similarity, decentralized_client.py:661-681: for each parameter tensor

@@ -198,3 +198,35 @@ def test_round_bcast_staging_limit(cuda, c4, waves, wg, shape):
         pout = pin.clone()
         ops.round_f32(pin, pout, plan, n=n)  # raises on any launch refusal
         assert _bits_equal(host(pout, n), ref), (k, shape)
+
+
+def test_round_executor_bf16_fma_per_operand_weights(cuda):
+    """The product's untimed default for a bf16 FMA round with per-operand (degree-centrality)
+    weights is the narrow kernel's broadcast form since round 4 (ops.default_plan; K3r before):
+    RoundExecutor on bf16 model rows of the SBM-256 topology runs it in place (one group, no
+    scratch pool), every row bitwise the bf16 FMA oracle (fp32 fused chain, one rounding), the
+    int64 segment through the plan's scalar form, bitwise the oracle's truncation."""
+    from topology_aware_learning_amd.arena import ModelPool, StateLayout
+    from topology_aware_learning_amd.round import RoundExecutor
+
+    orders, ws = _csr(bench.make_graph("sbm", 256, 8), "degcent")
+    row_ptr, col, w = ra.round_csr(orders, ws)
+    rows = len(orders)
+    lay = StateLayout.from_layout([("w", [1003], "bfloat16"), ("n", [3], "int64")])
+    pool = ModelPool(lay, rows, cuda)
+    rng = np.random.default_rng(5)
+    x = torch.from_numpy((rng.standard_normal((rows, lay.n_b16)) * 3).astype(np.float32)).to(torch.bfloat16)
+    xi = torch.from_numpy(rng.integers(0, 10 ** 6, (rows, lay.n_i64)))
+    pool.b16[:, :lay.n_b16].copy_(x.to(cuda))
+    pool.i64[:, :lay.n_i64].copy_(xi.to(cuda))
+    ex = RoundExecutor(pool, mode=ops.MODE_FMA)
+    plan = ex.plan(orders, ws, list(range(rows)))
+    assert isinstance(plan, ops.RoundPlan) and plan.info.narrow_bcast and plan.single_group
+    bits = x.view(torch.int16).numpy().view(np.uint16)
+    ref = oracle.round_bf16(bits, row_ptr, col, w, np.arange(rows, dtype=np.int32), exact=False)
+    iref = oracle.round_i64(xi.numpy(), row_ptr, col, w, np.arange(rows, dtype=np.int32))
+    ex.run(orders, ws)
+    torch.cuda.synchronize(cuda)
+    got = pool.b16[:, :lay.n_b16].cpu().view(torch.int16).numpy().view(np.uint16)
+    assert np.array_equal(got, ref)
+    assert np.array_equal(pool.i64[:, :lay.n_i64].cpu().numpy(), iref)

@@ -28,7 +28,6 @@ Entry point / kernel -> test
   k_round_f32_narrow, 8 / 12 staging loads    test_round_narrow_wide_groups
   k_round_f32_narrow, broadcast form          test_round_narrow_bcast
   k_round_stream, k_round_stream_scalar       test_round_stream, test_round_stream_scalar
-  k_round_reg (K3r), 1 and 4 register blocks  test_round_reg
   k_round_clique (K3c), uniform weights       test_round_clique
   k_round_clique (K3c), per-source weights    test_round_clique_weighted
   k_round_clique_col (K3c1)                   test_round_clique_col
@@ -310,25 +309,6 @@ def test_round_stream_scalar(cuda):
     assert plan.info.stream_cs > 0 and plan.info.n_groups > 1
     pin, _ = _run(cuda, case, plan, pad=False)
     assert pin.stride(0) % 4 != 0 and case.n > 256
-
-
-@pytest.mark.parametrize("weights", ["unweighted", "softmax"])
-@pytest.mark.parametrize("graph,cap,blocks", [("regular12", 16, 1), ("sbm64", 64, 4)])
-def test_round_reg(cuda, graph, cap, blocks, weights):
-    """K3r: sources in VGPRs, rows in pairs padded with the neutral operand (weight +0.0)."""
-    if graph == "regular12":
-        g = nx.random_regular_graph(4, 12, seed=1)
-    else:
-        p = [[14 / 31 if a == b else 2 / 224 for b in range(4)] for a in range(4)]
-        g = nx.stochastic_block_model([16] * 4, p, seed=3)
-    orders, ws = _graph_round(g, weights)
-    rows = len(orders)
-    case = RoundCase(orders, ws, np.arange(rows), rows, 259, seed=cap)
-    plan = ops.build_reg_plan(*case.csr, max_src=cap)
-    assert isinstance(plan, ops.RegPlan) and (plan.max_src + 15) // 16 == blocks
-    assert ops.round_kernel_name(plan) == "k_round_reg"
-    pin, pout = _run(cuda, case, plan)
-    assert pin.stride(0) % 2 == 0 and pin.data_ptr() % 8 == 0 and pout.data_ptr() % 8 == 0  # K3r itself, not plan.full
 
 
 def _clique_run(cuda, case, plan):

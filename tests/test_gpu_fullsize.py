@@ -122,7 +122,7 @@ def _check_resnet_round(cuda, name, spec):
 @pytest.mark.parametrize("spec", [None, {"c4": 64, "lds": 81920, "dense": 0}, {"c4": 128, "lds": 163840, "dense": 0},
                                   {"c4": 128, "lds": 81920, "dense": 0}, {"c4": 32, "lds": 81920, "dense": 0},
                                   {"c4": 16, "lds": 81920, "dense": 0}, {"c4": 64, "lds": 81920, "dense": 8},
-                                  {"stream_rows": 64, "stream_src": 0}, {"reg": 1}])
+                                  {"stream_rows": 64, "stream_src": 0}])
 def test_config3_full_round_vs_reference(cuda, spec):
     """The benchmark's round (64-device random 8-regular graph, ResNet-50, M = 9) at full size:
     all 64 output models bitwise the reference's, for every plan form the tuner can pick."""
@@ -130,7 +130,7 @@ def test_config3_full_round_vs_reference(cuda, spec):
 
 
 @pytest.mark.parametrize("spec", [None, {"c4": 128, "lds": 163840, "dense": 0}, {"c4": 64, "lds": 163840, "dense": 8},
-                                  {"c4": 16, "lds": 81920, "dense": 0}, {"reg": 1}])
+                                  {"c4": 16, "lds": 81920, "dense": 0}])
 def test_config4_full_round_vs_reference(cuda, spec):
     """barbell(60, 8), 128 x ResNet-50 at full size: the K3c clique blocks with their attached
     bridge rows (default plan) and the LDS-tiled forms, all 128 output models bitwise the
@@ -178,21 +178,21 @@ def _check_c5(cuda, dtype, fn, spec, mode=ops.MODE_EXACT):
     assert not bad, f"{len(bad)} (model, entry group) outputs differ from the reference, first {bad[:8]}"
 
 
-@pytest.mark.parametrize("spec", [None, {"c4": 32, "lds": 163840, "dense": 0}, {"reg": 1}])
+@pytest.mark.parametrize("spec", [None, {"c4": 32, "lds": 163840, "dense": 0}])
 def test_config5_full_round_vs_reference(cuda, spec):
     """SBM-256 x ViT-B/16 fp32 at full size (88.6 GB of models): every (output model, entry
     group) bitwise the reference's unweighted_module_avg."""
     _check_c5(cuda, "f32", "unweighted_module_avg", spec)
 
 
-@pytest.mark.parametrize("spec", [None, {"reg": 1}, {"c4": 16, "lds": 163840, "dense": 0},
+@pytest.mark.parametrize("spec", [None, {"c4": 16, "lds": 163840, "dense": 0},
                                   {"c4": 16, "lds": 163840, "dense": 0, "bcast": 16, "bcwg": 2},
                                   {"c4": 32, "lds": 163840, "dense": 0, "bcast": 16, "bcwg": 1}])
 def test_config5_degree_centrality_vs_reference(cuda, spec):
     """The per-operand-weight form (centrality_module_avg, degree, softmax coeff 10) of config 5
     at full width: every entry group of every output model bitwise the reference's, through the
-    default plan (the broadcast form, 8 wavefronts x 2), K3r, the pairs form and the 16 x 2
-    broadcast form, and the two-chunk broadcast form (c4 = 32, one workgroup per CU)."""
+    default plan (the broadcast form, 8 wavefronts x 2), the pairs form and the 16 x 2 broadcast
+    form, and the two-chunk broadcast form (c4 = 32, one workgroup per CU)."""
     _check_c5(cuda, "f32", "centrality_module_avg", spec)
 
 
@@ -204,7 +204,6 @@ def test_config5_bf16_exact_vs_reference(cuda):
 
 @pytest.mark.parametrize("fn,spec", [("unweighted_module_avg", None),
                                      ("centrality_module_avg", None),
-                                     ("centrality_module_avg", {"reg": 1}),
                                      ("centrality_module_avg", {"c4": 16, "lds": 163840, "dense": 0, "bcast": 16, "bcwg": 2}),
                                      ("centrality_module_avg", {"c4": 32, "lds": 163840, "dense": 0, "bcast": 16, "bcwg": 1})])
 def test_config5_bf16_fma_full_width_within_bound(cuda, fn, spec):
@@ -213,7 +212,8 @@ def test_config5_bf16_fma_full_width_within_bound(cuda, fn, spec):
         |got - ref| <= 2^-8 |ref| + M_r 2^-24 sum_i |w_i x_i|
     against an fp32 EXACT round of the same bf16-valued inputs (the fp32 round kernel that
     test_config5_full_round_vs_reference pins to the reference's sha256), column chunk by
-    column chunk; the default plan (per-operand weights: the broadcast form) and K3r."""
+    column chunk; the default plan (per-operand weights: the broadcast form) and the two other
+    broadcast forms."""
     fx = _fixture("full_round_c5_vit_sbm256.json")
     orders = fx["orders"]
     run = dict(fn=fn, softmax=True, softmax_coeff=10.0)

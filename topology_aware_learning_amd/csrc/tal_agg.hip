@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 32;
+constexpr int kAbiVersion = 33;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -93,8 +93,6 @@ int32_t with_int_or0(int v, F&& f) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // ------------------------------------------------------------------------------------------
 // element arithmetic
@@ -2652,435 +2650,6 @@ int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld
   return check_launch("clique round kernel (one column per lane)");
 }
 
-// ------------------------------------------------------------------------------------------
-// K3r: rounds whose rows fall into groups of <= 64 distinct sources (community graphs, BASELINE
-// config 5's stochastic block model), each group's sources held in VGPRs.
-//   One wave = one item (group g, piece t): the 64 lanes load 2 elements each (fp32 8 B, bf16
-//   4 B unpacked to fp32) of every source of g at columns [128 t, 128 t + 128) straight into
-//   v[32 : 32 + 2 S) - no LDS, no barrier - then emit every row of g for that piece in
-//   reference order.  A row's operand is read from the registers by its wave-uniform slot with
-//   the VGPR index mode (s_set_gpr_idx_on / _idx / _off, SRC0): the multiply itself reads
-//   v[32 + 2 slot], so the register file stands in for K3n's LDS tile and no per-operand LDS
-//   read or extra move is issued.  The loads and the indexed arithmetic are inline asm on
-//   fixed registers (the compiler keeps the source tuples pinned there: every asm lists them
-//   as operands); rows run in pairs so that no packed instruction reads the result of the one
-//   right before it (gfx950 needs a wait state there, which the pairs fill with the other row).
-//   Items are handed to waves per XCD label (blockIdx % 8): the groups of one piece run on one
-//   XCD at the same time, so a source shared by several groups is fetched from HBM once and
-//   served to the others by that XCD's L2.
-//   Arithmetic: EXACT = fp32 multiply then fp32 add per operand from -0.0 (-0 + p = p), the
-//   reference's order; FMA = fused chains from -0.0 (fma(w, x0, -0) = fl(w x0)), bitwise K1-FMA.
-//   bf16 pools: FMA only (fp32 accumulation, one rounding at the store).
-// ------------------------------------------------------------------------------------------
-typedef float v32f __attribute__((ext_vector_type(32)));
-typedef __attribute__((address_space(4))) const uint64_t* ConstU64;
-constexpr int kRegMaxSrc = 64;
-constexpr int kRegPiece = 128;  // elements per item: 64 lanes x 2
-
-// plain (temporal) loads: a source shared by several groups of a piece is served to the others
-// by the XCD's L2 (non-temporal loads were measured fetching every group's sources from HBM:
-// 4.1x the bytes on config 5)
-#define TAL_RLD2(a, b, k) "global_load_dwordx2 v[" #a ":" #b "], %17, %" #k "\n\t"
-#define TAL_RLD1(b, k) "global_load_dword v" #b ", %17, %" #k "\n\t"
-#define TAL_RUNP(a, b) "v_lshlrev_b32 v" #a ", 16, v" #b "\n\tv_and_b32 v" #b ", 0xffff0000, v" #b "\n\t"
-#define TAL_RF32_0 \
-  TAL_RLD2(32,33,1) TAL_RLD2(34,35,2) TAL_RLD2(36,37,3) TAL_RLD2(38,39,4) \
-  TAL_RLD2(40,41,5) TAL_RLD2(42,43,6) TAL_RLD2(44,45,7) TAL_RLD2(46,47,8) \
-  TAL_RLD2(48,49,9) TAL_RLD2(50,51,10) TAL_RLD2(52,53,11) TAL_RLD2(54,55,12) \
-  TAL_RLD2(56,57,13) TAL_RLD2(58,59,14) TAL_RLD2(60,61,15) TAL_RLD2(62,63,16)
-#define TAL_RF32_1 \
-  TAL_RLD2(64,65,1) TAL_RLD2(66,67,2) TAL_RLD2(68,69,3) TAL_RLD2(70,71,4) \
-  TAL_RLD2(72,73,5) TAL_RLD2(74,75,6) TAL_RLD2(76,77,7) TAL_RLD2(78,79,8) \
-  TAL_RLD2(80,81,9) TAL_RLD2(82,83,10) TAL_RLD2(84,85,11) TAL_RLD2(86,87,12) \
-  TAL_RLD2(88,89,13) TAL_RLD2(90,91,14) TAL_RLD2(92,93,15) TAL_RLD2(94,95,16)
-#define TAL_RF32_2 \
-  TAL_RLD2(96,97,1) TAL_RLD2(98,99,2) TAL_RLD2(100,101,3) TAL_RLD2(102,103,4) \
-  TAL_RLD2(104,105,5) TAL_RLD2(106,107,6) TAL_RLD2(108,109,7) TAL_RLD2(110,111,8) \
-  TAL_RLD2(112,113,9) TAL_RLD2(114,115,10) TAL_RLD2(116,117,11) TAL_RLD2(118,119,12) \
-  TAL_RLD2(120,121,13) TAL_RLD2(122,123,14) TAL_RLD2(124,125,15) TAL_RLD2(126,127,16)
-#define TAL_RF32_3 \
-  TAL_RLD2(128,129,1) TAL_RLD2(130,131,2) TAL_RLD2(132,133,3) TAL_RLD2(134,135,4) \
-  TAL_RLD2(136,137,5) TAL_RLD2(138,139,6) TAL_RLD2(140,141,7) TAL_RLD2(142,143,8) \
-  TAL_RLD2(144,145,9) TAL_RLD2(146,147,10) TAL_RLD2(148,149,11) TAL_RLD2(150,151,12) \
-  TAL_RLD2(152,153,13) TAL_RLD2(154,155,14) TAL_RLD2(156,157,15) TAL_RLD2(158,159,16)
-#define TAL_RB16_0 \
-  TAL_RLD1(33,1) TAL_RLD1(35,2) TAL_RLD1(37,3) TAL_RLD1(39,4) \
-  TAL_RLD1(41,5) TAL_RLD1(43,6) TAL_RLD1(45,7) TAL_RLD1(47,8) \
-  TAL_RLD1(49,9) TAL_RLD1(51,10) TAL_RLD1(53,11) TAL_RLD1(55,12) \
-  TAL_RLD1(57,13) TAL_RLD1(59,14) TAL_RLD1(61,15) TAL_RLD1(63,16)
-#define TAL_RB16_1 \
-  TAL_RLD1(65,1) TAL_RLD1(67,2) TAL_RLD1(69,3) TAL_RLD1(71,4) \
-  TAL_RLD1(73,5) TAL_RLD1(75,6) TAL_RLD1(77,7) TAL_RLD1(79,8) \
-  TAL_RLD1(81,9) TAL_RLD1(83,10) TAL_RLD1(85,11) TAL_RLD1(87,12) \
-  TAL_RLD1(89,13) TAL_RLD1(91,14) TAL_RLD1(93,15) TAL_RLD1(95,16)
-#define TAL_RB16_2 \
-  TAL_RLD1(97,1) TAL_RLD1(99,2) TAL_RLD1(101,3) TAL_RLD1(103,4) \
-  TAL_RLD1(105,5) TAL_RLD1(107,6) TAL_RLD1(109,7) TAL_RLD1(111,8) \
-  TAL_RLD1(113,9) TAL_RLD1(115,10) TAL_RLD1(117,11) TAL_RLD1(119,12) \
-  TAL_RLD1(121,13) TAL_RLD1(123,14) TAL_RLD1(125,15) TAL_RLD1(127,16)
-#define TAL_RB16_3 \
-  TAL_RLD1(129,1) TAL_RLD1(131,2) TAL_RLD1(133,3) TAL_RLD1(135,4) \
-  TAL_RLD1(137,5) TAL_RLD1(139,6) TAL_RLD1(141,7) TAL_RLD1(143,8) \
-  TAL_RLD1(145,9) TAL_RLD1(147,10) TAL_RLD1(149,11) TAL_RLD1(151,12) \
-  TAL_RLD1(153,13) TAL_RLD1(155,14) TAL_RLD1(157,15) TAL_RLD1(159,16)
-#define TAL_RUNP_0 \
-  TAL_RUNP(32,33) TAL_RUNP(34,35) TAL_RUNP(36,37) TAL_RUNP(38,39) \
-  TAL_RUNP(40,41) TAL_RUNP(42,43) TAL_RUNP(44,45) TAL_RUNP(46,47) \
-  TAL_RUNP(48,49) TAL_RUNP(50,51) TAL_RUNP(52,53) TAL_RUNP(54,55) \
-  TAL_RUNP(56,57) TAL_RUNP(58,59) TAL_RUNP(60,61) TAL_RUNP(62,63)
-#define TAL_RUNP_1 \
-  TAL_RUNP(64,65) TAL_RUNP(66,67) TAL_RUNP(68,69) TAL_RUNP(70,71) \
-  TAL_RUNP(72,73) TAL_RUNP(74,75) TAL_RUNP(76,77) TAL_RUNP(78,79) \
-  TAL_RUNP(80,81) TAL_RUNP(82,83) TAL_RUNP(84,85) TAL_RUNP(86,87) \
-  TAL_RUNP(88,89) TAL_RUNP(90,91) TAL_RUNP(92,93) TAL_RUNP(94,95)
-#define TAL_RUNP_2 \
-  TAL_RUNP(96,97) TAL_RUNP(98,99) TAL_RUNP(100,101) TAL_RUNP(102,103) \
-  TAL_RUNP(104,105) TAL_RUNP(106,107) TAL_RUNP(108,109) TAL_RUNP(110,111) \
-  TAL_RUNP(112,113) TAL_RUNP(114,115) TAL_RUNP(116,117) TAL_RUNP(118,119) \
-  TAL_RUNP(120,121) TAL_RUNP(122,123) TAL_RUNP(124,125) TAL_RUNP(126,127)
-#define TAL_RUNP_3 \
-  TAL_RUNP(128,129) TAL_RUNP(130,131) TAL_RUNP(132,133) TAL_RUNP(134,135) \
-  TAL_RUNP(136,137) TAL_RUNP(138,139) TAL_RUNP(140,141) TAL_RUNP(142,143) \
-  TAL_RUNP(144,145) TAL_RUNP(146,147) TAL_RUNP(148,149) TAL_RUNP(150,151) \
-  TAL_RUNP(152,153) TAL_RUNP(154,155) TAL_RUNP(156,157) TAL_RUNP(158,159)
-
-#define TAL_RB16(b)                                                                                 \
-  "s"(b[0]), "s"(b[1]), "s"(b[2]), "s"(b[3]), "s"(b[4]), "s"(b[5]), "s"(b[6]), "s"(b[7]), "s"(b[8]), \
-      "s"(b[9]), "s"(b[10]), "s"(b[11]), "s"(b[12]), "s"(b[13]), "s"(b[14]), "s"(b[15])
-#define TAL_RX1 "{v[32:63]}"(X0)
-#define TAL_RX2 TAL_RX1, "{v[64:95]}"(X1)
-#define TAL_RX3 TAL_RX2, "{v[96:127]}"(X2)
-#define TAL_RX4 TAL_RX3, "{v[128:159]}"(X3)
-#define TAL_UNP(...) __VA_ARGS__
-// one inline-asm statement with the NB source tuples appended to its inputs
-#define TAL_RASM(TMPL, OUTS, INS)                                                      \
-  do {                                                                                 \
-    if constexpr (NB == 1) asm volatile(TMPL : TAL_UNP OUTS : TAL_UNP INS, TAL_RX1);   \
-    else if constexpr (NB == 2) asm volatile(TMPL : TAL_UNP OUTS : TAL_UNP INS, TAL_RX2); \
-    else if constexpr (NB == 3) asm volatile(TMPL : TAL_UNP OUTS : TAL_UNP INS, TAL_RX3); \
-    else asm volatile(TMPL : TAL_UNP OUTS : TAL_UNP INS, TAL_RX4);                     \
-  } while (0)
-
-// 16 sources (block J) into v[32 + 32 J ...]: b = per-source byte addresses of the piece
-// (wave-uniform), off = the lane's byte offset in it.  No wait: reg_wait follows all blocks.
-template <int J, bool BF16>
-__device__ __forceinline__ v32f reg_load_block(const uint64_t* b, uint32_t off) {
-  v32f X;
-#define TAL_RLOAD(TM, R) asm volatile(TM : "=&{" R "}"(X) : TAL_RB16(b), "v"(off) : "memory")
-  if constexpr (!BF16) {
-    if constexpr (J == 0) TAL_RLOAD(TAL_RF32_0, "v[32:63]");
-    else if constexpr (J == 1) TAL_RLOAD(TAL_RF32_1, "v[64:95]");
-    else if constexpr (J == 2) TAL_RLOAD(TAL_RF32_2, "v[96:127]");
-    else TAL_RLOAD(TAL_RF32_3, "v[128:159]");
-  } else {  // the packed pair goes to the odd register; reg_wait unpacks it in place
-    if constexpr (J == 0) TAL_RLOAD(TAL_RB16_0, "v[32:63]");
-    else if constexpr (J == 1) TAL_RLOAD(TAL_RB16_1, "v[64:95]");
-    else if constexpr (J == 2) TAL_RLOAD(TAL_RB16_2, "v[96:127]");
-    else TAL_RLOAD(TAL_RB16_3, "v[128:159]");
-  }
-#undef TAL_RLOAD
-  return X;
-}
-
-template <int NB, bool BF16>
-__device__ __forceinline__ void reg_wait(v32f& X0, v32f& X1, v32f& X2, v32f& X3) {
-  if constexpr (!BF16) {
-    if constexpr (NB == 1) asm volatile("s_waitcnt vmcnt(0)" : "+{v[32:63]}"(X0));
-    else if constexpr (NB == 2) asm volatile("s_waitcnt vmcnt(0)" : "+{v[32:63]}"(X0), "+{v[64:95]}"(X1));
-    else if constexpr (NB == 3)
-      asm volatile("s_waitcnt vmcnt(0)" : "+{v[32:63]}"(X0), "+{v[64:95]}"(X1), "+{v[96:127]}"(X2));
-    else
-      asm volatile("s_waitcnt vmcnt(0)"
-                   : "+{v[32:63]}"(X0), "+{v[64:95]}"(X1), "+{v[96:127]}"(X2), "+{v[128:159]}"(X3));
-  } else {  // bf16 pair (lo = element 0) -> two fp32: v[2k] = lo << 16, v[2k+1] = hi & 0xffff0000
-    if constexpr (NB == 1) asm volatile("s_waitcnt vmcnt(0)\n\t" TAL_RUNP_0 : "+{v[32:63]}"(X0));
-    else if constexpr (NB == 2)
-      asm volatile("s_waitcnt vmcnt(0)\n\t" TAL_RUNP_0 TAL_RUNP_1 : "+{v[32:63]}"(X0), "+{v[64:95]}"(X1));
-    else if constexpr (NB == 3)
-      asm volatile("s_waitcnt vmcnt(0)\n\t" TAL_RUNP_0 TAL_RUNP_1 TAL_RUNP_2
-                   : "+{v[32:63]}"(X0), "+{v[64:95]}"(X1), "+{v[96:127]}"(X2));
-    else
-      asm volatile("s_waitcnt vmcnt(0)\n\t" TAL_RUNP_0 TAL_RUNP_1 TAL_RUNP_2 TAL_RUNP_3
-                   : "+{v[32:63]}"(X0), "+{v[64:95]}"(X1), "+{v[96:127]}"(X2), "+{v[128:159]}"(X3));
-  }
-}
-
-// Operands come in RECORDS of 16 dwords, one per trip of a row pair (A, B): {A's four register
-// offsets, B's four, A's four fp32 weights, B's four}; a register offset is 2 x the source's slot
-// in the group, and a row with fewer operands than its trips hold is padded with the NEUTRAL
-// operand (offset 32 x NB: the register pair held at -0.0 past the sources, weight +0.0), whose
-// product -0.0 leaves any accumulator unchanged (x + -0 = x, also for x = +0 and NaN; fma(0,
-// -0, x) = x).  A pair's trips run as ONE inline-asm loop: the next record is read into the
-// other half of s[40:71] (s_load_dwordx16) while the current one computes, so a trip is one
-// scalar load, the index switch per operand and four loop instructions — no copies, no address
-// arithmetic per operand (v3's per-operand SALU stream was the kernel's limit).  A weight
-// reaches the packed multiply as a 64-bit SGPR pair: op_sel_hi:[1,0] broadcasts its low dword,
-// op_sel:[0,1] op_sel_hi:[1,1] its high dword.  The two rows' chains are interleaved, so no
-// packed instruction reads the result of the one right before it (gfx950 needs a wait state
-// there).  M0, which the index mode writes, is used by nothing else in this kernel (no LDS).
-
-// one trip: i* / j* = A's / B's index SGPRs, wa* / wb* = their weight pairs
-#define TAL_TRIP_E(i0, i1, i2, i3, j0, j1, j2, j3, wa01, wa23, wb01, wb23)                            \
-  "s_set_gpr_idx_on " i0 ", gpr_idx(SRC0)\n\t"                                                          \
-  "v_pk_mul_f32 %[t0], v[32:33], " wa01 " op_sel_hi:[1,0]\n\t"                                          \
-  "s_set_gpr_idx_idx " j0 "\n\tv_pk_mul_f32 %[t4], v[32:33], " wb01 " op_sel_hi:[1,0]\n\t"              \
-  "s_set_gpr_idx_idx " i1 "\n\tv_pk_mul_f32 %[t1], v[32:33], " wa01 " op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
-  "s_set_gpr_idx_idx " j1 "\n\tv_pk_mul_f32 %[t5], v[32:33], " wb01 " op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
-  "s_set_gpr_idx_idx " i2 "\n\tv_pk_mul_f32 %[t2], v[32:33], " wa23 " op_sel_hi:[1,0]\n\t"              \
-  "s_set_gpr_idx_idx " j2 "\n\tv_pk_mul_f32 %[t6], v[32:33], " wb23 " op_sel_hi:[1,0]\n\t"              \
-  "s_set_gpr_idx_idx " i3 "\n\tv_pk_mul_f32 %[t3], v[32:33], " wa23 " op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
-  "s_set_gpr_idx_idx " j3 "\n\tv_pk_mul_f32 %[t7], v[32:33], " wb23 " op_sel:[0,1] op_sel_hi:[1,1]\n\t" \
-  "s_set_gpr_idx_off\n\t"                                                                               \
-  "v_pk_add_f32 %[ca], %[ca], %[t0]\n\tv_pk_add_f32 %[cb], %[cb], %[t4]\n\t"                            \
-  "v_pk_add_f32 %[ca], %[ca], %[t1]\n\tv_pk_add_f32 %[cb], %[cb], %[t5]\n\t"                            \
-  "v_pk_add_f32 %[ca], %[ca], %[t2]\n\tv_pk_add_f32 %[cb], %[cb], %[t6]\n\t"                            \
-  "v_pk_add_f32 %[ca], %[ca], %[t3]\n\tv_pk_add_f32 %[cb], %[cb], %[t7]\n\t"
-#define TAL_TRIP_F(i0, i1, i2, i3, j0, j1, j2, j3, wa01, wa23, wb01, wb23)                                          \
-  "s_set_gpr_idx_on " i0 ", gpr_idx(SRC0)\n\t"                                                                        \
-  "v_pk_fma_f32 %[ca], v[32:33], " wa01 ", %[ca] op_sel_hi:[1,0,1]\n\t"                                               \
-  "s_set_gpr_idx_idx " j0 "\n\tv_pk_fma_f32 %[cb], v[32:33], " wb01 ", %[cb] op_sel_hi:[1,0,1]\n\t"                   \
-  "s_set_gpr_idx_idx " i1 "\n\tv_pk_fma_f32 %[ca], v[32:33], " wa01 ", %[ca] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"    \
-  "s_set_gpr_idx_idx " j1 "\n\tv_pk_fma_f32 %[cb], v[32:33], " wb01 ", %[cb] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"    \
-  "s_set_gpr_idx_idx " i2 "\n\tv_pk_fma_f32 %[ca], v[32:33], " wa23 ", %[ca] op_sel_hi:[1,0,1]\n\t"                   \
-  "s_set_gpr_idx_idx " j2 "\n\tv_pk_fma_f32 %[cb], v[32:33], " wb23 ", %[cb] op_sel_hi:[1,0,1]\n\t"                   \
-  "s_set_gpr_idx_idx " i3 "\n\tv_pk_fma_f32 %[ca], v[32:33], " wa23 ", %[ca] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"    \
-  "s_set_gpr_idx_idx " j3 "\n\tv_pk_fma_f32 %[cb], v[32:33], " wb23 ", %[cb] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"    \
-  "s_set_gpr_idx_off\n\t"
-#define TAL_TRIP_P(TRIP) TRIP("s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s[48:49]", "s[50:51]", "s[52:53]", "s[54:55]")
-#define TAL_TRIP_Q(TRIP) TRIP("s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s[64:65]", "s[66:67]", "s[68:69]", "s[70:71]")
-// the pair loop over records at byte offsets off, off + 64, ... (from the table base), last =
-// off + 64 x trips: after a trip the offset register points one past the record being loaded,
-// i.e. at off + 64 (k + 2) after record k, and record k + 1 exists iff that is <= last
-#define TAL_PAIR_LOOP(TRIP)                                     \
-  "s_load_dwordx16 s[40:55], %[base], %[off]\n\t"                \
-  "s_add_u32 %[off], %[off], 64\n\t"                             \
-  "s_waitcnt lgkmcnt(0)\n"                                       \
-  "1:\n\t"                                                       \
-  "s_load_dwordx16 s[56:71], %[base], %[off]\n\t"                \
-  "s_add_u32 %[off], %[off], 64\n\t" TAL_TRIP_P(TRIP)           \
-  "s_cmp_le_u32 %[off], %[last]\n\t"                             \
-  "s_waitcnt lgkmcnt(0)\n\t"                                     \
-  "s_cbranch_scc0 2f\n\t"                                        \
-  "s_load_dwordx16 s[40:55], %[base], %[off]\n\t"                \
-  "s_add_u32 %[off], %[off], 64\n\t" TAL_TRIP_Q(TRIP)           \
-  "s_cmp_le_u32 %[off], %[last]\n\t"                             \
-  "s_waitcnt lgkmcnt(0)\n\t"                                     \
-  "s_cbranch_scc1 1b\n"                                          \
-  "2:"
-#define TAL_REC_CLOBBERS                                                                                    \
-  "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", \
-      "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68",     \
-      "s69", "s70", "s71", "scc"
-
-template <int NB, bool EXACT>
-__device__ __forceinline__ void reg_pair(v2f_t& ca, v2f_t& cb, uint64_t base, uint32_t off, uint32_t last,
-                                         const v32f& X0, const v32f& X1, const v32f& X2, const v32f& X3,
-                                         const v2f_t& Z) {
-#define TAL_PASM(TMPL, OUTS, ZR)                                                                             \
-  do {                                                                                                       \
-    if constexpr (NB == 1)                                                                                   \
-      asm volatile(TMPL : TAL_UNP OUTS : [base] "s"(base), [last] "s"(last), TAL_RX1, ZR(Z) : TAL_REC_CLOBBERS); \
-    else if constexpr (NB == 2)                                                                              \
-      asm volatile(TMPL : TAL_UNP OUTS : [base] "s"(base), [last] "s"(last), TAL_RX2, ZR(Z) : TAL_REC_CLOBBERS); \
-    else if constexpr (NB == 3)                                                                              \
-      asm volatile(TMPL : TAL_UNP OUTS : [base] "s"(base), [last] "s"(last), TAL_RX3, ZR(Z) : TAL_REC_CLOBBERS); \
-    else                                                                                                     \
-      asm volatile(TMPL : TAL_UNP OUTS : [base] "s"(base), [last] "s"(last), TAL_RX4, ZR(Z) : TAL_REC_CLOBBERS); \
-  } while (0)
-#define TAL_Z1 "{v[64:65]}"
-#define TAL_Z2 "{v[96:97]}"
-#define TAL_Z3 "{v[128:129]}"
-#define TAL_Z4 "{v[160:161]}"
-  if constexpr (EXACT) {
-    v2f_t t0, t1, t2, t3, t4, t5, t6, t7;
-#define TAL_OUTS_E                                                                                          \
-  ([ca] "+v"(ca), [cb] "+v"(cb), [off] "+s"(off), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),           \
-   [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6), [t7] "=&v"(t7))
-    if constexpr (NB == 1) TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_E), TAL_OUTS_E, TAL_Z1);
-    else if constexpr (NB == 2) TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_E), TAL_OUTS_E, TAL_Z2);
-    else if constexpr (NB == 3) TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_E), TAL_OUTS_E, TAL_Z3);
-    else TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_E), TAL_OUTS_E, TAL_Z4);
-#undef TAL_OUTS_E
-  } else {
-#define TAL_OUTS_F ([ca] "+v"(ca), [cb] "+v"(cb), [off] "+s"(off))
-    if constexpr (NB == 1) TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_F), TAL_OUTS_F, TAL_Z1);
-    else if constexpr (NB == 2) TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_F), TAL_OUTS_F, TAL_Z2);
-    else if constexpr (NB == 3) TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_F), TAL_OUTS_F, TAL_Z3);
-    else TAL_PASM(TAL_PAIR_LOOP(TAL_TRIP_F), TAL_OUTS_F, TAL_Z4);
-#undef TAL_OUTS_F
-  }
-#undef TAL_Z1
-#undef TAL_Z2
-#undef TAL_Z3
-#undef TAL_Z4
-#undef TAL_PASM
-}
-
-// Output stores with sc1: the line leaves the XCD's L2 instead of staying there (plain / nt
-// stores keep it), so the outputs do not push the sources the other groups of the piece are
-// about to read out of L2 (MI355X_MICROARCH.md, store flavours).
-template <typename T>
-__device__ __forceinline__ void reg_store(T* pout, int64_t ld_out, int32_t row, int64_t col, int64_t n, v2f_t acc) {
-  if (col >= n) return;
-  const int64_t e = static_cast<int64_t>(row) * ld_out + col;
-  if constexpr (kIsBf16<T>) {
-    uint32_t q = cvt_bf16x2(acc.x, acc.y);
-    if (__builtin_isunordered(acc.x, acc.y)) q = store_bf16x2(acc.x, acc.y);
-    if (col + 1 < n) asm volatile("global_store_dword %0, %1, off sc1" : : "v"(pout + e), "v"(q) : "memory");
-    else pout[e] = static_cast<uint16_t>(q & 0xffffu);
-  } else {
-    if (col + 1 < n) asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(pout + e), "v"(acc) : "memory");
-    else pout[e] = acc.x;
-  }
-}
-
-// Table (int32, device): groups [G][4] {first source, sources, first pair, pairs}; at off_src
-// the source pool rows (each group's list padded to 16 x NB entries; src_off = their byte
-// offsets in the pool); at off_pairs (a multiple of 4) pair records [P][4] {out row A, out row
-// B or -1, trips, byte offset of the first trip record}, a group's pairs consecutive; at off_rec
-// (a multiple of 16) the trip records [T][16], followed by one record of padding (the loop reads
-// one record ahead).
-template <int NB, typename T, bool EXACT>
-__global__ __launch_bounds__(256) void k_round_reg(const T* __restrict__ pin, T* __restrict__ pout, int64_t ld_out,
-                                                   int64_t n, const int32_t* __restrict__ table,
-                                                   const int64_t* __restrict__ src_off, int32_t n_groups,
-                                                   int32_t off_pairs, int32_t n_pieces,
-                                                   int32_t* __restrict__ ticket) {
-  constexpr bool kB = kIsBf16<T>;
-  constexpr int kEs = kB ? 2 : 4;
-  const ConstI32 tab = (ConstI32)table;
-  const ConstU64 soff = (ConstU64)src_off;
-  const uint64_t base = reinterpret_cast<uint64_t>(table);
-  const int lane = threadIdx.x & 63;
-  const int label = static_cast<int>(blockIdx.x & 7u);
-  const int pieces_l = n_pieces > label ? (n_pieces - 1 - label) / 8 + 1 : 0;
-  const int items = pieces_l * n_groups;
-  // Items are dealt in order by a per-label ticket counter (one atomic per item), so the items in
-  // flight on an XCD stay a window of consecutive pieces: with a static round-robin the waves
-  // drift apart over thousands of items and the groups of one piece no longer meet in L2
-  // (profiles/r03/k3r: HBM reads 3.9x -> 1.0-1.5x the algorithmic bytes).  The next ticket is
-  // taken once the current item's sources have arrived, not when the item starts: a ticket held
-  // for a whole item spreads a piece's groups over two item times, and the window (pieces whose
-  // sources must stay in L2) doubles past the 4 MB L2.
-  int32_t* my_ticket = ticket + 16 * label;  // 64 B apart
-  auto take = [&]() {
-    int t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return __builtin_amdgcn_readfirstlane(t);
-  };
-  const v2f_t zn = {-0.f, -0.f};  // the neutral operand's register pair
-  int s_next = take();
-  v32f X0, X1, X2, X3;
-  for (;;) {
-    const int s = s_next;
-    if (s >= items) break;
-    const int q = s / n_groups, g = s - q * n_groups;
-    const int piece = q * 8 + label;
-    const int s0 = tab[4 * g], p0 = tab[4 * g + 2], np = tab[4 * g + 3];
-    const int64_t col = static_cast<int64_t>(piece) * kRegPiece + 2 * lane;
-    const uint32_t loff = col < n ? static_cast<uint32_t>(2 * lane * kEs) : 0u;  // past n: the piece's start
-    const uint64_t pbase = reinterpret_cast<uint64_t>(pin) + static_cast<uint64_t>(piece) * (kRegPiece * kEs);
-    uint64_t b[16];
-    // each block's 16 source offsets come in two 8-dword scalar loads, one wait
-#define TAL_RBASES(J)                                                                            \
-    _Pragma("unroll") for (int k = 0; k < 16; ++k)                                               \
-      b[k] = pbase + static_cast<uint64_t>(soff[s0 + (J) * 16 + k]);
-    TAL_RBASES(0)
-    X0 = reg_load_block<0, kB>(b, loff);
-    if constexpr (NB > 1) { TAL_RBASES(1) X1 = reg_load_block<1, kB>(b, loff); }
-    if constexpr (NB > 2) { TAL_RBASES(2) X2 = reg_load_block<2, kB>(b, loff); }
-    if constexpr (NB > 3) { TAL_RBASES(3) X3 = reg_load_block<3, kB>(b, loff); }
-#undef TAL_RBASES
-    reg_wait<NB, kB>(X0, X1, X2, X3);
-    s_next = take();
-    for (int p = 0; p < np; ++p) {
-      const u32x4 pr = ((const __attribute__((address_space(4))) u32x4*)(tab + off_pairs))[p0 + p];
-      v2f_t ca = {-0.f, -0.f}, cb = {-0.f, -0.f};
-      const uint32_t off = pr[3];
-      const uint32_t last = off + 64u * pr[2];  // the loop goes on while (next record's offset + 64) <= last
-      reg_pair<NB, EXACT>(ca, cb, base, off, last, X0, X1, X2, X3, zn);
-      reg_store<T>(pout, ld_out, static_cast<int32_t>(pr[0]), col, n, ca);
-      if (static_cast<int32_t>(pr[1]) >= 0) reg_store<T>(pout, ld_out, static_cast<int32_t>(pr[1]), col, n, cb);
-    }
-  }
-}
-
-// The register round's item tickets: eight counters 64 B apart, one per XCD label, reset on the
-// stream before each launch.  One buffer per (device, stream): launches on one stream are
-// ordered, so they never share counters with a launch in flight elsewhere (two streams sharing
-// one buffer could reset or advance each other's counters and skip items).  The library's only
-// device allocations: 512 B per (device, stream) used, made on first use.
-constexpr size_t kRegTicketBytes = 8 * 64;
-
-int32_t reg_tickets(hipStream_t stream, int32_t** out) {
-  static std::mutex mu;
-  static std::vector<std::tuple<int, hipStream_t, int32_t*>> bufs;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return fail(TAL_ERR_HIP, "register round: no current device");
-  std::lock_guard<std::mutex> lk(mu);
-  for (const auto& b : bufs)
-    if (std::get<0>(b) == dev && std::get<1>(b) == stream) {
-      *out = std::get<2>(b);
-      return TAL_OK;
-    }
-  void* p = nullptr;
-  if (hipMalloc(&p, kRegTicketBytes) != hipSuccess) return fail(TAL_ERR_HIP, "register round: ticket allocation failed");
-  bufs.emplace_back(dev, stream, static_cast<int32_t*>(p));
-  *out = static_cast<int32_t*>(p);
-  return TAL_OK;
-}
-
-// Compute units of the current device, asked once per device (thread-safe).
-int32_t device_cus(int* n_cu) {
-  static std::mutex mu;
-  static std::vector<int> per_dev;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return fail(TAL_ERR_HIP, "no current device");
-  std::lock_guard<std::mutex> lk(mu);
-  if (per_dev.size() <= static_cast<size_t>(dev)) per_dev.resize(dev + 1, 0);
-  if (per_dev[dev] == 0 &&
-      hipDeviceGetAttribute(&per_dev[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return fail(TAL_ERR_HIP, "multiprocessor count query failed");
-  *n_cu = per_dev[dev];
-  return TAL_OK;
-}
-
-template <int NB, typename T, bool EXACT>
-int32_t launch_round_reg_nb(const T* pin, T* pout, int64_t ld_out, int64_t n, const int32_t* table,
-                            const int64_t* src_off, int32_t n_groups, int32_t off_pairs, int32_t n_pieces,
-                            hipStream_t s) {
-  int n_cu = 0;
-  if (int32_t rc = device_cus(&n_cu)) return rc;
-  // resident workgroups per CU: cached per kernel under a mutex (resident_per_cu)
-  const int blocks_per_cu = resident_per_cu(reinterpret_cast<const void*>(k_round_reg<NB, T, EXACT>), 256, 0);
-  // persistent: every resident wave (TAL_REG_BLOCKS_PER_CU caps it: A/B probes of how many
-  // pieces are in flight per XCD), a multiple of 8 blocks (XCD labels)
-  int bpc = blocks_per_cu;
-  if (const char* e = getenv("TAL_REG_BLOCKS_PER_CU")) bpc = std::max(1, std::min(bpc, atoi(e)));
-  const int grid = std::max(8, n_cu * bpc / 8 * 8);
-  int32_t* ticket = nullptr;
-  if (int32_t rc = reg_tickets(s, &ticket)) return rc;
-  if (hipMemsetAsync(ticket, 0, kRegTicketBytes, s) != hipSuccess)
-    return fail(TAL_ERR_HIP, "register round: ticket reset failed");
-  k_round_reg<NB, T, EXACT><<<grid, 256, 0, s>>>(pin, pout, ld_out, n, table, src_off, n_groups, off_pairs, n_pieces,
-                                                 ticket);
-  return check_launch("register round kernel");
-}
-
-template <typename T, bool EXACT>
-int32_t launch_round_reg(const T* pin, T* pout, int64_t ld_out, int64_t n, const int32_t* table,
-                         const int64_t* src_off, int32_t n_groups, int32_t off_pairs, int32_t max_src, hipStream_t s) {
-  const int64_t n_pieces = (n + kRegPiece - 1) / kRegPiece;
-  if (n_pieces * n_groups >= (1LL << 31)) return fail(TAL_ERR_INVALID, "register round: too many items");
-  const int np = static_cast<int>(n_pieces);
-#define TAL_REG_NB(NBV) launch_round_reg_nb<NBV, T, EXACT>(pin, pout, ld_out, n, table, src_off, n_groups, off_pairs, np, s)
-  if (max_src <= 16) return TAL_REG_NB(1);
-  if (max_src <= 32) return TAL_REG_NB(2);
-  if (max_src <= 48) return TAL_REG_NB(3);
-  return TAL_REG_NB(4);
-#undef TAL_REG_NB
-}
-
 template <int NT, bool EXACT>
 int32_t launch_round_stream_nt(const float* pin, int64_t ld_in, float* pout, int64_t ld_out, int64_t n4,
                                const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
@@ -5448,38 +5017,6 @@ int32_t tal_agg_round_clique_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint
                                     int32_t mode, void* stream, const float* wtab_dev) {
   return agg_round_clique<uint16_t, true>("tal_agg_round_clique_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
                                           table_dev, n_cliques, mmax, mode, stream, wtab_dev);
-}
-
-int32_t tal_agg_round_reg(const void* pool_in, int64_t ld_in, void* pool_out, int64_t ld_out, int64_t n,
-                          int32_t bf16, const int32_t* table_dev, const int64_t* src_off_dev, int32_t n_groups,
-                          int32_t off_src, int32_t off_pairs, int32_t off_rec, int32_t max_src, int32_t mode,
-                          void* stream) {
-  if (!pool_in || !pool_out || !table_dev || !src_off_dev)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: null pointer");
-  if (pool_in == pool_out)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: the register round runs out of place (snapshot semantics)");
-  const int64_t n2 = n + (n & 1);  // the last lane of an odd row reads one element of padding
-  if (n < 0 || ld_in < n2 || ld_out < n2 || ld_in % 2 || ld_out % 2)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: need even ld >= n rounded up to even");
-  if (n_groups < 0 || max_src < 1 || max_src > kRegMaxSrc || off_src < 4 * n_groups || off_pairs % 4 ||
-      off_rec % 16 || off_pairs < off_src || off_rec < off_pairs)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: bad table layout");
-  if (bf16 && mode == TAL_MODE_EXACT)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: bf16 rounds take FMA mode here (EXACT: tal_agg_round_bf16)");
-  if (bf16 ? !aligned4(pool_in) || !aligned4(pool_out) : !aligned8(pool_in) || !aligned8(pool_out))
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: pools must be aligned to 2 elements");
-  if (reinterpret_cast<uintptr_t>(table_dev) % 64)
-    return fail(TAL_ERR_INVALID, "tal_agg_round_reg: table must be 64-B aligned");
-  if (n == 0 || n_groups == 0) { g_err.clear(); return TAL_OK; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (bf16)
-    return launch_round_reg<uint16_t, false>(static_cast<const uint16_t*>(pool_in), static_cast<uint16_t*>(pool_out),
-                                             ld_out, n, table_dev, src_off_dev, n_groups, off_pairs, max_src, s);
-  if (mode == TAL_MODE_EXACT)
-    return launch_round_reg<float, true>(static_cast<const float*>(pool_in), static_cast<float*>(pool_out), ld_out, n,
-                                         table_dev, src_off_dev, n_groups, off_pairs, max_src, s);
-  return launch_round_reg<float, false>(static_cast<const float*>(pool_in), static_cast<float*>(pool_out), ld_out, n,
-                                        table_dev, src_off_dev, n_groups, off_pairs, max_src, s);
 }
 
 int32_t tal_agg_bf16(const uint16_t* const* x_host, const double* w_host, int32_t m, uint16_t* out,

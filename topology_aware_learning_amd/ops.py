@@ -592,199 +592,6 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
                       col_mmax=max((len(c[0]) for c in wide), default=0))
 
 
-REG_MAX_SRC = 64   # sources per register group (v[32:160): 64 x 2 fp32 per lane)
-REG_WINDOW = 64    # rows considered when growing a group
-
-
-@dataclass
-class RegPlan:
-    """A round as register-resident source groups (K3r, tal_agg_round_reg): rows grouped so that
-    each group's operands are <= max_src distinct sources, a group's rows run in pairs whose
-    operands come in trip records of four per row.  `full` is a sparse plan over all rows for
-    the int64 segment (and bf16 EXACT, which K3r does not take)."""
-    table: np.ndarray
-    n_groups: int
-    off_src: int
-    off_pairs: int
-    off_rec: int
-    max_src: int
-    group_sources: int   # sum over groups of their sources (L2 reads per column)
-    full: RoundPlan
-    rows: int
-    trips: int = 0       # trip records (16 dwords each; 8 operand slots, padding included)
-    device: Optional[torch.Tensor] = None
-    tuned_ms: Optional[float] = None
-    candidates: Optional[list] = None
-    spec: Optional[dict] = None
-
-    @property
-    def info(self) -> RoundPlanInfo:
-        return self.full.info
-
-    @property
-    def single_group(self) -> bool:
-        return False  # groups read other groups' output rows: never in place
-
-    def staged_rows(self) -> int:
-        """Distinct sources read per column: every source once (the groups sharing a source
-        are served by L2 on the XCD their piece runs on)."""
-        return int(len(np.unique(self.table[self.off_src: self.off_pairs])))
-
-    def pair_records(self) -> np.ndarray:
-        """[P, 4] {out row A, out row B or -1, trips, byte offset of the first trip record}."""
-        return self.table[self.off_pairs: self.off_rec].reshape(-1, 4)[:self.n_pairs]
-
-    @property
-    def n_pairs(self) -> int:
-        g = self.table[: 4 * self.n_groups].reshape(-1, 4)
-        return int(g[:, 3].sum())
-
-    def to(self, device) -> "RegPlan":
-        self.device = torch.from_numpy(self.table).to(device)
-        self.full.to(device)
-        self._src_off = {}
-        return self
-
-    def src_offsets(self, pitch_bytes: int, device) -> torch.Tensor:
-        """Device int64 byte offsets (row x pitch) of the source list's entries, once per pool
-        pitch: the kernel adds them to the piece's base instead of multiplying per source."""
-        cache = self.__dict__.setdefault("_src_off", {})
-        key = (int(pitch_bytes), str(device))
-        t = cache.get(key)
-        if t is None:
-            rows = self.table[self.off_src: self.off_src + 16 * ((self.max_src + 15) // 16) * self.n_groups]
-            t = cache[key] = torch.from_numpy(rows.astype(np.int64) * int(pitch_bytes)).to(device)
-        return t
-
-
-REG_TRIP = 4        # operands of each row per trip record
-REG_REC_WORDS = 16  # {A idx x4, B idx x4, A w x4, B w x4}
-
-
-def reg_groups(row_ptr, col, max_src: int = REG_MAX_SRC, window: int = REG_WINDOW):
-    """Rows grouped greedily: a group starts at the first unassigned row and repeatedly takes,
-    among the next `window` unassigned rows, the one adding the fewest new sources while the
-    union stays <= max_src.  Returns [(rows, sources ascending)]."""
-    n = len(row_ptr) - 1
-    ops_ = [set(col[row_ptr[r]: row_ptr[r + 1]].tolist()) for r in range(n)]
-    left = list(range(n))
-    groups = []
-    while left:
-        r0 = left.pop(0)
-        if len(ops_[r0]) > max_src:
-            raise ValueError(f"row {r0} has {len(ops_[r0])} distinct sources > {max_src}")
-        cur, src = [r0], set(ops_[r0])
-        while True:
-            best = None
-            for r in left[:window]:
-                add = len(ops_[r] - src)
-                if len(src) + add <= max_src and (best is None or add < best[0]):
-                    best = (add, r)
-            if best is None:
-                break
-            left.remove(best[1])
-            cur.append(best[1])
-            src |= ops_[best[1]]
-        groups.append((cur, sorted(src)))
-    return groups
-
-
-def build_reg_plan(row_ptr, col, w, out_row, max_src: int = REG_MAX_SRC) -> Optional[RegPlan]:
-    """RegPlan of a round (table layout: tal_agg.h K3r), or None when a row has more than
-    max_src distinct sources.  Inside a group the rows are ordered by operand count
-    (descending) and paired in that order, so a pair's rows need about the same number of
-    trips; the shorter row (and a lone last row's partner) is padded with the neutral operand
-    (register offset 32 x NB, weight +0.0)."""
-    row_ptr, col, w = row_ptr.astype(np.int32), col.astype(np.int32), np.asarray(w, np.float64)
-    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
-    try:
-        groups = reg_groups(row_ptr, col, max_src)
-    except ValueError:
-        return None
-    G = len(groups)
-    nb = (max(len(s_) for _, s_ in groups) + 15) // 16
-    span, neutral = 16 * nb, 32 * nb
-    w32all = w.astype(np.float32).view(np.uint32)
-    src_list, pairs, recs = [], [], []
-    grp = np.zeros((G, 4), np.int32)
-
-    def lists(r, slot):
-        if r is None:
-            return [], []
-        q0, q1 = int(row_ptr[r]), int(row_ptr[r + 1])
-        return [2 * slot[int(c)] for c in col[q0:q1]], [int(x) for x in w32all[q0:q1]]
-
-    for g, (rows, srcs) in enumerate(groups):
-        slot = {s_: k for k, s_ in enumerate(srcs)}
-        rows = sorted(rows, key=lambda r: -(row_ptr[r + 1] - row_ptr[r]))
-        grp[g] = (len(src_list), len(srcs), len(pairs), (len(rows) + 1) // 2)
-        src_list.extend(srcs + [srcs[0]] * (span - len(srcs)))  # padding reloads the first source
-        for k in range(0, len(rows), 2):
-            ra, rb = rows[k], rows[k + 1] if k + 1 < len(rows) else None
-            ia, wa = lists(ra, slot)
-            ib, wb = lists(rb, slot)
-            trips = (max(len(ia), len(ib)) + REG_TRIP - 1) // REG_TRIP
-            pad = REG_TRIP * trips
-            ia, wa = ia + [neutral] * (pad - len(ia)), wa + [0] * (pad - len(wa))
-            ib, wb = ib + [neutral] * (pad - len(ib)), wb + [0] * (pad - len(wb))
-            pairs.append([int(out_row[ra]), -1 if rb is None else int(out_row[rb]), trips, len(recs)])
-            for t in range(trips):
-                sl = slice(REG_TRIP * t, REG_TRIP * (t + 1))
-                recs.append(ia[sl] + ib[sl] + wa[sl] + wb[sl])
-    off_src = 4 * G
-    off_pairs = (off_src + len(src_list) + 3) // 4 * 4
-    off_rec = (off_pairs + 4 * len(pairs) + 15) // 16 * 16
-    words = off_rec + REG_REC_WORDS * (len(recs) + 1)  # + one record read ahead by the loop
-    table = np.zeros(words, np.int32)
-    table[:off_src] = grp.reshape(-1)
-    table[off_src: off_src + len(src_list)] = src_list
-    pr = np.asarray(pairs, np.int64)
-    pr[:, 3] = 4 * (off_rec + REG_REC_WORDS * pr[:, 3])  # byte offsets from the table base
-    table[off_pairs: off_pairs + 4 * len(pairs)] = pr.astype(np.int32).reshape(-1)
-    table[off_rec: off_rec + REG_REC_WORDS * len(recs)] = \
-        np.asarray(recs, np.uint32).view(np.int32).reshape(-1)
-    return RegPlan(table=table, n_groups=G, off_src=off_src, off_pairs=off_pairs, off_rec=off_rec,
-                   max_src=max(len(s_) for _, s_ in groups), group_sources=sum(len(s_) for _, s_ in groups),
-                   full=build_plan(row_ptr, col, w, out_row, dense=0), rows=len(out_row), trips=len(recs))
-
-
-def _round_reg(pool_in, pool_out, plan: RegPlan, n, dtype, mode, stream):
-    _require_gpu(pool_in, "pool_in", dtype)
-    _require_gpu(pool_out, "pool_out", dtype)
-    if pool_in.dim() != 2 or pool_out.dim() != 2:
-        raise ValueError("pools must be 2-D [models, ld]")
-    if pool_in.device != pool_out.device:
-        raise ValueError("pools on different devices")
-    if pool_in.data_ptr() == pool_out.data_ptr():
-        raise ValueError("a register round runs out of place (snapshot semantics)")
-    n = pool_in.shape[1] if n is None else int(n)
-    bf16 = dtype == torch.bfloat16
-    esz = pool_in.element_size()
-    pad = n + (n & 1)
-    if (bf16 and mode == MODE_EXACT) or pool_in.stride(0) % 2 or pool_out.stride(0) % 2 \
-            or pool_in.shape[1] < pad or pool_out.shape[1] < pad \
-            or (pool_in.data_ptr() | pool_out.data_ptr()) % (2 * esz):
-        # K3r reads and writes 2-element pairs and runs bf16 in FMA mode only: other pools and
-        # bf16 EXACT take the full plan
-        return _round(pool_in, pool_out, plan.full, n, dtype, mode, stream)
-    if plan.device is None or plan.device.device != pool_in.device:
-        plan.to(pool_in.device)
-    t = plan.table
-    if t[plan.off_src: plan.off_pairs].max(initial=-1) >= pool_in.shape[0]:
-        raise ValueError("plan reads a pool row beyond pool_in")
-    if plan.pair_records()[:, :2].max(initial=-1) >= pool_out.shape[0]:
-        raise ValueError("plan writes a pool row beyond pool_out")
-    L = _lib.load()
-    offs = plan.src_offsets(pool_in.stride(0) * esz, pool_in.device)
-    check(L.tal_agg_round_reg(ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0),
-                              ctypes.c_void_p(pool_out.data_ptr()), pool_out.stride(0), n, int(bf16),
-                              ctypes.c_void_p(plan.device.data_ptr()), ctypes.c_void_p(offs.data_ptr()),
-                              plan.n_groups, plan.off_src,
-                              plan.off_pairs, plan.off_rec, plan.max_src, int(mode),
-                              _stream(pool_in.device, stream)))
-    return pool_out
-
-
 def _sub_csr(row_ptr, col, w, out_row, rows):
     """The CSR of a subset of a round's rows."""
     rp = np.concatenate([[0], np.cumsum([row_ptr[r + 1] - row_ptr[r] for r in rows])]).astype(np.int32)
@@ -899,9 +706,10 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     staging stays within 1.25 x the fewest staged sources of any candidate (multi-group plans
     that re-read sources - config 3's 80 KiB c4 = 128 plan stages 3.7x - never won), the
     broadcast forms that won (BCAST_CANDIDATES) on rounds with per-operand weights, and the
-    clique plan (tune_candidates).  Dense row blocks, the streamed form and the
-    register-resident groups lost every measured A/B outside their probes (BENCH_r04: 5.9, 7.0
-    and 8.5-16 ms against 2.0 ms on config 3) and are built only on request (plan_from_spec).
+    clique plan (tune_candidates).  Dense row blocks and the streamed form lost every measured
+    A/B outside their probes (BENCH_r04: 5.9 and 7.0 ms against 2.0 ms on config 3) and are
+    built only on request (plan_from_spec); the register-resident groups (K3r: 8.5-16 ms on
+    that round) lost too and were removed.
 
     Each candidate runs `reps` times, interleaved rep by rep with the others, and is judged by
     its median; one slower than TUNE_DROP x the default on its first timed run is not timed
@@ -962,11 +770,9 @@ def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
         p.spec = dict(spec)
         return p
     if spec.get("reg"):
-        p = build_reg_plan(row_ptr, col, w, out_row, int(spec.get("max_src", REG_MAX_SRC)))
-        if p is None:
-            raise ValueError("plan spec asks for register groups but a row has too many sources")
-        p.spec = dict(spec)
-        return p
+        raise ValueError('plan spec asks for "reg": the register-resident form (K3r) was removed; a spec can ask '
+                         'for "clique" / "wclique", "rows_k1", "stream_rows" with "stream_src", or "c4", "lds" and '
+                         '"dense" (with "bcast" and "bcwg" for the broadcast form)')
     if "rows_k1" in spec:
         return row_call_plan(row_ptr, col, w, out_row)
     if "stream_rows" in spec:
@@ -1013,8 +819,8 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     broadcast form with the whole source set in one LDS tile — for bf16 in FMA mode the
     two-chunk form (c4 = 32, 16 wavefronts, one workgroup per CU; config 5 with
     degree-centrality weights: 23.0-23.3 ms against 23.7-24.4 for the 16 x 2 form, 32.1-32.6 for
-    the pairs form and 29.8-30.1 for the register-resident K3r, which round 3 picked;
-    profiles/r04/r04j, profiles/r04/pmc), for fp32 8 wavefronts x 2 (38.2-42.2 ms against 46.0
+    the pairs form and 29.8-30.1 for the register-resident K3r, which round 3 picked and which
+    has since been removed; profiles/r04/r04j, profiles/r04/pmc), for fp32 8 wavefronts x 2 (38.2-42.2 ms against 46.0
     for the cost model's two-group pairs plan; profiles/r04/r04f).  The broadcast plan is taken
     only when it has no more groups than the sparse plan; RoundExecutor runs a single-group
     plan (config 5's: every source in one tile) in place and a multi-group one through its
@@ -1078,8 +884,6 @@ def round_kernel_name(plan, bf16: bool = False) -> str:
     clique plans name the K3c kernel (their rest rows run a second one)."""
     if isinstance(plan, CliquePlan):
         return "k_round_clique" if plan.n_cliques > 0 else "k_round_clique_col"
-    if isinstance(plan, RegPlan):
-        return "k_round_reg"
     if isinstance(plan, RowCallPlan):
         return "k_agg (one call per row)"
     info = plan.info if isinstance(plan, RoundPlan) else plan
@@ -1109,8 +913,6 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
     its clique blocks with K3c and its other rows with their regular plan (out of place)."""
     if isinstance(plan, CliquePlan):
         return _round_clique(pool_in, pool_out, plan, n, torch.float32, mode, stream)
-    if isinstance(plan, RegPlan):
-        return _round_reg(pool_in, pool_out, plan, n, torch.float32, mode, stream)
     if isinstance(plan, RowCallPlan):
         return _round_rows(pool_in, pool_out, plan, n, torch.float32, mode, stream)
     return _round(pool_in, pool_out, plan, n, torch.float32, mode, stream)
@@ -1171,7 +973,7 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
 
 def round_i64(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n: Optional[int] = None,
               stream=None) -> torch.Tensor:
-    if isinstance(plan, (CliquePlan, RegPlan)):
+    if isinstance(plan, CliquePlan):
         plan = plan.full
     if isinstance(plan, RowCallPlan):
         return _round_rows(pool_in, pool_out, plan, n, torch.int64, MODE_EXACT, stream)
@@ -1188,8 +990,6 @@ def round_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n
     which has no alignment rule."""
     if isinstance(plan, CliquePlan):
         return _round_clique(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
-    if isinstance(plan, RegPlan):
-        return _round_reg(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
     if isinstance(plan, RowCallPlan):
         return _round_rows(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
     return _round(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
