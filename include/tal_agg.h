@@ -58,7 +58,8 @@ extern "C" {
 const char* tal_last_error(void);
 /* ABI version (bumped on any signature change).  ABI 33 removed the round over
  * register-resident source groups (K3r) with its entry point: no plan the library picks ever
- * selected it. */
+ * selected it.  ABI 34 added the column clique entries with per-source weights
+ * (tal_agg_round_clique_col_w_*). */
 int32_t tal_abi_version(void);
 
 /* ---- K1: one aggregation call over M flattened operands --------------------------------
@@ -339,6 +340,33 @@ int32_t tal_agg_round_clique_col_f32(const float* pool_in, int64_t ld_in, float*
 int32_t tal_agg_round_clique_col_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,
                                       int64_t ld_out, int64_t n, const int32_t* table_dev,
                                       int32_t n_cliques, int32_t mmax, int32_t mode, void* stream);
+
+/* K3c1 with per-source weights (ABI 34): the weighted and centrality apps on a clique of 65..128
+ * members (`weighted_module_avg` over 66 or 100 clients is one such block).  The column entries'
+ * chains with w_j in place of w: EXACT p_j = fl(w_j * x_j) (bf16: rounded to bf16, as is every
+ * step of a chain), then row i = ((S_i + p_{i+1}) + ... + p_{m-1}) + p_i; FMA acc = fma(w_j, x_j,
+ * acc) along the same chains from -0.0 (bf16 rounded once at the store, NaN stored as 0xFFFF).
+ * Zero and negative weights are ordinary values.  table_dev is the TAL_CLIQUE_COL_WORDS record
+ * above; its weight word is ignored.  wtab_dev: n_cliques records of TAL_CLIQUE_COL_WWORDS floats
+ * on the device, w[j] = the weight of src_row[j]; every slot not in use holds 1.0f (a padding
+ * step is x = -0.0 under weight 1.0 in both modes: fl(1 * -0.0) = -0.0, fma(1, -0.0, acc) = acc
+ * for every acc, -0.0 included).  Blocks of any m <= 128 are legal (m <= 64 gives the bits of
+ * tal_agg_round_clique_w_*; all weights equal gives those of tal_agg_round_clique_col_*).  Same
+ * checks and errors as the column entries, and TAL_ERR_INVALID, with no launch, for a null
+ * wtab_dev. */
+#define TAL_CLIQUE_COL_WWORDS 128
+#if defined(__cplusplus)
+static_assert(TAL_CLIQUE_COL_WWORDS == TAL_CLIQUE_COL_MAX, "column-form weight record: one float per member");
+#else
+_Static_assert(TAL_CLIQUE_COL_WWORDS == TAL_CLIQUE_COL_MAX, "column-form weight record: one float per member");
+#endif
+int32_t tal_agg_round_clique_col_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                       int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                       int32_t mode, void* stream, const float* wtab_dev);
+int32_t tal_agg_round_clique_col_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,
+                                        int64_t ld_out, int64_t n, const int32_t* table_dev,
+                                        int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
+                                        const float* wtab_dev);
 
 /* The same round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or

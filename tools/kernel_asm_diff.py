@@ -2,6 +2,7 @@
 
     hipcc <build.py's HIPCC_FLAGS without -shared / -ldl> --cuda-device-only -S tal_agg.hip -o X.s
     python tools/kernel_asm_diff.py parent.s new.s [--show SUBSTRING ...] [--lists DIR]
+                                    [--rename REGEX REPLACEMENT ...]
 
 A kernel is everything from its "Begin function" line to the end of its "Kernel info" block:
 instructions, labels, the .amdhsa_ descriptor and the .set resource symbols.  Two kernels of
@@ -11,7 +12,10 @@ the functions before it in the file).  The resource lines of the "Kernel info" c
 VGPRs, AGPRs, scratch, LDS, occupancy) are compared separately.  Prints the kernels only one
 side has, the count of identical ones, a unified diff of each that differs, and the resources
 of the kernels whose name contains a --show substring; --lists writes kernels_parent.txt and
-kernels_new.txt (one symbol per line) into DIR.  Exit status 1 when a common kernel differs.
+kernels_new.txt (one symbol per line) into DIR.  --rename rewrites the parent's symbols (in the
+kernels' names and wherever their lines spell them) before the comparison: a kernel whose
+template or argument list grew is then held against the instantiation that took its place, and
+what still differs (the kernarg size, say) is printed.  Exit status 1 when a common kernel differs.
 """
 from __future__ import annotations
 
@@ -26,15 +30,18 @@ _LABEL = re.compile(r"\.(LBB|Lfunc_end|Lfunc_begin|Ltmp)\d+")
 _RES = ("TotalNumSgprs", "NumVgprs", "NumAgprs", "ScratchSize", "LDSByteSize", "Occupancy")
 
 
-def kernels(path: Path) -> dict:
+def kernels(path: Path, renames=()) -> dict:
     """{symbol: (normalized lines, {resource: value})} of every kernel in the listing."""
     out, name, lines, res, in_info = {}, None, [], {}, False
+    text = path.read_text()
+    for pat, repl in renames:
+        text = re.sub(pat, repl, text)
 
     def close():
         if name is not None and any(ln.startswith(".amdhsa_kernel ") for ln in lines):
             out[name] = (lines, res)
 
-    for raw in path.read_text().splitlines():
+    for raw in text.splitlines():
         m = _BEGIN.search(raw)
         if m:
             close()
@@ -65,8 +72,10 @@ def main() -> int:
     ap.add_argument("new", type=Path)
     ap.add_argument("--show", action="append", default=[], help="print the resources of kernels whose name contains this")
     ap.add_argument("--lists", type=Path, help="directory for kernels_parent.txt / kernels_new.txt")
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPLACEMENT"),
+                    help="rewrite the parent's symbols before comparing")
     args = ap.parse_args()
-    a, b = kernels(args.parent), kernels(args.new)
+    a, b = kernels(args.parent, args.rename), kernels(args.new)
     if args.lists:
         (args.lists / "kernels_parent.txt").write_text("".join(k + "\n" for k in a))
         (args.lists / "kernels_new.txt").write_text("".join(k + "\n" for k in b))

@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 EXPORTED = (
     "tal_last_error",
@@ -51,6 +51,8 @@ EXPORTED = (
     "tal_agg_round_clique_w_bf16",
     "tal_agg_round_clique_col_f32",
     "tal_agg_round_clique_col_bf16",
+    "tal_agg_round_clique_col_w_f32",
+    "tal_agg_round_clique_col_w_bf16",
     "tal_cosine_plan_words",
     "tal_cosine_plan_build",
     "tal_cosine_plan_set_threads",
@@ -195,6 +197,8 @@ _SIGS = {
     "tal_agg_round_clique_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_agg_round_clique_col_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_clique_col_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
+    "tal_agg_round_clique_col_w_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
+    "tal_agg_round_clique_col_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_cosine_plan_words": (_I64, [_PI64, _I32]),
     "tal_cosine_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),
     "tal_cosine_plan_set_threads": (_I32, [_PI64, _I32]),

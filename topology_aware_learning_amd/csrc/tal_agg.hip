@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 33;
+constexpr int kAbiVersion = 34;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -2546,13 +2546,22 @@ int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
 // so that a step of four rows is two packed operations whose second source broadcasts one half
 // of a pair (op_sel); as float p[MMAX] the compiler gave every product an aligned pair of its
 // own (2 MMAX registers: one wave per SIMD and scratch at MMAX 128).  One column per lane needs
-// no column-pair alignment: any ld, element-aligned pools, no odd-width tail.  No attached rows
-// and no per-source weights.
+// no column-pair alignment: any ld, element-aligned pools, no odd-width tail.  No attached rows.
 // A kernel of its own: k_round_clique's body is built on column pairs throughout (ld2 / st2,
 // the 8-wide chain vector, the attached rows' pair arithmetic and the lane-held weights).
+// WSRC: per-source weights (tal_agg_round_clique_col_w_*: source j carries the same fp32 weight
+// w_j in every row of the block).  The chains with w_j in place of w: EXACT p_j = fl(w_j * x_j),
+// FMA fma(w_j, x_j, acc); padding slots are x = -0.0 under the table's weight 1.0f in both modes
+// (fl(1 * -0.0) = -0.0, fma(1, -0.0, acc) = acc), not the uniform kernel's zero by the sign of w.
+// The weights (TAL_CLIQUE_COL_WWORDS floats per block) are wave-uniform and are read by batched
+// scalar loads through the constant address space next to their use - EXACT once at the product
+// stage, FMA at every chain step - so the vector unit runs the uniform kernel's steps and lanes
+// past n leave early as they do there.  The kernels without WSRC are the ones before it,
+// instruction for instruction.
 // ------------------------------------------------------------------------------------------
 constexpr int kCliqueColMax = TAL_CLIQUE_COL_MAX;
 static_assert(4 + 2 * kCliqueColMax == TAL_CLIQUE_COL_WORDS, "column-form table layout");
+static_assert(kCliqueColMax == TAL_CLIQUE_COL_WWORDS, "column-form weight table layout");
 
 template <typename T, bool EXACT>
 __device__ __forceinline__ float clique_term(float acc, float w, float p) {
@@ -2571,18 +2580,37 @@ __device__ __forceinline__ v4f clique_term4(v4f acc, float w, v4f p) {
   else return __builtin_elementwise_fma(v4f{w, w, w, w}, p, acc);
 }
 
+// The chains' last step under per-source weights: chain k takes its own term with its own weight.
+template <typename T, bool EXACT>
+__device__ __forceinline__ v4f clique_term4(v4f acc, float w0, float w1, float w2, float w3, v4f p) {
+  if constexpr (EXACT) return clique_term4<T, EXACT>(acc, w0, p);
+  else return __builtin_elementwise_fma(v4f{w0, w1, w2, w3}, p, acc);
+}
+
+// A block's weight record read through the constant address space: every read is a scalar load
+// (wave-uniform address), whatever the compiler can prove about the pointer.
+typedef const __attribute__((address_space(4))) float* clique_wptr;
+constexpr int kCliqueColWBatch = 16;  // weights per scalar load (one s_load_dwordx16 at most)
+
 // Column e of every row of clique block `t` (TAL_CLIQUE_COL_WORDS record).
-template <int MMAX, bool EXACT, typename T>
+// wtab (WSRC): TAL_CLIQUE_COL_WWORDS floats per block beside the table's record, else unused (null)
+template <int MMAX, bool EXACT, typename T, bool WSRC = false>
 __global__ __launch_bounds__(kBlock) void k_round_clique_col(const T* __restrict__ pin, int64_t ld_in,
                                                              T* __restrict__ pout, int64_t ld_out, int64_t n,
-                                                             const int32_t* __restrict__ table) {
+                                                             const int32_t* __restrict__ table,
+                                                             const float* __restrict__ wtab) {
   static_assert(MMAX % 4 == 0 && MMAX <= kCliqueColMax, "rows are taken in fours");
   const int32_t* t = table + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_COL_WORDS;
   const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (e >= n) return;
   const int m = t[0];
-  const float w = __int_as_float(t[1]);
-  const float pad = EXACT ? -0.f : (__float_as_uint(w) >> 31 ? 0.f : -0.f);
+  const float w = WSRC ? 1.f : __int_as_float(t[1]);
+  const float pad = EXACT || WSRC ? -0.f : (__float_as_uint(w) >> 31 ? 0.f : -0.f);
+  // WSRC: w_j is read from the block's record by scalar loads next to its use, in batches of
+  // kCliqueColWBatch behind a fresh opaque zero each (a batch is one wide load that stays where
+  // it is written; no lane holds a weight, so lanes past n leave as above)
+  clique_wptr wt = nullptr;
+  if constexpr (WSRC) wt = (clique_wptr)(wtab + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_COL_WWORDS);
   // as k_round_clique: every load issued unconditionally (a padding slot re-reads member 0, an
   // L2 hit), all MMAX in flight before the first use, in batches of 8
   v2f pp[MMAX / 2];  // p_j = pp[j / 2][j % 2]
@@ -2592,10 +2620,16 @@ __global__ __launch_bounds__(kBlock) void k_round_clique_col(const T* __restrict
     pp[j >> 1][j & 1] = Io<T>::ld1(pin + static_cast<int64_t>(t[4 + (j < m ? j : 0) + opaque_zero()]) * ld_in, e);
     if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
   }
+  int zw = 0;
 #pragma unroll
   for (int j = 0; j < MMAX; ++j) {
-    if constexpr (kIsBf16<T> && EXACT) pp[j >> 1][j & 1] = round_bf16(__fmul_rn(w, p(j)));
-    else if constexpr (EXACT) pp[j >> 1][j & 1] = __fmul_rn(w, p(j));
+    float wj = w;
+    if constexpr (WSRC && EXACT) {
+      if (j % kCliqueColWBatch == 0) zw = opaque_zero();
+      wj = wt[j + zw];
+    }
+    if constexpr (kIsBf16<T> && EXACT) pp[j >> 1][j & 1] = round_bf16(__fmul_rn(wj, p(j)));
+    else if constexpr (EXACT) pp[j >> 1][j & 1] = __fmul_rn(wj, p(j));
     if (j >= m) pp[j >> 1][j & 1] = pad;
   }
   // rows four at a time, the four independent chains as one 4-wide vector per step (the
@@ -2606,10 +2640,18 @@ __global__ __launch_bounds__(kBlock) void k_round_clique_col(const T* __restrict
     int orow[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) orow[k] = i + k < m ? t[4 + kCliqueColMax + i + k + opaque_zero()] : -1;  // wave-uniform
+    // FMA under WSRC: the four rows' own weights w_i .. w_{i+3}; the steps past them read theirs
+    // batch by batch inside the chains
+    float wg[4] = {w, w, w, w};
+    if constexpr (WSRC && !EXACT) {
+      zw = opaque_zero();
+#pragma unroll
+      for (int k = 0; k < 4; ++k) wg[k] = wt[i + k + zw];
+    }
     float sp[4];  // S_i .. S_{i+3}
     sp[0] = s;
 #pragma unroll
-    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], w, p(i + k - 1));
+    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], wg[k - 1], p(i + k - 1));
     if (orow[0] >= 0 || orow[1] >= 0 || orow[2] >= 0 || orow[3] >= 0) {
       // heads: row i+k takes p(i+k+1 .. i+3) before the four chains run in step
       float a[4];
@@ -2617,30 +2659,41 @@ __global__ __launch_bounds__(kBlock) void k_round_clique_col(const T* __restrict
       for (int k = 0; k < 4; ++k) {
         a[k] = sp[k];
 #pragma unroll
-        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], w, p(j));
+        for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], wg[j - i], p(j));
       }
       v4f q = {a[0], a[1], a[2], a[3]};
 #pragma unroll
-      for (int j = i + 4; j < MMAX; ++j) q = clique_term4<T, EXACT>(q, w, v4f{p(j), p(j), p(j), p(j)});
-      q = clique_term4<T, EXACT>(q, w, v4f{p(i), p(i + 1), p(i + 2), p(i + 3)});
+      for (int j = i + 4; j < MMAX; ++j) {
+        float wj = w;
+        if constexpr (WSRC && !EXACT) {
+          if ((j - i - 4) % kCliqueColWBatch == 0) zw = opaque_zero();
+          wj = wt[j + zw];
+        }
+        q = clique_term4<T, EXACT>(q, wj, v4f{p(j), p(j), p(j), p(j)});
+      }
+      if constexpr (WSRC) q = clique_term4<T, EXACT>(q, wg[0], wg[1], wg[2], wg[3], v4f{p(i), p(i + 1), p(i + 2), p(i + 3)});
+      else q = clique_term4<T, EXACT>(q, w, v4f{p(i), p(i + 1), p(i + 2), p(i + 3)});
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (orow[k] >= 0) Io<T>::st1(pout + static_cast<int64_t>(orow[k]) * ld_out, e, q[k]);
     }
-    s = clique_term<T, EXACT>(sp[3], w, p(i + 3));
+    s = clique_term<T, EXACT>(sp[3], wg[3], p(i + 3));
   }
 }
 
-template <bool EXACT, typename T>
+// wtab: the per-source weight table (WSRC), else unused
+template <bool EXACT, typename T, bool WSRC = false>
 int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
-                                const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s) {
+                                const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s,
+                                const float* wtab = nullptr) {
   const int64_t blocks = (n + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "clique round (one column per lane): grid too large");
   const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_cliques));
   // MMAX close to the block size keeps the -0.0 padding steps few: 68 for the reference's 66
   // clients, 100 for its 100
   auto go = [&](auto M) {
-    k_round_clique_col<decltype(M)::value, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n, table);
+    k_round_clique_col<decltype(M)::value, EXACT, T, WSRC><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n, table,
+                                                                                   wtab);
   };
   if (mmax <= 68) go(std::integral_constant<int, 68>{});
   else if (mmax <= 84) go(std::integral_constant<int, 84>{});
@@ -4871,12 +4924,14 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
                                                    mmax, s);
 }
 
-// tal_agg_round_clique_col_<T>: K3c1, one column per lane - any ld, element-aligned pools.
-template <typename T>
+// tal_agg_round_clique_col_<T> and tal_agg_round_clique_col_w_<T> (WSRC: per-source weights from
+// wtab_dev): K3c1, one column per lane - any ld, element-aligned pools.
+template <typename T, bool WSRC = false>
 int32_t agg_round_clique_col(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
-                             const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream) {
+                             const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
+                             const float* wtab_dev = nullptr) {
   const std::string name(fn);
-  if (!pool_in || !pool_out || !table_dev) return fail(TAL_ERR_INVALID, name + ": null pointer");
+  if (!pool_in || !pool_out || !table_dev || (WSRC && !wtab_dev)) return fail(TAL_ERR_INVALID, name + ": null pointer");
   if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
   if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
   if (n_cliques < 0 || n_cliques > 65535 || mmax < 1 || mmax > kCliqueColMax)
@@ -4884,8 +4939,10 @@ int32_t agg_round_clique_col(const char* fn, const T* pool_in, int64_t ld_in, T*
   if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   return mode == TAL_MODE_EXACT
-             ? launch_round_clique_col<true, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s)
-             : launch_round_clique_col<false, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s);
+             ? launch_round_clique_col<true, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s,
+                                                      wtab_dev)
+             : launch_round_clique_col<false, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax,
+                                                       s, wtab_dev);
 }
 
 }  // namespace
@@ -5003,6 +5060,20 @@ int32_t tal_agg_round_clique_col_bf16(const uint16_t* pool_in, int64_t ld_in, ui
                                       int32_t mode, void* stream) {
   return agg_round_clique_col<uint16_t>("tal_agg_round_clique_col_bf16", pool_in, ld_in, pool_out, ld_out, n,
                                         table_dev, n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_col_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                       int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                       int32_t mode, void* stream, const float* wtab_dev) {
+  return agg_round_clique_col<float, true>("tal_agg_round_clique_col_w_f32", pool_in, ld_in, pool_out, ld_out, n,
+                                           table_dev, n_cliques, mmax, mode, stream, wtab_dev);
+}
+
+int32_t tal_agg_round_clique_col_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                        int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                        int32_t mode, void* stream, const float* wtab_dev) {
+  return agg_round_clique_col<uint16_t, true>("tal_agg_round_clique_col_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                              table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,

@@ -363,10 +363,25 @@ CLIQUE_COL_WORDS = 4 + 2 * CLIQUE_COL_MAX  # TAL_CLIQUE_COL_WORDS (260)
 # 100-client round (default_plan's docstring; profiles/r14) - all four, by 2.5x to 5.1x
 CLIQUE_COL_DEFAULT = {(False, MODE_EXACT): True, (False, MODE_FMA): True,
                       (True, MODE_EXACT): True, (True, MODE_FMA): True}
+CLIQUE_COL_WWORDS = CLIQUE_COL_MAX  # TAL_CLIQUE_COL_WWORDS (128): one weight per member of a K3c1 block
+# (bf16, mode): whether default_plan takes the per-source plan with blocks of 65..128 members
+# (K3c1 with per-source weights, spec {"wclique": 1, "members": 128}) where the round has such a
+# block: True only where that plan beat the plan default_plan returned before by more than
+# tune_plan's margin on every round of tools/clique_col_weighted_rate.py (profiles/r17; medians
+# of 20 interleaved runs, ms, new plan / earlier default on complete 66 and complete 100 at
+# CIFAR-CNN width, complete 100 at ResNet-50 width under data-size weights, barbell(66, 3) at
+# CIFAR-CNN width under degree-centrality softmax weights):
+#   fp32 EXACT  0.576 / 2.354   0.985 / 3.731   4.226 / 15.172   1.889 / 4.655
+#   fp32 FMA    0.579 / 1.914   1.068 / 2.894   4.437 / 12.153   1.864 / 3.797
+#   bf16 EXACT  0.818 / 4.248   1.938 / 7.777   7.589 / 31.380   2.365 / 8.447
+#   bf16 FMA    0.521 / 1.754   0.950 / 2.609   4.023 / 11.033   1.568 / 3.484
+# - all four, by 2.0x to 5.2x, the forms agreeing bit for bit
+WCLIQUE_COL_DEFAULT = {(False, MODE_EXACT): True, (False, MODE_FMA): True,
+                       (True, MODE_EXACT): True, (True, MODE_FMA): True}
 
 
 def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_source: bool = False,
-                 max_members: int = CLIQUE_MAX):
+                 max_members: int = CLIQUE_MAX, wide_per_source: bool = False):
     """Uniform-weight clique blocks of a round (the K3c kernel's rows, tal_agg.h): rows whose
     operands are strictly ascending sources and then their own model (not among them), all with
     one finite fp32 weight, grouped by (operand set, weight); a group of >= min_rows rows with
@@ -384,10 +399,14 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_
 
     max_members: the largest block, 64 (K3c) or up to 128: uniform-weight blocks of 65..128
     sources run the one-column-per-lane form (K3c1, tal_agg_round_clique_col_*), which has no
-    attached rows - rows beside such a block stay in rest - and no per-source weights."""
+    attached rows - rows beside such a block stay in rest.
+
+    wide_per_source: with per_source, lifts the per-source limit from 64 to 128 members too
+    (K3c1 with per-source weights, tal_agg_round_clique_col_w_*); without it per_source with
+    max_members > 64 is a ValueError, as it was before that form existed."""
     if max_members > CLIQUE_COL_MAX:
         raise ValueError(f"clique blocks have at most {CLIQUE_COL_MAX} members")
-    if per_source and max_members > CLIQUE_MAX:
+    if per_source and max_members > CLIQUE_MAX and not wide_per_source:
         raise ValueError(f"per-source clique blocks have at most {CLIQUE_MAX} members")
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
 
@@ -471,7 +490,10 @@ class CliquePlan:
     CLIQUE_WWORDS float32 per block, tal_agg.h) selects the tal_agg_round_clique_w_* entries.
     Blocks of 65..128 members (build_clique_plan(max_members=128)) are `col_table`: n_col records
     of CLIQUE_COL_WORDS for K3c1 (tal_agg_round_clique_col_*, one column per lane: no alignment
-    rule), launched after the K3c blocks of `table`; clique_sources and clique_rows count both."""
+    rule), launched after the K3c blocks of `table`; clique_sources and clique_rows count both.
+    A plan is per-source as a whole: built with wide_per_source, its blocks of 65..128 members
+    carry `col_wtable` (CLIQUE_COL_WWORDS float32 per block beside `col_table`, whose weight word
+    is then 0) and run tal_agg_round_clique_col_w_*."""
     table: np.ndarray
     n_cliques: int
     mmax: int
@@ -491,6 +513,8 @@ class CliquePlan:
     n_col: int = 0
     col_mmax: int = 0
     col_device: Optional[torch.Tensor] = None
+    col_wtable: Optional[np.ndarray] = None
+    col_wdevice: Optional[torch.Tensor] = None
 
     @property
     def info(self) -> RoundPlanInfo:
@@ -515,6 +539,8 @@ class CliquePlan:
             self.wdevice = torch.from_numpy(self.wtable).to(device)
         if self.col_table is not None:
             self.col_device = torch.from_numpy(self.col_table).to(device)
+        if self.col_wtable is not None:
+            self.col_wdevice = torch.from_numpy(self.col_wtable).to(device)
         if self.rest is not None:
             self.rest.to(device)
         self.full.to(device)
@@ -523,25 +549,32 @@ class CliquePlan:
 
 def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
                       rest_spec: Optional[dict] = None, bf16: bool = False,
-                      per_source: bool = False, max_members: int = CLIQUE_MAX) -> Optional[CliquePlan]:
+                      per_source: bool = False, max_members: int = CLIQUE_MAX,
+                      wide_per_source: bool = False) -> Optional[CliquePlan]:
     """CliquePlan of a round, or None when it has no clique block (find_cliques).  bf16: the
     plan runs on bf16 pools, so its rest plan must be a form tal_agg_round_bf16 takes (sparse or
     narrow: dense_rb 0, stream_cs 0); a rest_spec that asks for another form is a ValueError.
     per_source: blocks with one weight per source (find_cliques(per_source=True)); the plan then
     carries `wtable`, and the table's two weight words stay 0.
     max_members (find_cliques): up to 128 admits uniform-weight blocks of 65..128 sources, which
-    go to `col_table` (K3c1); blocks of <= 64 stay in `table` with their attached rows."""
+    go to `col_table` (K3c1); blocks of <= 64 stay in `table` with their attached rows.
+    wide_per_source (find_cliques): per-source blocks of 65..128 sources too; they go to
+    `col_table` + `col_wtable` (no attached rows: rows beside them go to the rest plan)."""
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
     cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows, per_source=per_source,
-                                 max_members=max_members)
+                                 max_members=max_members, wide_per_source=wide_per_source)
     if not cliques:
         return None
     wide = [c for c in cliques if len(c[0]) > CLIQUE_MAX]
     cliques = [c for c in cliques if len(c[0]) <= CLIQUE_MAX]
     col_table = np.zeros((len(wide), CLIQUE_COL_WORDS), np.int32) if wide else None
+    col_wtable = np.ones((len(wide), CLIQUE_COL_WWORDS), np.float32) if wide and per_source else None
     for k, (srcs, w32, outs, _) in enumerate(wide):
         col_table[k, 0] = len(srcs)
-        col_table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
+        if per_source:
+            col_wtable[k, : len(srcs)] = w32
+        else:
+            col_table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
         col_table[k, 4: 4 + len(srcs)] = srcs
         col_table[k, 4 + CLIQUE_COL_MAX:] = -1
         for i, o in outs.items():
@@ -589,7 +622,8 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
                       full=build_plan(row_ptr, col, w, out_row, dense=0), rows=len(out_row), rest_rows=rest,
                       wtable=wtable.reshape(-1) if per_source else None,
                       col_table=col_table.reshape(-1) if wide else None, n_col=len(wide),
-                      col_mmax=max((len(c[0]) for c in wide), default=0))
+                      col_mmax=max((len(c[0]) for c in wide), default=0),
+                      col_wtable=col_wtable.reshape(-1) if col_wtable is not None else None)
 
 
 def _sub_csr(row_ptr, col, w, out_row, rows):
@@ -693,6 +727,15 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
         if xp is not None and xp.n_col > 0 and xp.clique_rows > (cp.clique_rows if cp is not None and cp.wtable is None else 0):
             xp.spec = dict(clique=1, members=CLIQUE_COL_MAX, rest=xp.rest.spec if xp.rest is not None else None)
             cands.append((("clique128",), xp))
+    if cp is None or cp.col_wtable is None:
+        # per-source blocks of 65..128 members (K3c1 with per-source weights): offered when the
+        # plan has such a block, that is, takes rows no other clique plan takes
+        yp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True, max_members=CLIQUE_COL_MAX,
+                               wide_per_source=True)
+        taken = max((c.clique_rows for _, c in cands if isinstance(c, CliquePlan)), default=0)
+        if yp is not None and yp.col_wtable is not None and yp.clique_rows > taken:
+            yp.spec = dict(wclique=1, members=CLIQUE_COL_MAX, rest=yp.rest.spec if yp.rest is not None else None)
+            cands.append((("wclique128",), yp))
     return cands
 
 
@@ -764,7 +807,8 @@ def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
     if spec.get("clique") or spec.get("wclique"):
         p = build_clique_plan(row_ptr, col, w, out_row, rest_spec=spec.get("rest"),
                               per_source=not spec.get("clique"),
-                              max_members=int(spec.get("members", CLIQUE_MAX)))  # "members": 128 admits K3c1 blocks
+                              max_members=int(spec.get("members", CLIQUE_MAX)),  # "members": 128 admits K3c1 blocks
+                              wide_per_source=not spec.get("clique"))
         if p is None:
             raise ValueError("plan spec asks for clique blocks but the round has none")
         p.spec = dict(spec)
@@ -813,7 +857,21 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     against 2.235 / 3.276, fp32 FMA 0.603 / 0.985 against 1.828 / 2.654, bf16 EXACT 0.835 / 1.858
     against 4.275 / 5.885, bf16 FMA 0.488 / 0.907 against 1.755 / 2.279 (the closest: 2.5x), each
     past tune_plan's 1 % margin on both rounds, the forms agreeing bit for bit; rounds whose blocks
-    all have <= 64 members keep exactly the plans above.  One exception, from
+    all have <= 64 members keep exactly the plans above.  A round without uniform blocks that has
+    a per-source block of 65..128 members (`weighted_module_avg` over 66 or 100 clients of a
+    complete graph, the weighted and centrality apps on a barbell with cliques past 64) takes the
+    per-source 128-member plan (K3c1 with per-source weights, spec {"wclique": 1, "members": 128})
+    for fp32 and bf16 in both modes (WCLIQUE_COL_DEFAULT): against the plan this function returned
+    before - the sparse c4 = 128 plan, or on complete 100 the narrow broadcast forms below -
+    (medians of 20 interleaved runs, tools/clique_col_weighted_rate.py, profiles/r17; complete 66 /
+    complete 100 at CIFAR-CNN width / complete 100 at ResNet-50 width under data-size weights /
+    barbell(66, 3) at CIFAR-CNN width under degree-centrality softmax) fp32 EXACT took 0.576 /
+    0.985 / 4.226 / 1.889 ms against 2.354 / 3.731 / 15.172 / 4.655, fp32 FMA 0.579 / 1.068 / 4.437
+    / 1.864 against 1.914 / 2.894 / 12.153 / 3.797, bf16 EXACT 0.818 / 1.938 / 7.589 / 2.365 against
+    4.248 / 7.777 / 31.380 / 8.447, bf16 FMA 0.521 / 0.950 / 4.023 / 1.568 against 1.754 / 2.609 /
+    11.033 / 3.484 (the closest: 2.0x), each past tune_plan's 1 % margin on all four rounds, the
+    forms agreeing bit for bit; rounds without such a block keep exactly the plans above.  One
+    exception, from
     round 4's measurements: a round whose narrow plan needs per-operand weights (the pairs
     form: centrality weights on a graph whose degrees differ) runs the narrow kernel's
     broadcast form with the whole source set in one LDS tile — for bf16 in FMA mode the
@@ -838,6 +896,12 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
         if cp is not None:
             cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
             return cp
+        if WCLIQUE_COL_DEFAULT[bool(bf16), int(mode)]:
+            yp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True, max_members=CLIQUE_COL_MAX,
+                                   wide_per_source=True)
+            if yp is not None and yp.col_wtable is not None:  # a round without such a block keeps the plan below
+                yp.spec = dict(wclique=1, members=CLIQUE_COL_MAX, rest=yp.rest.spec if yp.rest is not None else None)
+                return yp
         if WCLIQUE_DEFAULT[bool(bf16), int(mode)]:
             wp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True)
             if wp is not None:
@@ -921,6 +985,8 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
 _CLIQUE_FN = {torch.float32: "tal_agg_round_clique_f32", torch.bfloat16: "tal_agg_round_clique_bf16"}
 _CLIQUE_W_FN = {torch.float32: "tal_agg_round_clique_w_f32", torch.bfloat16: "tal_agg_round_clique_w_bf16"}
 _CLIQUE_COL_FN = {torch.float32: "tal_agg_round_clique_col_f32", torch.bfloat16: "tal_agg_round_clique_col_bf16"}
+_CLIQUE_COL_W_FN = {torch.float32: "tal_agg_round_clique_col_w_f32",
+                    torch.bfloat16: "tal_agg_round_clique_col_w_bf16"}
 
 
 def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
@@ -933,7 +999,8 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("a clique round runs out of place (snapshot semantics)")
     if (plan.device is None or plan.device.device != pool_in.device or (plan.wtable is not None and plan.wdevice is None)
-            or (plan.col_table is not None and plan.col_device is None)):
+            or (plan.col_table is not None and plan.col_device is None)
+            or (plan.col_wtable is not None and plan.col_wdevice is None)):
         plan.to(pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
     pair = 2 * pool_in.element_size()
@@ -963,9 +1030,13 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
         check(getattr(L, _CLIQUE_W_FN[dtype])(*args, ctypes.c_void_p(plan.wdevice.data_ptr())))
     else:
         check(getattr(L, _CLIQUE_FN[dtype])(*args))
-    if plan.n_col > 0:  # blocks of 65..128 members: K3c1
-        check(getattr(L, _CLIQUE_COL_FN[dtype])(*head, ctypes.c_void_p(plan.col_device.data_ptr()), plan.n_col,
-                                                plan.col_mmax, int(mode), _stream(pool_in.device, stream)))
+    if plan.n_col > 0:  # blocks of 65..128 members: K3c1, with per-source weights where the plan carries them
+        cargs = (*head, ctypes.c_void_p(plan.col_device.data_ptr()), plan.n_col, plan.col_mmax, int(mode),
+                 _stream(pool_in.device, stream))
+        if plan.col_wtable is not None:
+            check(getattr(L, _CLIQUE_COL_W_FN[dtype])(*cargs, ctypes.c_void_p(plan.col_wdevice.data_ptr())))
+        else:
+            check(getattr(L, _CLIQUE_COL_FN[dtype])(*cargs))
     if plan.rest is not None:
         _round(pool_in, pool_out, plan.rest, n, dtype, mode, stream)
     return pool_out
