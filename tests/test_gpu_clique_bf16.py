@@ -13,15 +13,15 @@ import torch
 
 import oracle
 from oracle import reference_alg as ra
-from topology_aware_learning_amd import _lib, ops
+from topology_aware_learning_amd import ops
 from topology_aware_learning_amd.arena import ModelPool, StateLayout
 from topology_aware_learning_amd.round import RoundExecutor
 
+from _clique import MODES, bits, count, inputs, padded, round_of, sentinel_pool, to_dev
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-MODES = [ops.MODE_EXACT, ops.MODE_FMA]
 SENTINEL = 0x1234
 
 _CLIQUE_GRAPHS = {
@@ -44,47 +44,24 @@ def _bf16_bits(rng, n, special=False):
     return oracle.f32_to_bf16(x)
 
 
-def _as_torch(bits, dev):
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(torch.bfloat16).to(dev)
-
-
-def _bits(t):
-    return t.cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+def _as_torch(bits_, dev):
+    return to_dev(bits_, True, dev)
 
 
 def _sentinel_pool(rows, ld, dev):
-    return torch.full((rows, ld), SENTINEL, dtype=torch.int16, device=dev).view(torch.bfloat16)
+    return sentinel_pool(rows, ld, True, dev, SENTINEL)
 
 
 def _round_of(graph, n):
-    g = _CLIQUE_GRAPHS[graph]()
-    orders = [sorted(g.neighbors(i)) + [i] for i in sorted(g.nodes)]
-    sign = -1.0 if n % 2 else 1.0
-    ws = [[sign / len(o)] * len(o) for o in orders]
-    return orders, ws
+    return round_of(_CLIQUE_GRAPHS[graph](), "uniform", n=n)  # signed: negative for odd n
 
 
 def _inputs(rows, n, seed):
-    """Row 0: the bf16 specials (n > 12); member 1 holds a payload NaN in one column; a column of
-    -0.0; +inf / -inf in every third row."""
-    rng = np.random.default_rng(seed)
-    pool = np.stack([_bf16_bits(rng, n, special=(r == 0)) for r in range(rows)])
-    nan_col = 3 if n > 3 else 0
-    pool[1, nan_col] = 0x7FC1
-    if n > 5:
-        pool[:, 5] = 0x8000
-    if n > 6:
-        pool[::3, 6] = 0x7F80
-        pool[3::6, 6] = 0xFF80
-    return pool, nan_col
+    return inputs(rows, n, seed, True, by_row=True)
 
 
 def _padded(pool, dev):
-    rows, n = pool.shape
-    ld = n + (3 if n % 2 else 2)  # even, padded stride
-    pin = torch.zeros(rows, ld, dtype=torch.bfloat16, device=dev)
-    pin[:, :n] = _as_torch(pool, dev)
-    return pin
+    return padded(pool, True, dev)  # even, padded stride
 
 
 @pytest.mark.parametrize("graph,n", _CASES)
@@ -104,7 +81,7 @@ def test_round_clique_bf16_vs_oracle(cuda, graph, n):
         ref = oracle.round_bf16(pool, row_ptr, col, w, out_rows - 2, exact=(mode == ops.MODE_EXACT))
         pout = _sentinel_pool(rows + 2, pin.shape[1], cuda)
         ops.round_bf16(pin, pout, plan, n=n, mode=mode)
-        got = _bits(pout)
+        got = bits(pout)
         assert np.array_equal(got[2:, :n], ref), (graph, n, mode)
         for r in range(rows):
             if 1 in orders[r]:
@@ -141,25 +118,7 @@ def test_round_clique_bf16_attached_rows(cuda, n):
                                 exact=(mode == ops.MODE_EXACT))
         pout = _sentinel_pool(rows, pin.shape[1], cuda)
         ops.round_bf16(pin, pout, plan, n=n, mode=mode)
-        assert np.array_equal(_bits(pout)[:, :n], ref), mode
-
-
-class _Counter:
-    """A library entry point wrapped in a counting Python callable."""
-
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
-
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
-
-
-def _count(monkeypatch, name):
-    L = _lib.load()
-    c = _Counter(getattr(L, name))
-    monkeypatch.setattr(L, name, c)
-    return c
+        assert np.array_equal(bits(pout)[:, :n], ref), mode
 
 
 def _barbell20(n, cuda):
@@ -181,11 +140,11 @@ def test_round_bf16_dispatches_clique_plan(cuda, monkeypatch, mode):
     plan, pool, csr = _barbell20(n, cuda)
     pin = _padded(pool, cuda)
     pout = torch.zeros_like(pin)
-    clique = _count(monkeypatch, "tal_agg_round_clique_bf16")
-    regular = _count(monkeypatch, "tal_agg_round_bf16")
+    clique = count(monkeypatch, "tal_agg_round_clique_bf16")
+    regular = count(monkeypatch, "tal_agg_round_bf16")
     ops.round_bf16(pin, pout, plan, n=n, mode=mode)
     assert clique.calls == 1 and regular.calls == 1
-    assert np.array_equal(_bits(pout)[:, :n], oracle.round_bf16(pool, *csr, exact=(mode == ops.MODE_EXACT)))
+    assert np.array_equal(bits(pout)[:, :n], oracle.round_bf16(pool, *csr, exact=(mode == ops.MODE_EXACT)))
     with pytest.raises(ValueError):
         ops.round_bf16(pin, pin, plan, n=n, mode=mode)
     assert clique.calls == 1
@@ -201,9 +160,9 @@ def test_round_bf16_clique_alignment_fallback(cuda, monkeypatch, mode):
     pin = _padded(pool, cuda)
     want = torch.zeros_like(pin)
     ops.round_bf16(pin, want, plan, n=n, mode=mode)
-    want = _bits(want)[:, :n]
+    want = bits(want)[:, :n]
     assert np.array_equal(want, oracle.round_bf16(pool, *csr, exact=(mode == ops.MODE_EXACT)))
-    clique = _count(monkeypatch, "tal_agg_round_clique_bf16")
+    clique = count(monkeypatch, "tal_agg_round_clique_bf16")
     ld = pin.shape[1]
     # a view that starts one element (2 bytes) into an aligned buffer, even stride
     src = torch.zeros(rows * ld + 1, dtype=torch.bfloat16, device=cuda)[1:].view(rows, ld)
@@ -211,13 +170,13 @@ def test_round_bf16_clique_alignment_fallback(cuda, monkeypatch, mode):
     assert src.data_ptr() % 4 == 2 and dst.data_ptr() % 4 == 2
     src.copy_(pin)
     ops.round_bf16(src, dst, plan, n=n, mode=mode)
-    assert np.array_equal(_bits(dst)[:, :n], want)
+    assert np.array_equal(bits(dst)[:, :n], want)
     # an odd row stride
     src = torch.zeros(rows, ld + 1, dtype=torch.bfloat16, device=cuda)
     dst = torch.zeros(rows, ld + 1, dtype=torch.bfloat16, device=cuda)
     src[:, :ld] = pin
     ops.round_bf16(src, dst, plan, n=n, mode=mode)
-    assert np.array_equal(_bits(dst)[:, :n], want)
+    assert np.array_equal(bits(dst)[:, :n], want)
     assert clique.calls == 0
 
 
@@ -243,15 +202,15 @@ def test_round_executor_bf16_pool_barbell(cuda, monkeypatch, mode, double_buffer
     rng = np.random.default_rng(4)
     pool.b16[:, : layout.n_b16].copy_(_as_torch(np.stack([_bf16_bits(rng, layout.n_b16) for _ in range(rows)]), cuda))
     pool.i64[:, : layout.n_i64].random_(0, 1000)
-    before = _bits(pool.b16[:, : layout.n_b16])
+    before = bits(pool.b16[:, : layout.n_b16])
     before_i = pool.i64[:, : layout.n_i64].cpu().numpy().copy()
-    clique = _count(monkeypatch, "tal_agg_round_clique_bf16")
+    clique = count(monkeypatch, "tal_agg_round_clique_bf16")
     ex = RoundExecutor(pool, mode=mode, double_buffer=double_buffer)
     ex.run(orders, ws)
     exact = mode == ops.MODE_EXACT
     for i in range(rows):
         ref = oracle.agg_bf16([before[j] for j in orders[i]], ws[i], exact=exact)
-        assert np.array_equal(_bits(pool.row_b16(i)), ref), i
+        assert np.array_equal(bits(pool.row_b16(i)), ref), i
     assert np.array_equal(pool.i64[:, : layout.n_i64].cpu().numpy(), oracle.round_i64(before_i, row_ptr, col, w, out_rows))
     default = ops.default_plan(row_ptr, col, w, out_rows, bf16=True, mode=mode)
     if isinstance(default, ops.CliquePlan):

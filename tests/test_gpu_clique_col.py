@@ -14,11 +14,12 @@ import oracle
 from oracle import reference_alg as ra
 from topology_aware_learning_amd import _lib, ops
 
+from _clique import (MODES, bits, count, inputs, is_nan, k1_fma, np_dtype, oracle_round, padded, round_of, run, same,
+                     sentinel_pool, tdtype)
+
 pytestmark = pytest.mark.gpu
 
-MODES = [ops.MODE_EXACT, ops.MODE_FMA]
 SENTINEL = {False: 0x40E01234, True: 0x1234}  # fp32 / bf16 bits of an untouched output element
-SPECIALS = [1e-40, -0.0, 3.3e38, -1e-45, 65504.0, 1.17e-38, -3.3e38, 2.0 ** -133, 0.0, 1.0, -1.0, 3.0e38]
 
 _GRAPHS = {
     "complete65": lambda: nx.complete_graph(65),    # the smallest block past 64: MMAX 68, a row group of one
@@ -32,97 +33,22 @@ _GRAPHS = {
 _CASES = [(g, n) for g in _GRAPHS for n in (1, 7, 259)] + [("complete100", 4099), ("complete128", 4099)]
 
 
-def _np_dtype(bf16):
-    return np.uint16 if bf16 else np.uint32
-
-
-def _tdtype(bf16):
-    return torch.bfloat16 if bf16 else torch.float32
-
-
-def _to_dev(bits, bf16, dev):
-    """Host bit array -> device tensor of the storage type."""
-    a = np.ascontiguousarray(bits)
-    return torch.from_numpy(a.view(np.int16 if bf16 else np.int32)).view(_tdtype(bf16)).to(dev)
-
-
-def _bits(t):
-    bf16 = t.dtype == torch.bfloat16
-    return t.cpu().contiguous().view(torch.int16 if bf16 else torch.int32).numpy().view(_np_dtype(bf16))
+def _round_of(graph, n, who=None):
+    """Uniform weights, negative for odd n."""
+    return round_of(_GRAPHS[graph]() if isinstance(graph, str) else graph, "uniform", who=who, n=n)
 
 
 def _sentinel_pool(rows, ld, bf16, dev):
-    return _to_dev(np.full((rows, ld), SENTINEL[bf16], _np_dtype(bf16)), bf16, dev)
-
-
-def _round_of(graph, n, who=None):
-    g = _GRAPHS[graph]() if isinstance(graph, str) else graph
-    nodes = sorted(g.nodes) if who is None else who
-    orders = [sorted(g.neighbors(i)) + [i] for i in nodes]
-    sign = -1.0 if n % 2 else 1.0  # signed weights: negative for odd n
-    ws = [[sign / len(o)] * len(o) for o in orders]
-    return orders, ws
-
-
-def _inputs(rows, n, seed, bf16):
-    """Pool bits [rows, n].  Row 0: the specials (n > 12); member 1 holds a payload NaN in one
-    column; a column of -0.0; +inf / -inf in every third row of another."""
-    rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((rows, n)) * 3.0).astype(np.float32)
-    if n > 12:
-        x[0, :12] = SPECIALS
-    pool = oracle.f32_to_bf16(x) if bf16 else x.view(np.uint32).copy()
-    nan_col = 3 if n > 3 else 0
-    pool[1, nan_col] = 0x7FC1 if bf16 else 0x7FC00001
-    if n > 5:
-        pool[:, 5] = 0x8000 if bf16 else 0x80000000
-    if n > 6:
-        pool[::3, 6] = 0x7F80 if bf16 else 0x7F800000
-        pool[3::6, 6] = 0xFF80 if bf16 else 0xFF800000
-    return pool, nan_col
+    return sentinel_pool(rows, ld, bf16, dev, SENTINEL[bf16])
 
 
 def _padded(pool, bf16, dev, odd=True):
-    """Device copy with a padded row stride: odd on purpose (no column-pair rule here), even for
-    plans that also hold K3c blocks."""
-    rows, n = pool.shape
-    ld = n + 2 + ((n + odd) % 2)
-    assert ld % 2 == int(odd)
-    pin = torch.zeros(rows, ld, dtype=_tdtype(bf16), device=dev)
-    pin[:, :n] = _to_dev(pool, bf16, dev)
-    return pin
-
-
-def _oracle(pool, csr, out_rows, bf16, exact=True, pool_out=None):
-    row_ptr, col, w = csr
-    if bf16:
-        return oracle.round_bf16(pool, row_ptr, col, w, out_rows, pool_out=pool_out, exact=exact)
-    out = oracle.round_f32(pool.view(np.float32), row_ptr, col, w, out_rows,
-                           pool_out=None if pool_out is None else pool_out.view(np.float32))
-    return out.view(np.uint32)
+    return padded(pool, bf16, dev, odd=odd)
 
 
 def _same(got, ref, bf16):
     """Bit for bit; on fp32 a NaN matches a NaN (payloads are not the oracle's to pin)."""
-    if bf16:
-        return np.array_equal(got, ref)
-    ng, nr = np.isnan(got.view(np.float32)), np.isnan(ref.view(np.float32))
-    return np.array_equal(ng, nr) and np.array_equal(got[~ng], ref[~nr])
-
-
-def _is_nan(bits, bf16):
-    return bits == 0xFFFF if bf16 else np.isnan(np.array([bits], np.uint32).view(np.float32))[0]
-
-
-def _run(pin, pout, plan, n, mode):
-    (ops.round_bf16 if pin.dtype == torch.bfloat16 else ops.round_f32)(pin, pout, plan, n=n, mode=mode)
-
-
-def _k1_fma(pin, orders, ws, r, n):
-    bf16 = pin.dtype == torch.bfloat16
-    chk = torch.empty(n, dtype=pin.dtype, device=pin.device)
-    (ops.agg_bf16 if bf16 else ops.agg_f32)([pin[j, :n] for j in orders[r]], ws[r], chk, mode=ops.MODE_FMA)
-    return _bits(chk)
+    return same(got, ref, nan_payloads_free=not bf16)
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -139,21 +65,21 @@ def test_round_clique_col_vs_oracle(cuda, graph, n, bf16):
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16, max_members=128)
     assert plan is not None and plan.n_col >= 1
     assert (plan.n_cliques > 0) == (graph == "mixed") and (plan.rest is not None) == (graph in ("mixed", "barbell66"))
-    pool, nan_col = _inputs(rows, n, rows + n, bf16)
+    pool, nan_col = inputs(rows, n, rows + n, bf16)
     pin = _padded(pool, bf16, cuda, odd=plan.n_cliques == 0)
     for mode in MODES:
         pout = _sentinel_pool(rows + 2, pin.shape[1], bf16, cuda)
-        _run(pin, pout, plan, n, mode)
-        got = _bits(pout)
+        run(pin, pout, plan, n, mode)
+        got = bits(pout)
         if mode == ops.MODE_EXACT or bf16:
-            ref = _oracle(pool, csr, out_rows - 2, bf16, exact=(mode == ops.MODE_EXACT))
+            ref = oracle_round(pool, csr, out_rows - 2, bf16, exact=(mode == ops.MODE_EXACT))
             assert _same(got[2:, :n], ref, bf16), (graph, n, mode)
         if mode == ops.MODE_FMA:
             for r in (0, rows // 2, rows - 1):
-                assert _same(got[out_rows[r], :n], _k1_fma(pin, orders, ws, r, n), bf16), (graph, n, r)
+                assert _same(got[out_rows[r], :n], k1_fma(pin, orders, ws, r, n), bf16), (graph, n, r)
         for r in range(rows):
             if 1 in orders[r]:
-                assert _is_nan(got[out_rows[r], nan_col], bf16), (r, mode)
+                assert is_nan(got[out_rows[r], nan_col], bf16), (r, mode)
         assert np.all(got[:2] == SENTINEL[bf16]) and np.all(got[:, n:] == SENTINEL[bf16])  # nothing else written
 
 
@@ -168,19 +94,19 @@ def test_partial_participation(cuda, bf16):
     out_rows = np.array(who, dtype=np.int32)
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16, max_members=128)
     assert (plan.n_cliques, plan.n_col, plan.col_mmax) == (0, 1, 100) and plan.rest is None
-    pool, _ = _inputs(100, n, 11, bf16)
+    pool, _ = inputs(100, n, 11, bf16)
     pin = _padded(pool, bf16, cuda)
     for mode in MODES:
         pout = _sentinel_pool(100, pin.shape[1], bf16, cuda)
-        _run(pin, pout, plan, n, mode)
-        got = _bits(pout)
+        run(pin, pout, plan, n, mode)
+        got = bits(pout)
         if mode == ops.MODE_EXACT or bf16:
-            ref = _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT),
-                          pool_out=np.full((100, n), SENTINEL[bf16], _np_dtype(bf16)))
+            ref = oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT),
+                          pool_out=np.full((100, n), SENTINEL[bf16], np_dtype(bf16)))
             assert _same(got[:, :n], ref, bf16), mode
         else:
             for k in (0, 18, 36):
-                assert _same(got[who[k], :n], _k1_fma(pin, orders, ws, k, n), bf16), k
+                assert _same(got[who[k], :n], k1_fma(pin, orders, ws, k, n), bf16), k
         idle = np.setdiff1d(np.arange(100), who)
         assert len(idle) == 63 and np.all(got[idle] == SENTINEL[bf16]) and np.all(got[:, n:] == SENTINEL[bf16])
 
@@ -207,45 +133,27 @@ def test_small_block_equals_k3c(cuda, bf16, n):
     out_rows = np.arange(40, dtype=np.int32)
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16)
     assert plan.n_cliques == 1 and plan.mmax == 40 and plan.rest is None
-    pool, _ = _inputs(40, n, 40 + n, bf16)
+    pool, _ = inputs(40, n, 40 + n, bf16)
     pin = _padded(pool, bf16, cuda, odd=False)
     table = torch.from_numpy(_col_table_of(plan).reshape(-1)).to(cuda)
     L = _lib.load()
     fn = getattr(L, "tal_agg_round_clique_col_bf16" if bf16 else "tal_agg_round_clique_col_f32")
     for mode in MODES:
         want = _sentinel_pool(40, pin.shape[1], bf16, cuda)
-        _run(pin, want, plan, n, mode)
+        run(pin, want, plan, n, mode)
         pout = _sentinel_pool(40, pin.shape[1], bf16, cuda)
         ops.check(fn(ctypes.c_void_p(pin.data_ptr()), pin.stride(0), ctypes.c_void_p(pout.data_ptr()), pout.stride(0),
                      n, ctypes.c_void_p(table.data_ptr()), 1, 40, int(mode), ops._stream(cuda, None)))
         torch.cuda.synchronize()
-        assert np.array_equal(_bits(pout), _bits(want)), mode
+        assert np.array_equal(bits(pout), bits(want)), mode
         if mode == ops.MODE_EXACT:
-            assert _same(_bits(want)[:, :n], _oracle(pool, csr, out_rows, bf16), bf16)
-
-
-class _Counter:
-    """A library entry point wrapped in a counting Python callable."""
-
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
-
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
-
-
-def _count(monkeypatch, name):
-    L = _lib.load()
-    c = _Counter(getattr(L, name))
-    monkeypatch.setattr(L, name, c)
-    return c
+            assert _same(bits(want)[:, :n], oracle_round(pool, csr, out_rows, bf16), bf16)
 
 
 def _entries(monkeypatch, bf16):
     t = "bf16" if bf16 else "f32"
-    return (_count(monkeypatch, f"tal_agg_round_clique_col_{t}"), _count(monkeypatch, f"tal_agg_round_clique_{t}"),
-            _count(monkeypatch, f"tal_agg_round_{t}"))
+    return (count(monkeypatch, f"tal_agg_round_clique_col_{t}"), count(monkeypatch, f"tal_agg_round_clique_{t}"),
+            count(monkeypatch, f"tal_agg_round_{t}"))
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -261,16 +169,16 @@ def test_dispatch_counts(cuda, monkeypatch, bf16, mode):
         csr = ra.round_csr(orders, ws)
         out_rows = np.arange(rows, dtype=np.int32)
         plan = ops.plan_from_spec(*csr, out_rows, {"clique": 1, "members": 128, "rest": None})
-        pool, _ = _inputs(rows, n, 3, bf16)
+        pool, _ = inputs(rows, n, 3, bf16)
         pin = _padded(pool, bf16, cuda, odd=False)
         pout = torch.zeros_like(pin)
         before = (col.calls, k3c.calls, regular.calls)
-        _run(pin, pout, plan, n, mode)
+        run(pin, pout, plan, n, mode)
         assert (col.calls - before[0], k3c.calls - before[1], regular.calls - before[2]) == want, graph
         if mode == ops.MODE_EXACT or bf16:
-            assert _same(_bits(pout)[:, :n], _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
+            assert _same(bits(pout)[:, :n], oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
         with pytest.raises(ValueError):
-            _run(pin, pin, plan, n, mode)
+            run(pin, pin, plan, n, mode)
         assert (col.calls - before[0], k3c.calls - before[1], regular.calls - before[2]) == want
 
 
@@ -285,13 +193,13 @@ def test_unaligned_pools_stay_on_the_clique_path(cuda, monkeypatch, bf16, mode):
     csr = ra.round_csr(orders, ws)
     out_rows = np.arange(100, dtype=np.int32)
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16, max_members=128)
-    pool, _ = _inputs(100, n, 9, bf16)
+    pool, _ = inputs(100, n, 9, bf16)
     aligned = _padded(pool, bf16, cuda, odd=False)
     want = torch.zeros_like(aligned)
-    _run(aligned, want, plan, n, mode)
-    want = _bits(want)[:, :n]
+    run(aligned, want, plan, n, mode)
+    want = bits(want)[:, :n]
     if mode == ops.MODE_EXACT or bf16:
-        assert _same(want, _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
+        assert _same(want, oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
     col, k3c, regular = _entries(monkeypatch, bf16)
     ld = aligned.shape[1] + 1  # odd
     assert ld % 2 == 1
@@ -300,6 +208,27 @@ def test_unaligned_pools_stay_on_the_clique_path(cuda, monkeypatch, bf16, mode):
     dst = torch.zeros(100 * ld + 1, dtype=aligned.dtype, device=cuda)[1:].view(100, ld)
     assert src.data_ptr() % (2 * esize) == esize and dst.data_ptr() % (2 * esize) == esize
     src[:, : aligned.shape[1]] = aligned
-    _run(src, dst, plan, n, mode)
-    assert np.array_equal(_bits(dst)[:, :n], want)
+    run(src, dst, plan, n, mode)
+    assert np.array_equal(bits(dst)[:, :n], want)
     assert (col.calls, k3c.calls, regular.calls) == (1, 0, 0)
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+def test_plan_rows_beyond_a_pool_raise_before_any_launch(cuda, monkeypatch, bf16):
+    """A plan that reads a row pool_in lacks, or writes one pool_out lacks, is a ValueError of
+    ops.round_* for the 64-member record (complete 9) and the column record (complete 65) alike,
+    and none of the five round entries is called."""
+    n = 8
+    t = "bf16" if bf16 else "f32"
+    cs = [count(monkeypatch, f"tal_agg_round_{k}{t}") for k in ("clique_col_w_", "clique_w_", "", "clique_col_", "clique_")]
+    for m, blocks in ((9, (1, 0)), (65, (0, 1))):
+        orders, ws = _round_of(nx.complete_graph(m), n)
+        plan = ops.build_clique_plan(*ra.round_csr(orders, ws), np.arange(m, dtype=np.int32), bf16=bf16, max_members=128)
+        assert (plan.n_cliques, plan.n_col) == blocks and plan.rest is None
+        whole = torch.zeros(m, n, dtype=tdtype(bf16), device=cuda)
+        short = torch.zeros(m - 1, n, dtype=tdtype(bf16), device=cuda)
+        with pytest.raises(ValueError, match="beyond pool_in"):
+            run(short, whole, plan, n, ops.MODE_EXACT)
+        with pytest.raises(ValueError, match="beyond pool_out"):
+            run(whole, short, plan, n, ops.MODE_EXACT)
+    assert [c.calls for c in cs] == [0] * 5

@@ -17,15 +17,15 @@ import torch
 import oracle
 from oracle import reference_alg as ra
 from topology_aware_learning_amd import _lib, ops
-from topology_aware_learning_amd import weights as tw
 from topology_aware_learning_amd.arena import ModelPool, StateLayout
 from topology_aware_learning_amd.round import RoundExecutor
 
+from _clique import (MODES, bits, count, inputs, is_nan, k1_fma, np_dtype, oracle_round, padded, round_of, run, same,
+                     sentinel_pool, to_dev)
+
 pytestmark = pytest.mark.gpu
 
-MODES = [ops.MODE_EXACT, ops.MODE_FMA]
 SENTINEL = {False: 0x40E01234, True: 0x1234}  # fp32 / bf16 bits of an untouched output element
-SPECIALS = [1e-40, -0.0, 3.3e38, -1e-45, 65504.0, 1.17e-38, -3.3e38, 2.0 ** -133, 0.0, 1.0, -1.0, 3.0e38]
 WIDE = dict(per_source=True, max_members=128, wide_per_source=True)
 
 _GRAPHS = {
@@ -44,105 +44,21 @@ _CASES = ([(g, k, n) for g in _GRAPHS for k in _KINDS[g] for n in (1, 7, 259)]
 
 
 def _round_of(graph, kind, who=None):
-    """(orders, weights): data-size weights, every source distinct; softmax of 10 x the degree
-    centrality; hand-made signed weights per source, some exactly 0 - the same for a source in
-    every row that reads it, so the clique rows form per-source blocks."""
-    g = _GRAPHS[graph]() if isinstance(graph, str) else graph
-    nodes = sorted(g.nodes)
-    rows = nodes if who is None else who
-    orders = [sorted(g.neighbors(i)) + [i] for i in rows]
-    if kind == "datasize":
-        lens = (np.random.default_rng(5).permutation(len(nodes)) * 37 + 101).tolist()  # all distinct
-        return orders, [tw.weighted([lens[j] for j in o]) for o in orders]
-    if kind == "degcent":
-        cent = nx.degree_centrality(g)
-        return orders, [tw.centrality(o, cent, True, 10.0) for o in orders]
-    per = [0.0 if j % 7 == 3 else ((-1.0) ** j) * (0.013 * (j % 11) + 0.002) for j in nodes]
-    return orders, [[per[j] for j in o] for o in orders]
-
-
-def _np_dtype(bf16):
-    return np.uint16 if bf16 else np.uint32
-
-
-def _tdtype(bf16):
-    return torch.bfloat16 if bf16 else torch.float32
-
-
-def _to_dev(bits, bf16, dev):
-    """Host bit array -> device tensor of the storage type."""
-    a = np.ascontiguousarray(bits)
-    return torch.from_numpy(a.view(np.int16 if bf16 else np.int32)).view(_tdtype(bf16)).to(dev)
-
-
-def _bits(t):
-    bf16 = t.dtype == torch.bfloat16
-    return t.cpu().contiguous().view(torch.int16 if bf16 else torch.int32).numpy().view(_np_dtype(bf16))
+    """Per-source weights of one kind (_clique.round_of)."""
+    return round_of(_GRAPHS[graph]() if isinstance(graph, str) else graph, kind, who=who)
 
 
 def _sentinel_pool(rows, ld, bf16, dev):
-    return _to_dev(np.full((rows, ld), SENTINEL[bf16], _np_dtype(bf16)), bf16, dev)
-
-
-def _inputs(rows, n, seed, bf16):
-    """Pool bits [rows, n].  Row 0: the specials (n > 12); member 1 holds a payload NaN in one
-    column; a column of -0.0; +inf / -inf in every third row of another."""
-    rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((rows, n)) * 3.0).astype(np.float32)
-    if n > 12:
-        x[0, :12] = SPECIALS
-    pool = oracle.f32_to_bf16(x) if bf16 else x.view(np.uint32).copy()
-    nan_col = 3 if n > 3 else 0
-    pool[1, nan_col] = 0x7FC1 if bf16 else 0x7FC00001
-    if n > 5:
-        pool[:, 5] = 0x8000 if bf16 else 0x80000000
-    if n > 6:
-        pool[::3, 6] = 0x7F80 if bf16 else 0x7F800000
-        pool[3::6, 6] = 0xFF80 if bf16 else 0xFF800000
-    return pool, nan_col
+    return sentinel_pool(rows, ld, bf16, dev, SENTINEL[bf16])
 
 
 def _padded(pool, bf16, dev, odd=True):
-    """Device copy with a padded row stride: odd on purpose (no column-pair rule here), even for
-    plans that also hold K3c blocks."""
-    rows, n = pool.shape
-    ld = n + 2 + ((n + odd) % 2)
-    assert ld % 2 == int(odd)
-    pin = torch.zeros(rows, ld, dtype=_tdtype(bf16), device=dev)
-    pin[:, :n] = _to_dev(pool, bf16, dev)
-    return pin
-
-
-def _oracle(pool, csr, out_rows, bf16, exact=True, pool_out=None):
-    row_ptr, col, w = csr
-    if bf16:
-        return oracle.round_bf16(pool, row_ptr, col, w, out_rows, pool_out=pool_out, exact=exact)
-    out = oracle.round_f32(pool.view(np.float32), row_ptr, col, w, out_rows,
-                           pool_out=None if pool_out is None else pool_out.view(np.float32), exact=exact)
-    return out.view(np.uint32)
+    return padded(pool, bf16, dev, odd=odd)
 
 
 def _same(got, ref, bf16):
     """Bit for bit; on fp32 a NaN matches a NaN (payloads are not the oracle's to pin)."""
-    if bf16:
-        return np.array_equal(got, ref)
-    ng, nr = np.isnan(got.view(np.float32)), np.isnan(ref.view(np.float32))
-    return np.array_equal(ng, nr) and np.array_equal(got[~ng], ref[~nr])
-
-
-def _is_nan(bits, bf16):
-    return bits == 0xFFFF if bf16 else np.isnan(np.array([bits], np.uint32).view(np.float32))[0]
-
-
-def _run(pin, pout, plan, n, mode):
-    (ops.round_bf16 if pin.dtype == torch.bfloat16 else ops.round_f32)(pin, pout, plan, n=n, mode=mode)
-
-
-def _k1_fma(pin, orders, ws, r, n):
-    bf16 = pin.dtype == torch.bfloat16
-    chk = torch.empty(n, dtype=pin.dtype, device=pin.device)
-    (ops.agg_bf16 if bf16 else ops.agg_f32)([pin[j, :n] for j in orders[r]], ws[r], chk, mode=ops.MODE_FMA)
-    return _bits(chk)
+    return same(got, ref, nan_payloads_free=not bf16)
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -159,20 +75,20 @@ def test_round_clique_col_weighted_vs_oracle(cuda, graph, kind, n, bf16):
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16, **WIDE)
     assert plan is not None and plan.n_col >= 1 and plan.col_wtable is not None
     assert (plan.n_cliques > 0) == (graph == "mixed") and (plan.rest is not None) == (graph in ("mixed", "barbell66"))
-    pool, nan_col = _inputs(rows, n, rows + n, bf16)
+    pool, nan_col = inputs(rows, n, rows + n, bf16)
     pin = _padded(pool, bf16, cuda, odd=plan.n_cliques == 0)
     for mode in MODES:
         pout = _sentinel_pool(rows + 2, pin.shape[1], bf16, cuda)
-        _run(pin, pout, plan, n, mode)
-        got = _bits(pout)
-        ref = _oracle(pool, csr, out_rows - 2, bf16, exact=(mode == ops.MODE_EXACT))
+        run(pin, pout, plan, n, mode)
+        got = bits(pout)
+        ref = oracle_round(pool, csr, out_rows - 2, bf16, exact=(mode == ops.MODE_EXACT))
         assert _same(got[2:, :n], ref, bf16), (graph, kind, n, mode)
         if mode == ops.MODE_FMA and not bf16:
             for r in (0, rows // 2, rows - 1):
-                assert _same(got[out_rows[r], :n], _k1_fma(pin, orders, ws, r, n), bf16), (graph, kind, n, r)
+                assert _same(got[out_rows[r], :n], k1_fma(pin, orders, ws, r, n), bf16), (graph, kind, n, r)
         for r in range(rows):
             if 1 in orders[r]:
-                assert _is_nan(got[out_rows[r], nan_col], bf16), (r, mode)
+                assert is_nan(got[out_rows[r], nan_col], bf16), (r, mode)
         assert np.all(got[:2] == SENTINEL[bf16]) and np.all(got[:, n:] == SENTINEL[bf16])  # nothing else written
 
 
@@ -187,14 +103,14 @@ def test_partial_participation(cuda, bf16):
     out_rows = np.array(who, dtype=np.int32)
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16, **WIDE)
     assert (plan.n_cliques, plan.n_col, plan.col_mmax) == (0, 1, 100) and plan.rest is None
-    pool, _ = _inputs(100, n, 11, bf16)
+    pool, _ = inputs(100, n, 11, bf16)
     pin = _padded(pool, bf16, cuda)
     for mode in MODES:
         pout = _sentinel_pool(100, pin.shape[1], bf16, cuda)
-        _run(pin, pout, plan, n, mode)
-        got = _bits(pout)
-        ref = _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT),
-                      pool_out=np.full((100, n), SENTINEL[bf16], _np_dtype(bf16)))
+        run(pin, pout, plan, n, mode)
+        got = bits(pout)
+        ref = oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT),
+                      pool_out=np.full((100, n), SENTINEL[bf16], np_dtype(bf16)))
         assert _same(got[:, :n], ref, bf16), mode
         idle = np.setdiff1d(np.arange(100), who)
         assert len(idle) == 63 and np.all(got[idle] == SENTINEL[bf16]) and np.all(got[:, n:] == SENTINEL[bf16])
@@ -230,17 +146,17 @@ def test_small_block_equals_k3c_weighted(cuda, bf16, n):
     c[0, 4 + ops.CLIQUE_COL_MAX: 4 + ops.CLIQUE_COL_MAX + ops.CLIQUE_MAX] = t[0, 4 + ops.CLIQUE_MAX: 4 + 2 * ops.CLIQUE_MAX]
     cw = np.ones((1, ops.CLIQUE_COL_WWORDS), np.float32)
     cw[0, :ops.CLIQUE_MAX] = plan.wtable.reshape(1, ops.CLIQUE_WWORDS)[0, :ops.CLIQUE_MAX]
-    pool, _ = _inputs(40, n, 40 + n, bf16)
+    pool, _ = inputs(40, n, 40 + n, bf16)
     pin = _padded(pool, bf16, cuda, odd=False)
     table = torch.from_numpy(c.reshape(-1)).to(cuda)
     wtab = torch.from_numpy(cw.reshape(-1)).to(cuda)
     for mode in MODES:
         want = _sentinel_pool(40, pin.shape[1], bf16, cuda)
-        _run(pin, want, plan, n, mode)
+        run(pin, want, plan, n, mode)
         pout = _sentinel_pool(40, pin.shape[1], bf16, cuda)
         _call_entry(bf16, pin, pout, n, table, 1, 40, mode, wtab, cuda)
-        assert np.array_equal(_bits(pout), _bits(want)), mode
-        assert _same(_bits(want)[:, :n], _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
+        assert np.array_equal(bits(pout), bits(want)), mode
+        assert _same(bits(want)[:, :n], oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -260,43 +176,25 @@ def test_equal_weights_equal_uniform_entry(cuda, bf16, n):
     assert (per.n_cliques, per.n_col) == (0, 1)
     cw = per.col_wtable.reshape(1, ops.CLIQUE_COL_WWORDS)
     assert np.all(cw[0, :100] == np.float32(-0.01)) and np.all(cw[0, 100:] == 1.0)
-    pool, _ = _inputs(100, n, 17 + n, bf16)
+    pool, _ = inputs(100, n, 17 + n, bf16)
     pin = _padded(pool, bf16, cuda)
     table = torch.from_numpy(uni.col_table).to(cuda)  # the uniform record: its weight word is ignored
     wtab = torch.from_numpy(per.col_wtable).to(cuda)
     for mode in MODES:
         want = _sentinel_pool(100, pin.shape[1], bf16, cuda)
-        _run(pin, want, uni, n, mode)
+        run(pin, want, uni, n, mode)
         pout = _sentinel_pool(100, pin.shape[1], bf16, cuda)
         _call_entry(bf16, pin, pout, n, table, 1, 100, mode, wtab, cuda)
-        assert np.array_equal(_bits(pout), _bits(want)), mode
+        assert np.array_equal(bits(pout), bits(want)), mode
         via_plan = _sentinel_pool(100, pin.shape[1], bf16, cuda)
-        _run(pin, via_plan, per, n, mode)
-        assert np.array_equal(_bits(via_plan), _bits(want)), mode
-
-
-class _Counter:
-    """A library entry point wrapped in a counting Python callable."""
-
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
-
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
-
-
-def _count(monkeypatch, name):
-    L = _lib.load()
-    c = _Counter(getattr(L, name))
-    monkeypatch.setattr(L, name, c)
-    return c
+        run(pin, via_plan, per, n, mode)
+        assert np.array_equal(bits(via_plan), bits(want)), mode
 
 
 def _entries(monkeypatch, bf16):
     """Counters: the new entry, K3c-w, the regular round, the uniform column entry, uniform K3c."""
     t = "bf16" if bf16 else "f32"
-    return [_count(monkeypatch, f"tal_agg_round_{k}{t}") for k in ("clique_col_w_", "clique_w_", "", "clique_col_", "clique_")]
+    return [count(monkeypatch, f"tal_agg_round_{k}{t}") for k in ("clique_col_w_", "clique_w_", "", "clique_col_", "clique_")]
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -315,15 +213,15 @@ def test_dispatch_counts(cuda, monkeypatch, bf16, mode):
         plan = ops.plan_from_spec(*csr, out_rows, {"wclique": 1, "members": 128, "rest": None})
         assert plan.col_wtable is not None and ops.round_kernel_name(plan) == (
             "k_round_clique" if graph == "mixed" else "k_round_clique_col")
-        pool, _ = _inputs(rows, n, 3, bf16)
+        pool, _ = inputs(rows, n, 3, bf16)
         pin = _padded(pool, bf16, cuda, odd=False)
         pout = torch.zeros_like(pin)
         before = [c.calls for c in cs]
-        _run(pin, pout, plan, n, mode)
+        run(pin, pout, plan, n, mode)
         assert tuple(c.calls - b for c, b in zip(cs, before)) == want, graph
-        assert _same(_bits(pout)[:, :n], _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
+        assert _same(bits(pout)[:, :n], oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
         with pytest.raises(ValueError):
-            _run(pin, pin, plan, n, mode)
+            run(pin, pin, plan, n, mode)
         assert tuple(c.calls - b for c, b in zip(cs, before)) == want
 
 
@@ -338,12 +236,12 @@ def test_unaligned_pools_stay_on_the_clique_path(cuda, monkeypatch, bf16, mode):
     csr = ra.round_csr(orders, ws)
     out_rows = np.arange(100, dtype=np.int32)
     plan = ops.build_clique_plan(*csr, out_rows, bf16=bf16, **WIDE)
-    pool, _ = _inputs(100, n, 9, bf16)
+    pool, _ = inputs(100, n, 9, bf16)
     aligned = _padded(pool, bf16, cuda, odd=False)
     want = torch.zeros_like(aligned)
-    _run(aligned, want, plan, n, mode)
-    want = _bits(want)[:, :n]
-    assert _same(want, _oracle(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
+    run(aligned, want, plan, n, mode)
+    want = bits(want)[:, :n]
+    assert _same(want, oracle_round(pool, csr, out_rows, bf16, exact=(mode == ops.MODE_EXACT)), bf16)
     cs = _entries(monkeypatch, bf16)
     ld = aligned.shape[1] + 1  # odd
     assert ld % 2 == 1
@@ -352,8 +250,8 @@ def test_unaligned_pools_stay_on_the_clique_path(cuda, monkeypatch, bf16, mode):
     dst = torch.zeros(100 * ld + 1, dtype=aligned.dtype, device=cuda)[1:].view(100, ld)
     assert src.data_ptr() % (2 * esize) == esize and dst.data_ptr() % (2 * esize) == esize
     src[:, : aligned.shape[1]] = aligned
-    _run(src, dst, plan, n, mode)
-    assert np.array_equal(_bits(dst)[:, :n], want)
+    run(src, dst, plan, n, mode)
+    assert np.array_equal(bits(dst)[:, :n], want)
     assert tuple(c.calls for c in cs) == (1, 0, 0, 0, 0)
 
 
@@ -372,11 +270,11 @@ def test_round_executor_complete66(cuda, monkeypatch, bf16):
     plan.rest_rows = None  # every row aggregates: nothing to carry into the spare (RoundExecutor.plan's form)
     pool = ModelPool(layout, 66, cuda)
     seg = pool.b16 if bf16 else pool.f32
-    before, _ = _inputs(66, n, 4, bf16)
-    seg[:, :n].copy_(_to_dev(before, bf16, cuda))
-    new = _count(monkeypatch, "tal_agg_round_clique_col_w_" + ("bf16" if bf16 else "f32"))
+    before, _ = inputs(66, n, 4, bf16)
+    seg[:, :n].copy_(to_dev(before, bf16, cuda))
+    new = count(monkeypatch, "tal_agg_round_clique_col_w_" + ("bf16" if bf16 else "f32"))
     ex = RoundExecutor(pool, mode=ops.MODE_EXACT, placement_trials=1)  # no placement runs: the round alone
     ex.run(orders, ws, plan=plan)
     seg = pool.b16 if bf16 else pool.f32
-    assert _same(_bits(seg[:, :n]), _oracle(before, csr, out_rows, bf16), bf16)
+    assert _same(bits(seg[:, :n]), oracle_round(before, csr, out_rows, bf16), bf16)
     assert new.calls == 1

@@ -14,14 +14,15 @@ import torch
 
 import oracle
 from oracle import reference_alg as ra
-from topology_aware_learning_amd import _lib, ops
+from topology_aware_learning_amd import ops
 from topology_aware_learning_amd import weights as tw
 from topology_aware_learning_amd.arena import ModelPool, StateLayout
 from topology_aware_learning_amd.round import RoundExecutor
 
+from _clique import MODES, bits, count, inputs, padded, round_of, run, same, sentinel_pool, to_dev
+
 pytestmark = pytest.mark.gpu
 
-MODES = [ops.MODE_EXACT, ops.MODE_FMA]
 F32, BF16 = "f32", "bf16"
 SENTINEL = {F32: 0x12345678, BF16: 0x1234}
 
@@ -40,20 +41,7 @@ _CASES = [(g, n) for g in _GRAPHS for n in (1, 7, 4098)] + [("barbell60", 20003)
 
 
 def _round_of(graph, kind):
-    """(orders, weights): (a) data-size weights, every source distinct; (b) softmax of 10 x the
-    degree centrality; (c) hand-made signed weights per source, zero included - the same for a
-    source in every row that reads it, so the clique rows form blocks."""
-    g = _GRAPHS[graph]()
-    nodes = sorted(g.nodes)
-    orders = [sorted(g.neighbors(i)) + [i] for i in nodes]
-    if kind == "datasize":
-        lens = (np.random.default_rng(5).permutation(len(nodes)) * 37 + 101).tolist()  # all distinct
-        return orders, [tw.weighted([lens[j] for j in o]) for o in orders]
-    if kind == "degcent":
-        cent = nx.degree_centrality(g)
-        return orders, [tw.centrality(o, cent, True, 10.0) for o in orders]
-    per = [0.0 if j % 7 == 3 else ((-1.0) ** j) * (0.013 * (j % 11) + 0.002) for j in nodes]  # some exactly 0
-    return orders, [[per[j] for j in o] for o in orders]
+    return round_of(_GRAPHS[graph](), kind)
 
 
 def _to_bits(x, dt):
@@ -61,52 +49,19 @@ def _to_bits(x, dt):
 
 
 def _inputs(rows, n, seed, dt):
-    """Storage bits [rows, n].  Row 0: fp32 denormals, 3e38 and other edge values (n > 12); member 1
-    holds a payload NaN in one column; a column of -0.0; +inf / -inf in every third row."""
-    rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((rows, n)) * 3.0).astype(np.float32)
-    if n > 12:
-        x[0, :12] = [1e-40, -0.0, 3.3e38, -1e-45, 65504.0, 1.17e-38, -3.3e38, 2.0 ** -133, 0.0, 1.0, -1.0, 3.0e38]
-    pool = _to_bits(x, dt).copy()
-    nan_col = 3 if n > 3 else 0
-    pool[1, nan_col] = 0x7FC00001 if dt == F32 else 0x7FC1
-    neg0, pinf, ninf = (0x80000000, 0x7F800000, 0xFF800000) if dt == F32 else (0x8000, 0x7F80, 0xFF80)
-    if n > 5:
-        pool[:, 5] = neg0
-    if n > 6:
-        pool[::3, 6] = pinf
-        pool[3::6, 6] = ninf
-    return pool, nan_col
+    return inputs(rows, n, seed, dt == BF16)
 
 
-def _as_torch(bits, dt, dev):
-    if dt == F32:
-        return torch.from_numpy(np.ascontiguousarray(bits).view(np.float32)).to(dev)
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(torch.bfloat16).to(dev)
-
-
-def _bits(t):
-    if t.dtype == torch.float32:
-        return t.cpu().contiguous().view(torch.int32).numpy().view(np.uint32)
-    return t.cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+def _as_torch(bits_, dt, dev):
+    return to_dev(bits_, dt == BF16, dev)
 
 
 def _sentinel_pool(rows, ld, dt, dev):
-    if dt == F32:
-        return torch.full((rows, ld), SENTINEL[F32], dtype=torch.int32, device=dev).view(torch.float32)
-    return torch.full((rows, ld), SENTINEL[BF16], dtype=torch.int16, device=dev).view(torch.bfloat16)
+    return sentinel_pool(rows, ld, dt == BF16, dev, SENTINEL[dt])
 
 
 def _padded(pool, dt, dev):
-    rows, n = pool.shape
-    ld = n + (3 if n % 2 else 2)  # even, padded stride
-    pin = torch.zeros(rows, ld, dtype=torch.float32 if dt == F32 else torch.bfloat16, device=dev)
-    pin[:, :n] = _as_torch(pool, dt, dev)
-    return pin
-
-
-def _run(pin, pout, plan, n, mode):
-    (ops.round_f32 if pin.dtype == torch.float32 else ops.round_bf16)(pin, pout, plan, n=n, mode=mode)
+    return padded(pool, dt == BF16, dev)  # even, padded stride
 
 
 def _k1_rows_fma(pin, orders, ws, n, dev):
@@ -114,17 +69,12 @@ def _k1_rows_fma(pin, orders, ws, n, dev):
     out = torch.empty(len(orders), n, dtype=torch.float32, device=dev)
     for r, (o, w) in enumerate(zip(orders, ws)):
         ops.agg_f32([pin[j, :n] for j in o], w, out[r], mode=ops.MODE_FMA)
-    return _bits(out)
+    return bits(out)
 
 
 def _same(got, ref, dt, mode):
-    """Bit for bit.  fp32 EXACT is held against the C oracle on the CPU, whose NaNs carry x86's
-    payloads (inf - inf is 0xFFC00000 there, 0x7FC00000 on the GPU): as everywhere in this suite's
-    fp32 checks, NaNs must sit in the same places and every other value must agree in every bit."""
-    if dt == F32 and mode == ops.MODE_EXACT:
-        ng, nr = np.isnan(got.view(np.float32)), np.isnan(ref.view(np.float32))
-        return np.array_equal(ng, nr) and np.array_equal(got[~ng], ref[~nr])
-    return np.array_equal(got, ref)
+    """Bit for bit; fp32 EXACT is held against the C oracle on the CPU, whose NaN payloads differ."""
+    return same(got, ref, nan_payloads_free=(dt == F32 and mode == ops.MODE_EXACT))
 
 
 def _reference(dt, mode, pool, pin, csr, orders, ws, n, dev):
@@ -160,8 +110,8 @@ def test_round_clique_weighted(cuda, graph, n, kind, dt):
     for mode in MODES:
         ref = _reference(dt, mode, pool, pin, csr, orders, ws, n, cuda)
         pout = _sentinel_pool(rows + 2, pin.shape[1], dt, cuda)
-        _run(pin, pout, plan, n, mode)
-        got = _bits(pout)
+        run(pin, pout, plan, n, mode)
+        got = bits(pout)
         assert _same(got[out_rows, :n], ref, dt, mode), (graph, n, kind, dt, mode)
         if dt == BF16:
             for r in range(rows):
@@ -203,8 +153,8 @@ def test_round_clique_weighted_attached_rows(cuda, n, dt):
     for mode in MODES:
         ref = _reference(dt, mode, pool, pin, csr, orders, ws, n, cuda)
         pout = _sentinel_pool(rows, pin.shape[1], dt, cuda)
-        _run(pin, pout, plan, n, mode)
-        assert _same(_bits(pout)[:, :n], ref, dt, mode), (dt, mode)
+        run(pin, pout, plan, n, mode)
+        assert _same(bits(pout)[:, :n], ref, dt, mode), (dt, mode)
 
 
 @pytest.mark.parametrize("dt", [F32, BF16])
@@ -227,27 +177,9 @@ def test_uniform_round_through_weighted_entries(cuda, graph, n, dt):
     for mode in MODES:
         a = _sentinel_pool(rows, pin.shape[1], dt, cuda)
         b = _sentinel_pool(rows, pin.shape[1], dt, cuda)
-        _run(pin, a, uni, n, mode)
-        _run(pin, b, per, n, mode)
-        assert np.array_equal(_bits(a), _bits(b)), (graph, dt, mode)
-
-
-class _Counter:
-    """A library entry point wrapped in a counting Python callable."""
-
-    def __init__(self, fn):
-        self.fn, self.calls = fn, 0
-
-    def __call__(self, *args):
-        self.calls += 1
-        return self.fn(*args)
-
-
-def _count(monkeypatch, name):
-    L = _lib.load()
-    c = _Counter(getattr(L, name))
-    monkeypatch.setattr(L, name, c)
-    return c
+        run(pin, a, uni, n, mode)
+        run(pin, b, per, n, mode)
+        assert np.array_equal(bits(a), bits(b)), (graph, dt, mode)
 
 
 @pytest.mark.parametrize("dt", [F32, BF16])
@@ -264,28 +196,28 @@ def test_weighted_clique_dispatch_and_alignment_fallback(cuda, monkeypatch, mode
     assert plan.rest is not None
     pool, _ = _inputs(rows, n, 7, dt)
     pin = _padded(pool, dt, cuda)
-    weighted = _count(monkeypatch, f"tal_agg_round_clique_w_{dt}")
-    uniform = _count(monkeypatch, f"tal_agg_round_clique_{dt}")
-    regular = _count(monkeypatch, f"tal_agg_round_{dt}")
+    weighted = count(monkeypatch, f"tal_agg_round_clique_w_{dt}")
+    uniform = count(monkeypatch, f"tal_agg_round_clique_{dt}")
+    regular = count(monkeypatch, f"tal_agg_round_{dt}")
     want = torch.zeros_like(pin)
-    _run(pin, want, plan, n, mode)
+    run(pin, want, plan, n, mode)
     assert (weighted.calls, uniform.calls, regular.calls) == (1, 0, 1)
-    want = _bits(want)[:, :n]
+    want = bits(want)[:, :n]
     assert _same(want, _reference(dt, mode, pool, pin, csr, orders, ws, n, cuda), dt, mode)
     with pytest.raises(ValueError):
-        _run(pin, pin, plan, n, mode)
+        run(pin, pin, plan, n, mode)
     ld, tdt = pin.shape[1], pin.dtype
     src = torch.zeros(rows * ld + 1, dtype=tdt, device=cuda)[1:].view(rows, ld)  # half a column pair in
     dst = torch.zeros(rows * ld + 1, dtype=tdt, device=cuda)[1:].view(rows, ld)
     assert src.data_ptr() % (2 * src.element_size()) == src.element_size()
     src.copy_(pin)
-    _run(src, dst, plan, n, mode)
-    assert np.array_equal(_bits(dst)[:, :n], want)
+    run(src, dst, plan, n, mode)
+    assert np.array_equal(bits(dst)[:, :n], want)
     src = torch.zeros(rows, ld + 1, dtype=tdt, device=cuda)  # an odd row stride
     dst = torch.zeros(rows, ld + 1, dtype=tdt, device=cuda)
     src[:, :ld] = pin
-    _run(src, dst, plan, n, mode)
-    assert np.array_equal(_bits(dst)[:, :n], want)
+    run(src, dst, plan, n, mode)
+    assert np.array_equal(bits(dst)[:, :n], want)
     assert (weighted.calls, uniform.calls) == (1, 0)
 
 
@@ -309,10 +241,10 @@ def test_round_executor_weighted_barbell(cuda, monkeypatch, dt):
     seg = pool.f32 if dt == F32 else pool.b16
     before = _to_bits((np.random.default_rng(4).standard_normal((rows, n)) * 3.0).astype(np.float32), dt)
     seg[:, :n].copy_(_as_torch(before, dt, cuda))
-    weighted = _count(monkeypatch, f"tal_agg_round_clique_w_{dt}")
+    weighted = count(monkeypatch, f"tal_agg_round_clique_w_{dt}")
     ex = RoundExecutor(pool, mode=ops.MODE_EXACT, placement_trials=1)  # no placement runs: the round alone
     ex.run(orders, ws)
     ref = _reference(dt, ops.MODE_EXACT, before, None, csr, orders, ws, n, cuda)
     seg = pool.f32 if dt == F32 else pool.b16
-    assert _same(_bits(seg[:, :n]), ref, dt, ops.MODE_EXACT)
+    assert _same(bits(seg[:, :n]), ref, dt, ops.MODE_EXACT)
     assert weighted.calls == 1

@@ -2682,10 +2682,10 @@ __global__ __launch_bounds__(kBlock) void k_round_clique_col(const T* __restrict
 }
 
 // wtab: the per-source weight table (WSRC), else unused
-template <bool EXACT, typename T, bool WSRC = false>
+template <bool EXACT, typename T, bool WSRC>
 int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
-                                const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s,
-                                const float* wtab = nullptr) {
+                                const int32_t* table, const float* wtab, int32_t n_cliques, int32_t mmax,
+                                hipStream_t s) {
   const int64_t blocks = (n + kBlock - 1) / kBlock;
   if (blocks > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "clique round (one column per lane): grid too large");
   const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_cliques));
@@ -4900,9 +4900,11 @@ int32_t agg_round(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, 
   return launch_round_scalar<T>(pool_in, ld_in, pool_out, ld_out, e_vec, n, v, *info, exact, s);
 }
 
-// tal_agg_round_clique_<T> and tal_agg_round_clique_w_<T> (WSRC: per-source weights from
-// wtab_dev): a column pair is one 8-B (fp32) or 4-B (bf16) access, which sets the alignment rule.
-template <typename T, bool WSRC = false>
+// tal_agg_round_clique_<T> / _w_<T> and, COL, tal_agg_round_clique_col_<T> / _col_w_<T> (WSRC:
+// per-source weights from wtab_dev).  K3c: a column pair is one 8-B (fp32) or 4-B (bf16) access,
+// which sets the alignment rule, and too many blocks are found at the launch.  K3c1, one column
+// per lane: any ld, element-aligned pools.
+template <typename T, bool COL, bool WSRC>
 int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
                          const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
                          const float* wtab_dev = nullptr) {
@@ -4910,39 +4912,27 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
   if (!pool_in || !pool_out || !table_dev || (WSRC && !wtab_dev)) return fail(TAL_ERR_INVALID, name + ": null pointer");
   if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
   if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
-  if (n_cliques < 0 || mmax < 1 || mmax > kCliqueMax)
-    return fail(TAL_ERR_INVALID, name + ": n_cliques >= 0, 1 <= mmax <= 64");
-  const uintptr_t mask = 2 * sizeof(T) - 1;
-  if (((reinterpret_cast<uintptr_t>(pool_in) | reinterpret_cast<uintptr_t>(pool_out)) & mask) || ld_in % 2 || ld_out % 2)
-    return fail(TAL_ERR_INVALID, name + ": pools must be " + std::to_string(2 * sizeof(T)) + "-B aligned with even ld");
+  if constexpr (COL) {
+    if (n_cliques < 0 || n_cliques > 65535 || mmax < 1 || mmax > kCliqueColMax)
+      return fail(TAL_ERR_INVALID, name + ": 0 <= n_cliques <= 65535, 1 <= mmax <= 128");
+  } else {
+    if (n_cliques < 0 || mmax < 1 || mmax > kCliqueMax)
+      return fail(TAL_ERR_INVALID, name + ": n_cliques >= 0, 1 <= mmax <= 64");
+    const uintptr_t mask = 2 * sizeof(T) - 1;
+    if (((reinterpret_cast<uintptr_t>(pool_in) | reinterpret_cast<uintptr_t>(pool_out)) & mask) || ld_in % 2 || ld_out % 2)
+      return fail(TAL_ERR_INVALID, name + ": pools must be " + std::to_string(2 * sizeof(T)) + "-B aligned with even ld");
+  }
   if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return mode == TAL_MODE_EXACT
-             ? launch_round_clique<true, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
-                                                  mmax, s)
-             : launch_round_clique<false, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
-                                                   mmax, s);
-}
-
-// tal_agg_round_clique_col_<T> and tal_agg_round_clique_col_w_<T> (WSRC: per-source weights from
-// wtab_dev): K3c1, one column per lane - any ld, element-aligned pools.
-template <typename T, bool WSRC = false>
-int32_t agg_round_clique_col(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
-                             const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
-                             const float* wtab_dev = nullptr) {
-  const std::string name(fn);
-  if (!pool_in || !pool_out || !table_dev || (WSRC && !wtab_dev)) return fail(TAL_ERR_INVALID, name + ": null pointer");
-  if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
-  if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
-  if (n_cliques < 0 || n_cliques > 65535 || mmax < 1 || mmax > kCliqueColMax)
-    return fail(TAL_ERR_INVALID, name + ": 0 <= n_cliques <= 65535, 1 <= mmax <= 128");
-  if (n == 0 || n_cliques == 0) { g_err.clear(); return TAL_OK; }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return mode == TAL_MODE_EXACT
-             ? launch_round_clique_col<true, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s,
-                                                      wtab_dev)
-             : launch_round_clique_col<false, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax,
-                                                       s, wtab_dev);
+  return with_bool(mode == TAL_MODE_EXACT, [&](auto ex) {
+    constexpr bool kExact = decltype(ex)::value;
+    if constexpr (COL)
+      return launch_round_clique_col<kExact, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
+                                                      mmax, s);
+    else
+      return launch_round_clique<kExact, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
+                                                  mmax, s);
+  });
 }
 
 }  // namespace
@@ -5037,57 +5027,57 @@ const char* tal_round_kernel_name(const tal_round_plan_info* info, int32_t bf16)
 int32_t tal_agg_round_clique_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                  int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                  int32_t mode, void* stream) {
-  return agg_round_clique<float>("tal_agg_round_clique_f32", pool_in, ld_in, pool_out, ld_out, n, table_dev,
-                                 n_cliques, mmax, mode, stream);
+  return agg_round_clique<float, false, false>("tal_agg_round_clique_f32", pool_in, ld_in, pool_out, ld_out, n,
+                                               table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                   int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                   int32_t mode, void* stream) {
-  return agg_round_clique<uint16_t>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n, table_dev,
-                                    n_cliques, mmax, mode, stream);
+  return agg_round_clique<uint16_t, false, false>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                                  table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_col_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                      int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                      int32_t mode, void* stream) {
-  return agg_round_clique_col<float>("tal_agg_round_clique_col_f32", pool_in, ld_in, pool_out, ld_out, n, table_dev,
-                                     n_cliques, mmax, mode, stream);
+  return agg_round_clique<float, true, false>("tal_agg_round_clique_col_f32", pool_in, ld_in, pool_out, ld_out, n,
+                                              table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_col_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                       int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                       int32_t mode, void* stream) {
-  return agg_round_clique_col<uint16_t>("tal_agg_round_clique_col_bf16", pool_in, ld_in, pool_out, ld_out, n,
-                                        table_dev, n_cliques, mmax, mode, stream);
+  return agg_round_clique<uint16_t, true, false>("tal_agg_round_clique_col_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                                 table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_col_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                        int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                        int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique_col<float, true>("tal_agg_round_clique_col_w_f32", pool_in, ld_in, pool_out, ld_out, n,
-                                           table_dev, n_cliques, mmax, mode, stream, wtab_dev);
+  return agg_round_clique<float, true, true>("tal_agg_round_clique_col_w_f32", pool_in, ld_in, pool_out, ld_out, n,
+                                             table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_col_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                         int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                         int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique_col<uint16_t, true>("tal_agg_round_clique_col_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
-                                              table_dev, n_cliques, mmax, mode, stream, wtab_dev);
+  return agg_round_clique<uint16_t, true, true>("tal_agg_round_clique_col_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                                table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                    int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                    int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique<float, true>("tal_agg_round_clique_w_f32", pool_in, ld_in, pool_out, ld_out, n, table_dev,
-                                       n_cliques, mmax, mode, stream, wtab_dev);
+  return agg_round_clique<float, false, true>("tal_agg_round_clique_w_f32", pool_in, ld_in, pool_out, ld_out, n,
+                                              table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                     int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                     int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique<uint16_t, true>("tal_agg_round_clique_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
-                                          table_dev, n_cliques, mmax, mode, stream, wtab_dev);
+  return agg_round_clique<uint16_t, false, true>("tal_agg_round_clique_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                                 table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_bf16(const uint16_t* const* x_host, const double* w_host, int32_t m, uint16_t* out,

@@ -515,6 +515,7 @@ class CliquePlan:
     col_device: Optional[torch.Tensor] = None
     col_wtable: Optional[np.ndarray] = None
     col_wdevice: Optional[torch.Tensor] = None
+    on: Optional[torch.device] = None  # where the device copies are (to)
 
     @property
     def info(self) -> RoundPlanInfo:
@@ -533,18 +534,48 @@ class CliquePlan:
         """Source rows read from HBM per column (clique sources + the rest plan's)."""
         return self.clique_sources + (self.rest.staged_rows() if self.rest is not None else 0)
 
+    def make_spec(self) -> dict:
+        """The spec plan_from_spec rebuilds this plan from: its name, "members": 128 when it has
+        blocks of 65..128 members, and its rest plan's spec."""
+        return {self.spec_key: 1, **({"members": CLIQUE_COL_MAX} if self.n_col else {}),
+                "rest": self.rest.spec if self.rest is not None else None}
+
     def to(self, device) -> "CliquePlan":
-        self.device = torch.from_numpy(self.table).to(device)
-        if self.wtable is not None:
-            self.wdevice = torch.from_numpy(self.wtable).to(device)
-        if self.col_table is not None:
-            self.col_device = torch.from_numpy(self.col_table).to(device)
-        if self.col_wtable is not None:
-            self.col_wdevice = torch.from_numpy(self.col_wtable).to(device)
+        for host, attr in ((self.table, "device"), (self.wtable, "wdevice"), (self.col_table, "col_device"),
+                           (self.col_wtable, "col_wdevice")):
+            if host is not None:
+                setattr(self, attr, torch.from_numpy(host).to(device))
+        self.on = self.device.device
         if self.rest is not None:
             self.rest.to(device)
         self.full.to(device)
         return self
+
+    def row_bounds(self):
+        """(largest pool row the clique blocks read, largest they write); -1 for none."""
+        t = self.table.reshape(self.n_cliques, CLIQUE_WORDS)
+        att = t[:, 4 + 2 * CLIQUE_MAX:].reshape(self.n_cliques, CLIQUE_EXTRA, CLIQUE_EXTRA_WORDS)
+        att = att[np.arange(CLIQUE_EXTRA)[None, :] < t[:, 2:3]]  # attached records in use
+        ct = (self.col_table if self.col_table is not None else np.zeros(0, np.int32)).reshape(self.n_col, CLIQUE_COL_WORDS)
+        return (max(t[:, 4: 4 + CLIQUE_MAX].max(initial=-1), att[:, [5, 7, 8]].max(initial=-1),
+                    ct[:, 4: 4 + CLIQUE_COL_MAX].max(initial=-1)),
+                max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(initial=-1), att[:, 0].max(initial=-1),
+                    ct[:, 4 + CLIQUE_COL_MAX:].max(initial=-1)))
+
+
+def _clique_head(rec, wrec, cap, srcs, w32, outs):
+    """A block's head in a record of either layout (cap = CLIQUE_MAX or CLIQUE_COL_MAX members):
+    member count, weight - per source into wrec where the plan has a weight table, else the
+    record's weight word - sources, and output rows (-1: none)."""
+    rec[0] = len(srcs)
+    if wrec is not None:
+        wrec[: len(srcs)] = w32
+    else:
+        rec[1] = np.array([w32], np.float32).view(np.int32)[0]
+    rec[4: 4 + len(srcs)] = srcs
+    rec[4 + cap: 4 + 2 * cap] = -1
+    for i, o in outs.items():
+        rec[4 + cap + i] = o
 
 
 def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
@@ -570,29 +601,13 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
     col_table = np.zeros((len(wide), CLIQUE_COL_WORDS), np.int32) if wide else None
     col_wtable = np.ones((len(wide), CLIQUE_COL_WWORDS), np.float32) if wide and per_source else None
     for k, (srcs, w32, outs, _) in enumerate(wide):
-        col_table[k, 0] = len(srcs)
-        if per_source:
-            col_wtable[k, : len(srcs)] = w32
-        else:
-            col_table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
-        col_table[k, 4: 4 + len(srcs)] = srcs
-        col_table[k, 4 + CLIQUE_COL_MAX:] = -1
-        for i, o in outs.items():
-            col_table[k, 4 + CLIQUE_COL_MAX + i] = o
+        _clique_head(col_table[k], col_wtable[k] if per_source else None, CLIQUE_COL_MAX, srcs, w32, outs)
     table = np.zeros((len(cliques), CLIQUE_WORDS), np.int32)
     wtable = np.ones((len(cliques), CLIQUE_WWORDS), np.float32) if per_source else None
     n_ext_loads = 0
     for k, (srcs, w32, outs, att) in enumerate(cliques):
-        table[k, 0] = len(srcs)
-        if per_source:
-            wtable[k, : len(srcs)] = w32
-        else:
-            table[k, 1] = np.array([w32], np.float32).view(np.int32)[0]
+        _clique_head(table[k], wtable[k] if per_source else None, CLIQUE_MAX, srcs, w32, outs)
         table[k, 2] = len(att)
-        table[k, 4: 4 + len(srcs)] = srcs
-        table[k, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX] = -1
-        for i, o in outs.items():
-            table[k, 4 + CLIQUE_MAX + i] = o
         for q, a in enumerate(att):
             rec = table[k, 4 + 2 * CLIQUE_MAX + q * CLIQUE_EXTRA_WORDS:][:CLIQUE_EXTRA_WORDS]
             rec[0] = a["out"]
@@ -680,6 +695,27 @@ def rows_uniform(row_ptr, w) -> bool:
     return bool(np.array_equal(w32, first))
 
 
+# The clique variants by candidate key: build_clique_plan's keywords, the table that gates the
+# variant as a default (None: not gated), and whether a plan has the blocks the variant exists for
+_CLIQUE_VARIANTS = {
+    "clique": (dict(), None, lambda p: True),
+    "wclique": (dict(per_source=True), WCLIQUE_DEFAULT, lambda p: True),
+    "clique128": (dict(max_members=CLIQUE_COL_MAX), CLIQUE_COL_DEFAULT, lambda p: p.n_col > 0),
+    "wclique128": (dict(per_source=True, max_members=CLIQUE_COL_MAX, wide_per_source=True), WCLIQUE_COL_DEFAULT,
+                   lambda p: p.col_wtable is not None),
+}
+
+
+def _clique_variant(name, row_ptr, col, w, out_row, bf16) -> Optional[CliquePlan]:
+    """The variant's plan with its spec, or None where the round has no block of its kind."""
+    kw, _, has_blocks = _CLIQUE_VARIANTS[name]
+    p = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, **kw)
+    if p is None or not has_blocks(p):
+        return None
+    p.spec = p.make_spec()
+    return p
+
+
 def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT):
     """tune_plan's candidates [(key, plan)], the default plan first (host-side plans)."""
     base = default_plan(row_ptr, col, w, out_row, bf16=bf16, mode=mode)
@@ -708,34 +744,18 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
         key = ("bcast", c4, waves, wg)
         if all(key != k for k, _ in cands) and p.spec != base.spec:
             cands.append((key, p))
-    cp = base if isinstance(base, CliquePlan) else None
-    if cp is None:
-        cp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16)
-        if cp is not None:
-            cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
-            cands.append((("clique",), cp))
-    if cp is None or cp.wtable is None:
-        # per-source blocks (weighted / centrality apps on cliques): offered when they take rows
-        # no uniform-weight plan of the round takes
-        wp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True)
-        if wp is not None and wp.clique_rows > (cp.clique_rows if cp is not None else 0):
-            wp.spec = dict(wclique=1, rest=wp.rest.spec if wp.rest is not None else None)
-            cands.append((("wclique",), wp))
-    if cp is None or cp.n_col == 0:
-        # blocks of 65..128 members (K3c1): offered when they take rows the <= 64 plan does not
-        xp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, max_members=CLIQUE_COL_MAX)
-        if xp is not None and xp.n_col > 0 and xp.clique_rows > (cp.clique_rows if cp is not None and cp.wtable is None else 0):
-            xp.spec = dict(clique=1, members=CLIQUE_COL_MAX, rest=xp.rest.spec if xp.rest is not None else None)
-            cands.append((("clique128",), xp))
-    if cp is None or cp.col_wtable is None:
-        # per-source blocks of 65..128 members (K3c1 with per-source weights): offered when the
-        # plan has such a block, that is, takes rows no other clique plan takes
-        yp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True, max_members=CLIQUE_COL_MAX,
-                               wide_per_source=True)
-        taken = max((c.clique_rows for _, c in cands if isinstance(c, CliquePlan)), default=0)
-        if yp is not None and yp.col_wtable is not None and yp.clique_rows > taken:
-            yp.spec = dict(wclique=1, members=CLIQUE_COL_MAX, rest=yp.rest.spec if yp.rest is not None else None)
-            cands.append((("wclique128",), yp))
+    for name, (kw, _, _) in _CLIQUE_VARIANTS.items():
+        # a clique variant is offered when no clique plan already among the candidates is of its
+        # kind (per-source weights, blocks of 65..128 members) and it takes rows none of them
+        # takes; per-source plans (weighted / centrality apps on cliques) do not count against a
+        # uniform-weight variant
+        have = [c for _, c in cands if isinstance(c, CliquePlan)]
+        per, wide = kw.get("per_source", False), "max_members" in kw
+        if any((c.wtable is not None or not per) and (c.n_col > 0 or not wide) for c in have):
+            continue
+        p = _clique_variant(name, row_ptr, col, w, out_row, bf16)
+        if p is not None and p.clique_rows > max((c.clique_rows for c in have if per or c.wtable is None), default=0):
+            cands.append(((name,), p))
     return cands
 
 
@@ -769,7 +789,7 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     if isinstance(base, CliquePlan) and base.rest is not None:  # the rows outside the cliques: tuned too
         r_rp, r_col, r_w, r_out = _sub_csr(row_ptr, col, w, out_row, base.rest_rows)
         base.rest = tune_plan(r_rp, r_col, r_w, r_out, pool_in, pool_out, n=n, reps=reps, mode=mode, margin=margin)
-        base.spec = {base.spec_key: 1, **({"members": CLIQUE_COL_MAX} if base.n_col else {}), "rest": base.rest.spec}
+        base.spec = base.make_spec()
     if len(cands) == 1:
         return base.to(pool_in.device)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -829,50 +849,27 @@ def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
 
 
 def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT):
-    """The plan the round components build when they do not time candidates (tune=False):
-    the round's uniform-weight clique blocks by K3c when it has any (the other rows by their own
-    sparse plan), else build_plan's sparse form at the tile width and LDS budget its cost model
-    picks.  On the round-1 A/B tables this is the measured winner's form for configs 2-5
-    (tests/test_host_logic.py::test_default_plan_forms).  bf16 pools take the clique plan in
-    both modes: against the sparse form they ran before (medians of 20 interleaved runs,
-    tools/clique_bf16_rate.py, profiles/r12) config 4 on bf16 - barbell(60, 8), 128 x ResNet-50 -
-    took 7.38 ms against 19.05 in EXACT mode and 6.11 against 8.48 in FMA mode, and the complete
-    graph of 64 (`unweighted_fl`, CIFAR-CNN width) 0.869 against 5.23 and 0.729 against 2.26; each
-    is past tune_plan's 1 % margin and the forms agree bit for bit (block sizes other than 60
-    and 64 were not timed on bf16; they follow the fp32 rule).  A round without uniform blocks
-    whose clique rows carry one weight per source (`weighted_module_avg`, `centrality_module_avg`
-    on a barbell or a complete graph) takes the per-source clique plan (K3c with per-source
-    weights, spec {"wclique": 1}) for fp32 and bf16 in both modes (WCLIQUE_DEFAULT): against the
-    sparse c4 = 128 plan this function returned before (medians of 20 interleaved runs,
-    tools/clique_weighted_rate.py, profiles/r13) config 4 under degree-centrality softmax /
-    data-size weights took, fp32 EXACT 4.54 / 4.60 ms against 11.42 / 11.48, fp32 FMA 4.66 / 4.66
-    against 9.46 / 9.47, bf16 EXACT 7.57 / 7.55 against 19.13 / 19.14, bf16 FMA 7.89 / 7.88 against
-    8.65 / 8.66 (the closest: 9 %), each past tune_plan's 1 % margin on both rounds, the forms
-    agreeing bit for bit; a round that has uniform blocks keeps exactly the plan above.  A round with a
-    uniform-weight block of 65..128 members (`unweighted_fl` over 66 or 100 clients: one complete
-    graph) takes the 128-member clique plan (K3c1, one column per lane, spec {"clique": 1,
-    "members": 128}) for fp32 and bf16 in both modes (CLIQUE_COL_DEFAULT): against the sparse
-    plan this function returned before (medians of 20 interleaved runs, tools/clique_col_rate.py,
-    profiles/r14; complete 66 / complete 100 at CIFAR-CNN width) fp32 EXACT took 0.598 / 0.999 ms
-    against 2.235 / 3.276, fp32 FMA 0.603 / 0.985 against 1.828 / 2.654, bf16 EXACT 0.835 / 1.858
-    against 4.275 / 5.885, bf16 FMA 0.488 / 0.907 against 1.755 / 2.279 (the closest: 2.5x), each
-    past tune_plan's 1 % margin on both rounds, the forms agreeing bit for bit; rounds whose blocks
-    all have <= 64 members keep exactly the plans above.  A round without uniform blocks that has
-    a per-source block of 65..128 members (`weighted_module_avg` over 66 or 100 clients of a
-    complete graph, the weighted and centrality apps on a barbell with cliques past 64) takes the
-    per-source 128-member plan (K3c1 with per-source weights, spec {"wclique": 1, "members": 128})
-    for fp32 and bf16 in both modes (WCLIQUE_COL_DEFAULT): against the plan this function returned
-    before - the sparse c4 = 128 plan, or on complete 100 the narrow broadcast forms below -
-    (medians of 20 interleaved runs, tools/clique_col_weighted_rate.py, profiles/r17; complete 66 /
-    complete 100 at CIFAR-CNN width / complete 100 at ResNet-50 width under data-size weights /
-    barbell(66, 3) at CIFAR-CNN width under degree-centrality softmax) fp32 EXACT took 0.576 /
-    0.985 / 4.226 / 1.889 ms against 2.354 / 3.731 / 15.172 / 4.655, fp32 FMA 0.579 / 1.068 / 4.437
-    / 1.864 against 1.914 / 2.894 / 12.153 / 3.797, bf16 EXACT 0.818 / 1.938 / 7.589 / 2.365 against
-    4.248 / 7.777 / 31.380 / 8.447, bf16 FMA 0.521 / 0.950 / 4.023 / 1.568 against 1.754 / 2.609 /
-    11.033 / 3.484 (the closest: 2.0x), each past tune_plan's 1 % margin on all four rounds, the
-    forms agreeing bit for bit; rounds without such a block keep exactly the plans above.  One
-    exception, from
-    round 4's measurements: a round whose narrow plan needs per-operand weights (the pairs
+    """The plan the round components build when they do not time candidates (tune=False).
+    A round with clique blocks takes the first clique variant (_CLIQUE_VARIANTS) that finds
+    blocks of its kind, in this order of preference:
+      clique128   a uniform-weight block of 65..128 members (`unweighted_fl` over 66 or 100
+                  clients): K3c1, spec {"clique": 1, "members": 128}; gated by CLIQUE_COL_DEFAULT
+      clique      uniform-weight blocks of <= 64 members: K3c, spec {"clique": 1}; never gated
+      wclique128  no uniform block, a per-source block of 65..128 members (`weighted_module_avg`,
+                  `centrality_module_avg` past 64 clients): K3c1 with per-source weights, spec
+                  {"wclique": 1, "members": 128}; gated by WCLIQUE_COL_DEFAULT
+      wclique     no uniform block, per-source blocks of <= 64 members: K3c with per-source
+                  weights, spec {"wclique": 1}; gated by WCLIQUE_DEFAULT
+    with the other rows in a sparse plan of their own; a round that lacks a variant's blocks, or
+    whose (bf16, mode) the variant's table switches off, keeps exactly the plan of the lines below
+    it.  Each table is True where the variant beat the plan returned before it by more than
+    tune_plan's 1 % margin on every measured round, the forms agreeing bit for bit: the
+    measurements are in DESIGN §4 and beside the *_DEFAULT tables (tools/clique_*_rate.py;
+    profiles/r12, r13, r14 and r17).  A round without clique blocks takes
+    build_plan's sparse form at the tile width and LDS budget its cost model picks; on the round-1
+    A/B tables this is the measured winner's form for configs 2-5
+    (tests/test_host_logic.py::test_default_plan_forms).  One exception, from round 4's
+    measurements: a round whose narrow plan needs per-operand weights (the pairs
     form: centrality weights on a graph whose degrees differ) runs the narrow kernel's
     broadcast form with the whole source set in one LDS tile — for bf16 in FMA mode the
     two-chunk form (c4 = 32, 16 wavefronts, one workgroup per CU; config 5 with
@@ -887,26 +884,12 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     bf16 pools the wide-row kernel - or, rows out of reference order, one K1 call per row
     (RowCallPlan)."""
     try:
-        if CLIQUE_COL_DEFAULT[bool(bf16), int(mode)]:
-            xp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, max_members=CLIQUE_COL_MAX)
-            if xp is not None and xp.n_col > 0:  # a round without such a block keeps the plan below
-                xp.spec = dict(clique=1, members=CLIQUE_COL_MAX, rest=xp.rest.spec if xp.rest is not None else None)
-                return xp
-        cp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16)
-        if cp is not None:
-            cp.spec = dict(clique=1, rest=cp.rest.spec if cp.rest is not None else None)
-            return cp
-        if WCLIQUE_COL_DEFAULT[bool(bf16), int(mode)]:
-            yp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True, max_members=CLIQUE_COL_MAX,
-                                   wide_per_source=True)
-            if yp is not None and yp.col_wtable is not None:  # a round without such a block keeps the plan below
-                yp.spec = dict(wclique=1, members=CLIQUE_COL_MAX, rest=yp.rest.spec if yp.rest is not None else None)
-                return yp
-        if WCLIQUE_DEFAULT[bool(bf16), int(mode)]:
-            wp = build_clique_plan(row_ptr, col, w, out_row, bf16=bf16, per_source=True)
-            if wp is not None:
-                wp.spec = dict(wclique=1, rest=wp.rest.spec if wp.rest is not None else None)
-                return wp
+        for name in ("clique128", "clique", "wclique128", "wclique"):
+            gate = _CLIQUE_VARIANTS[name][1]
+            if gate is None or gate[bool(bf16), int(mode)]:
+                cp = _clique_variant(name, row_ptr, col, w, out_row, bf16)
+                if cp is not None:  # a round without the variant's blocks keeps the plans below
+                    return cp
         p = build_plan(row_ptr, col, w, out_row, dense=0)
     except _lib.TalError as exc:
         if exc.code != _lib.TAL_ERR_CAPACITY:
@@ -982,11 +965,7 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
     return _round(pool_in, pool_out, plan, n, torch.float32, mode, stream)
 
 
-_CLIQUE_FN = {torch.float32: "tal_agg_round_clique_f32", torch.bfloat16: "tal_agg_round_clique_bf16"}
-_CLIQUE_W_FN = {torch.float32: "tal_agg_round_clique_w_f32", torch.bfloat16: "tal_agg_round_clique_w_bf16"}
-_CLIQUE_COL_FN = {torch.float32: "tal_agg_round_clique_col_f32", torch.bfloat16: "tal_agg_round_clique_col_bf16"}
-_CLIQUE_COL_W_FN = {torch.float32: "tal_agg_round_clique_col_w_f32",
-                    torch.bfloat16: "tal_agg_round_clique_col_w_bf16"}
+_CLIQUE_SUFFIX = {torch.float32: "_f32", torch.bfloat16: "_bf16"}
 
 
 def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
@@ -998,9 +977,7 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
         raise ValueError("pools on different devices")
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("a clique round runs out of place (snapshot semantics)")
-    if (plan.device is None or plan.device.device != pool_in.device or (plan.wtable is not None and plan.wdevice is None)
-            or (plan.col_table is not None and plan.col_device is None)
-            or (plan.col_wtable is not None and plan.col_wdevice is None)):
+    if plan.on != pool_in.device:
         plan.to(pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
     pair = 2 * pool_in.element_size()
@@ -1009,34 +986,22 @@ def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
         # K3c reads and writes column pairs (8 B fp32, 4 B bf16): rows not aligned to one take the full plan
         # (K3c1 has no such rule: a plan of 65..128-member blocks alone never gets here)
         return _round(pool_in, pool_out, plan.full, n, dtype, mode, stream)
-    t = plan.table.reshape(plan.n_cliques, CLIQUE_WORDS)
-    att = t[:, 4 + 2 * CLIQUE_MAX:].reshape(plan.n_cliques, CLIQUE_EXTRA, CLIQUE_EXTRA_WORDS)
-    used = np.arange(CLIQUE_EXTRA)[None, :] < t[:, 2:3]  # attached records in use
-    ct = (plan.col_table if plan.col_table is not None else np.zeros(0, np.int32)).reshape(plan.n_col, CLIQUE_COL_WORDS)
-    if max(t[:, 4: 4 + CLIQUE_MAX].max(initial=-1), att[used][:, [5, 7, 8]].max(initial=-1),
-           ct[:, 4: 4 + CLIQUE_COL_MAX].max(initial=-1)) >= pool_in.shape[0]:
+    reads, writes = plan.row_bounds()
+    if reads >= pool_in.shape[0]:
         raise ValueError("plan reads a pool row beyond pool_in")
-    if max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(initial=-1), att[used][:, 0].max(initial=-1),
-           ct[:, 4 + CLIQUE_COL_MAX:].max(initial=-1)) >= pool_out.shape[0]:
+    if writes >= pool_out.shape[0]:
         raise ValueError("plan writes a pool row beyond pool_out")
     L = _lib.load()
-    head = (ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
-            pool_out.stride(0), n)
-    args = (*head, ctypes.c_void_p(plan.device.data_ptr()), plan.n_cliques, plan.mmax, int(mode),
-            _stream(pool_in.device, stream))
-    if plan.n_cliques == 0:
-        pass  # blocks of 65..128 members only
-    elif plan.wtable is not None:  # per-source weights
-        check(getattr(L, _CLIQUE_W_FN[dtype])(*args, ctypes.c_void_p(plan.wdevice.data_ptr())))
-    else:
-        check(getattr(L, _CLIQUE_FN[dtype])(*args))
-    if plan.n_col > 0:  # blocks of 65..128 members: K3c1, with per-source weights where the plan carries them
-        cargs = (*head, ctypes.c_void_p(plan.col_device.data_ptr()), plan.n_col, plan.col_mmax, int(mode),
-                 _stream(pool_in.device, stream))
-        if plan.col_wtable is not None:
-            check(getattr(L, _CLIQUE_COL_W_FN[dtype])(*cargs, ctypes.c_void_p(plan.col_wdevice.data_ptr())))
-        else:
-            check(getattr(L, _CLIQUE_COL_FN[dtype])(*cargs))
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    # K3c for the blocks of <= 64 members, then K3c1 for those of 65..128, each with per-source
+    # weights where the plan carries them; the entry is looked up by name at every call
+    for col_form, table, blocks, mmax, wtab in (
+            (False, plan.device, plan.n_cliques, plan.mmax, plan.wdevice if plan.wtable is not None else None),
+            (True, plan.col_device, plan.n_col, plan.col_mmax, plan.col_wdevice if plan.col_wtable is not None else None)):
+        if blocks > 0:
+            fn = getattr(L, "tal_agg_round_clique" + "_col" * col_form + "_w" * (wtab is not None) + _CLIQUE_SUFFIX[dtype])
+            check(fn(ptr(pool_in), pool_in.stride(0), ptr(pool_out), pool_out.stride(0), n, ptr(table), blocks, mmax,
+                     int(mode), _stream(pool_in.device, stream), *((ptr(wtab),) if wtab is not None else ())))
     if plan.rest is not None:
         _round(pool_in, pool_out, plan.rest, n, dtype, mode, stream)
     return pool_out
