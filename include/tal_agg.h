@@ -59,7 +59,8 @@ const char* tal_last_error(void);
 /* ABI version (bumped on any signature change).  ABI 33 removed the round over
  * register-resident source groups (K3r) with its entry point: no plan the library picks ever
  * selected it.  ABI 34 added the column clique entries with per-source weights
- * (tal_agg_round_clique_col_w_*). */
+ * (tal_agg_round_clique_col_w_*).  ABI 35 added the sequential round in one launch (K3q:
+ * tal_seq_plan_*, tal_agg_round_seq_*). */
 int32_t tal_abi_version(void);
 
 /* ---- K1: one aggregation call over M flattened operands --------------------------------
@@ -368,7 +369,79 @@ int32_t tal_agg_round_clique_col_w_bf16(const uint16_t* pool_in, int64_t ld_in, 
                                         int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
                                         const float* wtab_dev);
 
-/* The same round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
+/* ---- K3q: a sequential round in one launch (ABI 35) -----------------------------------------
+ * The reference's round under one aggregation thread: its apps overwrite the client models that
+ * later apps of the same round read (decentralized_client.py:413, decentralized_app.py:606,629),
+ * so clients go in order and each call sees the earlier calls' writes.  In place on one pool:
+ *
+ *   for r = 0 .. rows-1, in plan order:
+ *     pool[out_row[r]][e] = chain over k = row_ptr[r] .. row_ptr[r+1]-1 of (fp32(w[k]), pool[col[k]][e])
+ *
+ * where pool is the state rows 0 .. r-1 of this call left (a row reads its own old value where it
+ * lists itself).  The chain is tal_agg_f32 / tal_agg_bf16 / tal_agg_i64's per dtype and mode, from
+ * the same device code, so row r has the bits of that call on the running pool: fp32 EXACT a
+ * separate multiply and add per operand, FMA fl(w_0 x_0) then fma; bf16 EXACT every product and
+ * sum rounded to bf16, FMA rounded once at the store (NaN stored as 0xFFFF); int64 operands
+ * converted to fp32, accumulated in fp32 and truncated toward zero (NaN / out of range:
+ * INT64_MIN).  The value later rows read is the stored one (bf16: the rounded value; int64: the
+ * truncated integer).  Rows keep the caller's order - the order of the sweep - and operands the
+ * caller's order; any operand order and count is legal and a source may occur twice in a row.
+ * Pool rows the round does not write are not touched.
+ *
+ * The sweep is independent per element column: a wavefront owns a tile of 64 columns for the
+ * whole round (one column per lane; each source row's piece staged into LDS once, each result
+ * written to HBM and back into its LDS slot), so every model is read once and no spare pool is
+ * needed.  One column per lane: any ld >= n, element-aligned pools.  At most TAL_SEQ_MAX_SRC
+ * distinct source rows (a 64-column fp32 tile of 256 sources is 64 KiB of LDS for one wave).
+ * The int64 entry runs one thread per column on global memory.
+ *
+ * Plan blob (int32 words, built on the host, copied to the device by the caller):
+ *   {rows, nnz, n_src, words, max_row, max_ops, 0, 0}
+ *   src_row[n_src]   the distinct pool rows that occur as operands, ascending; a row's slot is
+ *                    its index here
+ *   row_ptr[rows+1]
+ *   op_slot[nnz]     slot of each operand
+ *   op_w[nnz]        fp32 bits of (float)w
+ *   out_row[rows]
+ *   out_slot[rows]   slot of out_row[r], or -1 when no row reads it
+ *   0 x 8            padding: the kernel reads the plan eight words at a time
+ * tal_seq_plan_build: TAL_ERR_INVALID for a null array, rows <= 0, an empty row, a negative pool
+ * row or an out_row listed twice; TAL_ERR_CAPACITY when n_src > TAL_SEQ_MAX_SRC, and when
+ * plan_host is null or capacity_words too small (info->words then holds the size needed; info is
+ * filled in both cases).  tal_seq_plan_words is an upper bound for any such round.
+ *
+ * tal_agg_round_seq_*: pool_rows = rows of the pool.  TAL_ERR_INVALID, with no launch, for a null
+ * pointer, n < 0, ld < n or a plan row >= pool_rows (info->max_row); n == 0 returns TAL_OK
+ * without a launch. */
+#define TAL_SEQ_MAX_SRC 256
+typedef struct tal_seq_plan_info {
+  int32_t rows;          /* rows of the round */
+  int32_t nnz;           /* operands over all rows */
+  int32_t n_src;         /* distinct source rows (LDS slots) */
+  int32_t max_row;       /* largest pool row read or written */
+  int32_t max_ops;       /* operands of the longest row */
+  /* offsets (int32 words) of the arrays inside the blob */
+  int32_t off_src_row;
+  int32_t off_row_ptr;
+  int32_t off_op_slot;
+  int32_t off_op_w;
+  int32_t off_out_row;
+  int32_t off_out_slot;
+  int32_t reserved;
+  int64_t words;         /* total int32 words of the blob */
+} tal_seq_plan_info;
+int64_t tal_seq_plan_words(int32_t rows, int64_t nnz);
+int32_t tal_seq_plan_build(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
+                           const double* w_host, const int32_t* out_row_host, int32_t* plan_host,
+                           int64_t capacity_words, tal_seq_plan_info* info);
+int32_t tal_agg_round_seq_f32(float* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                              const tal_seq_plan_info* info, int32_t mode, void* stream);
+int32_t tal_agg_round_seq_bf16(uint16_t* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                               const tal_seq_plan_info* info, int32_t mode, void* stream);
+int32_t tal_agg_round_seq_i64(int64_t* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                              const tal_seq_plan_info* info, void* stream);
+
+/* tal_agg_round_f32's round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or
  * streamed plans.  A staged tile holds the sources' values as fp32 (c4 float4 per source). */
 int32_t tal_agg_round_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,

@@ -5,7 +5,8 @@ checkpoint/resume protocol follow the reference (decentralized_app.py:96-644).  
 difference: when a GPU is visible every client's model is bound to one device-resident
 ModelPool row (topology_aware_learning_amd.arena), so local training and the aggregation
 kernels work on the same HBM bytes and no model crosses PCIe between rounds
-(TAL_DEVICE_POOL=0 keeps the reference's CPU-resident models).  TAL_BATCHED_ROUND=1 (opt-in)
+(TAL_DEVICE_POOL=0 keeps the reference's CPU-resident models).  TAL_BATCHED_ROUND=1 (opt-in;
+=seq: the same batch as a sequential round, clients in order, one K3q launch per segment)
 runs each round's aggregations as one K3 launch over that pool, with snapshot semantics.
 """
 from __future__ import annotations
@@ -82,6 +83,8 @@ class _Resolved(Future):
 
 class DecentrallearnApp:
     """Decentralized learning experiment (reference :58-454)."""
+
+    sequential_round = False  # TAL_BATCHED_ROUND=seq (set in __init__): the batch as a sequential round
 
     def __init__(self, data_dir: str = "../data", topology_path: str = "topology/topo_1.txt",
                  dataset: str = "mnist", rounds: int = 5, batch_size: int = 16, epochs: int = 2,
@@ -171,7 +174,17 @@ class DecentrallearnApp:
         self.pool = self._bind_device_pool()
         # opt-in (no CLI change): the round's aggregations as one K3 launch with snapshot
         # semantics instead of one app call per client (the reference's form, the default)
-        self.batched_round = os.environ.get("TAL_BATCHED_ROUND", "0") == "1" and self.pool is not None
+        # =seq: the same batch as a sequential round (RoundExecutor.run(sequential=True)): clients in
+        # the order of the batch, each reading the models the earlier ones left - the reference's
+        # round under one aggregation thread
+        batched = os.environ.get("TAL_BATCHED_ROUND", "0")
+        self.batched_round = batched in ("1", "seq") and self.pool is not None
+        self.sequential_round = self.batched_round and batched == "seq"
+        if self.sequential_round:
+            why = self._seq_round_per_call()
+            if why:
+                print(f"TAL_BATCHED_ROUND=seq: {why}; the round runs as one app call per client")
+                self.batched_round = self.sequential_round = False
         self._executor = None
         self._round_cache: dict = {}  # _round_key -> the round's rows, weights and printout
         self.round_cache_hits = 0
@@ -218,6 +231,21 @@ class DecentrallearnApp:
             c.model.to(pool.device)
             pool.bind(c.model, c.idx)
         return pool
+
+    def _seq_round_per_call(self) -> str:
+        """Why TAL_BATCHED_ROUND=seq takes the per-call app path ("" when it does not): a `*_sim`
+        strategy's similarities must be taken at each client's turn, on the models the earlier
+        clients left; a MultiPool's clients are spread over several pools."""
+        from topology_aware_learning_amd.multipool import MultiPool
+
+        from src.decentralized_client import weight_rule
+
+        rule = weight_rule(self.aggregation_function)
+        if rule is not None and rule.__name__ == "_sim_centrality_weights":
+            return "a *_sim strategy takes its similarities at each client's turn"
+        if isinstance(self.pool, MultiPool):
+            return "the models are spread over several GPUs (TAL_GPUS)"
+        return ""
 
     def close(self) -> None:
         pass
@@ -347,7 +375,10 @@ class DecentrallearnApp:
             self.round_cache_hits += 1
             if self.seed is not None:
                 manual_seed(self.seed)
-            self._executor.run(hit["orders"], hit["weights"], hit["out_rows"], plan=hit["plan"])
+            if self.sequential_round:
+                self._executor.run(hit["orders"], hit["weights"], hit["out_rows"], sequential=True)
+            else:
+                self._executor.run(hit["orders"], hit["weights"], hit["out_rows"], plan=hit["plan"])
             return [memo[id(e[2])] for e in batch]
         row_of: dict = {}  # id(model) -> pool row
 
@@ -383,8 +414,12 @@ class DecentrallearnApp:
         if orders:
             if self._executor is None:
                 self._executor = RoundExecutor(self.pool)
-            plan = self._executor.plan(orders, weights, out_rows)
-            self._executor.run(orders, weights, out_rows, plan=plan)
+            if self.sequential_round:  # the executor keeps the sequential plan of these lists itself
+                plan = None
+                self._executor.run(orders, weights, out_rows, sequential=True)
+            else:
+                plan = self._executor.plan(orders, weights, out_rows)
+                self._executor.run(orders, weights, out_rows, plan=plan)
             if key is not None:
                 if len(self._round_cache) > 16:
                     self._round_cache.clear()

@@ -27,7 +27,7 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 EXPORTED = (
     "tal_last_error",
@@ -53,6 +53,11 @@ EXPORTED = (
     "tal_agg_round_clique_col_bf16",
     "tal_agg_round_clique_col_w_f32",
     "tal_agg_round_clique_col_w_bf16",
+    "tal_seq_plan_words",
+    "tal_seq_plan_build",
+    "tal_agg_round_seq_f32",
+    "tal_agg_round_seq_bf16",
+    "tal_agg_round_seq_i64",
     "tal_cosine_plan_words",
     "tal_cosine_plan_build",
     "tal_cosine_plan_set_threads",
@@ -142,6 +147,26 @@ class RoundPlanInfo(ctypes.Structure):
     ]
 
 
+class SeqPlanInfo(ctypes.Structure):
+    """tal_seq_plan_info (tal_agg.h K3q)."""
+
+    _fields_ = [
+        ("rows", ctypes.c_int32),
+        ("nnz", ctypes.c_int32),
+        ("n_src", ctypes.c_int32),
+        ("max_row", ctypes.c_int32),
+        ("max_ops", ctypes.c_int32),
+        ("off_src_row", ctypes.c_int32),
+        ("off_row_ptr", ctypes.c_int32),
+        ("off_op_slot", ctypes.c_int32),
+        ("off_op_w", ctypes.c_int32),
+        ("off_out_row", ctypes.c_int32),
+        ("off_out_slot", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("words", ctypes.c_int64),
+    ]
+
+
 class CosineRoundInfo(ctypes.Structure):
     """tal_cosine_round_info (tal_agg.h K2r)."""
 
@@ -199,6 +224,11 @@ _SIGS = {
     "tal_agg_round_clique_col_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_clique_col_w_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_agg_round_clique_col_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
+    "tal_seq_plan_words": (_I64, [_I32, _I64]),
+    "tal_seq_plan_build": (_I32, [_I32, _PI32, _PI32, _PD, _PI32, _PI32, _I64, ctypes.POINTER(SeqPlanInfo)]),
+    "tal_agg_round_seq_f32": (_I32, [_P, _I64, _I64, _I64, _P, ctypes.POINTER(SeqPlanInfo), _I32, _P]),
+    "tal_agg_round_seq_bf16": (_I32, [_P, _I64, _I64, _I64, _P, ctypes.POINTER(SeqPlanInfo), _I32, _P]),
+    "tal_agg_round_seq_i64": (_I32, [_P, _I64, _I64, _I64, _P, ctypes.POINTER(SeqPlanInfo), _P]),
     "tal_cosine_plan_words": (_I64, [_PI64, _I32]),
     "tal_cosine_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),
     "tal_cosine_plan_set_threads": (_I32, [_PI64, _I32]),

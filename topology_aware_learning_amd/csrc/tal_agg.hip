@@ -46,7 +46,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 34;
+constexpr int kAbiVersion = 35;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -2703,6 +2703,195 @@ int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld
   return check_launch("clique round kernel (one column per lane)");
 }
 
+// ------------------------------------------------------------------------------------------
+// K3q: a sequential round in one launch, in place on one pool.  Rows run in plan order and row r
+// reads the pool as rows 0 .. r-1 of the call left it (the reference's round under one
+// aggregation thread: decentralized_client.py:413 overwrites the model later apps of the round
+// read).  The sweep is independent per element column, so one wavefront owns a tile of
+// kSeqTile columns for the whole round, one column per lane: it stages the column of every
+// source row into LDS (each model read once), walks the rows in order reading operands from
+// LDS, stores each row to HBM and writes the stored value back into the row's LDS slot for the
+// rows after it.  A lane touches only its own column of the tile, so program order is all the
+// ordering there is: no barrier, and no other wave sees the tile.  Every column of a tile is
+// staged before the tile's first store and tiles are disjoint, hence in place.
+//
+// Plan blob (tal_seq_plan_build): {rows, nnz, n_src, words, max_row, max_ops, 0, 0},
+// src_row[n_src], row_ptr[rows+1], op_slot[nnz], op_w[nnz], out_row[rows], out_slot[rows], eight
+// zero words; all wave-uniform and read through the constant address space (scalar loads).
+// ------------------------------------------------------------------------------------------
+constexpr int kSeqTile = 64;
+constexpr int kSeqHeader = 8;
+static_assert(TAL_SEQ_MAX_SRC * kSeqTile * 4 <= 64 * 1024, "a full fp32 tile is 64 KiB of LDS");
+
+// What a staged value is kept as in LDS.  fp32: itself.  bf16: its 16 bits (TAL_SEQ_BF16_LDS 16,
+// the default: half the tile, so twice the waves on a CU, for a 16-bit read and a shift per
+// operand) or widened to fp32 (32: the A/B build; 1.6x slower on every measured round, DESIGN §4
+// "K3q").
+#ifndef TAL_SEQ_BF16_LDS
+#define TAL_SEQ_BF16_LDS 16
+#endif
+template <typename T>
+struct SeqCell {
+  typedef float type;
+  static __device__ __forceinline__ float get(float c) { return c; }
+  static __device__ __forceinline__ float put(float v) { return v; }
+};
+#if TAL_SEQ_BF16_LDS == 16
+template <>
+struct SeqCell<uint16_t> {
+  typedef uint16_t type;
+  static __device__ __forceinline__ float get(uint16_t c) { return __uint_as_float(static_cast<uint32_t>(c) << 16); }
+  static __device__ __forceinline__ uint16_t put(float v) { return static_cast<uint16_t>(__float_as_uint(v) >> 16); }
+};
+#endif
+
+// Store the chain's value to row[e] and return the value a later read of row[e] gives: fp32
+// itself, bf16 the rounded value (Io<uint16_t>::st1's bits: a NaN is 0xFFFF).
+__device__ __forceinline__ float seq_store(float* row, int64_t e, float v) {
+  Io<float>::st1(row, e, v);
+  return v;
+}
+__device__ __forceinline__ float seq_store(uint16_t* row, int64_t e, float v) {
+  const uint32_t b = store_bf16x2(v, 0.f) & 0xffffu;
+  row[e] = static_cast<uint16_t>(b);
+  return __uint_as_float(b << 16);
+}
+
+struct SeqPlanView {
+  int rows, nnz, n_src;
+  ConstI32 src_row, row_ptr, op_slot, out_row, out_slot;
+  ConstF32 op_w;
+  __device__ __forceinline__ explicit SeqPlanView(const int32_t* plan) {
+    const ConstI32 p = (ConstI32)plan;
+    rows = p[0], nnz = p[1], n_src = p[2];
+    src_row = p + kSeqHeader;
+    row_ptr = src_row + n_src;
+    op_slot = row_ptr + rows + 1;
+    op_w = (ConstF32)(op_slot + nnz);
+    out_row = op_slot + 2 * static_cast<int64_t>(nnz);
+    out_slot = out_row + rows;
+  }
+};
+
+// f(std::integral_constant<int, cnt>) for a wave-uniform cnt in 1..8: one scalar branch, then
+// straight-line code for that many loads or chain steps.
+template <class F>
+__device__ __forceinline__ void seq_counted(int cnt, F&& f) {
+  switch (cnt) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: break;
+  }
+}
+
+// Eight consecutive plan words from index i on.  The blob ends in kSeqBatch words of padding, so
+// a batch that starts inside an array stays inside the blob whatever the count in use is.
+constexpr int kSeqBatch = 8;
+template <class P>
+__device__ __forceinline__ void seq_batch(P a, int64_t i, decltype(+a[0]) (&v)[kSeqBatch]) {
+#pragma unroll
+  for (int u = 0; u < kSeqBatch; ++u) v[u] = a[i + u];
+}
+
+template <typename T, bool EXACT>
+__global__ __launch_bounds__(kSeqTile) void k_round_seq(T* pool, int64_t ld, int64_t n, const int32_t* plan) {
+  typedef SeqCell<T> Cell;
+  extern __shared__ float4 s_data[];
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * kSeqTile + threadIdx.x;
+  if (e >= n) return;  // no barrier below: the lanes past n are not needed
+  // the lane's column of the tile: slot s at col[s * kSeqTile]
+  typename Cell::type* const col = reinterpret_cast<typename Cell::type*>(s_data) + threadIdx.x;
+  const SeqPlanView p(plan);
+  // stage: each source row's column, eight loads in flight per lane
+  for (int s0 = 0; s0 < p.n_src; s0 += kSeqBatch) {
+    int32_t row[kSeqBatch];
+    seq_batch(p.src_row, s0, row);
+    seq_counted(min(kSeqBatch, p.n_src - s0), [&](auto cnt) {
+      float v[decltype(cnt)::value];
+#pragma unroll
+      for (int j = 0; j < decltype(cnt)::value; ++j) v[j] = Io<T>::ld1(pool + static_cast<int64_t>(row[j]) * ld, e);
+#pragma unroll
+      for (int j = 0; j < decltype(cnt)::value; ++j) col[(s0 + j) * kSeqTile] = Cell::put(v[j]);
+    });
+  }
+  // the sweep.  Everything a row needs from the plan - its extent, its first operand, a batch of
+  // eight more, where it goes - is asked for at the top of the row, before the first use: one
+  // scalar-memory round trip per row of up to nine operands.
+  int q0 = p.row_ptr[0];
+  for (int r = 0; r < p.rows; ++r) {
+    const int q1 = p.row_ptr[r + 1];
+    const int orow = p.out_row[r], oslot = p.out_slot[r];
+    const int s_first = p.op_slot[q0];
+    const float w_first = p.op_w[q0];
+    int32_t sl[kSeqBatch];
+    float w[kSeqBatch];
+    seq_batch(p.op_slot, q0 + 1, sl);
+    seq_batch(p.op_w, q0 + 1, w);
+    float acc = first1t<T, EXACT>(w_first, Cell::get(col[s_first * kSeqTile]));
+    for (int q = q0 + 1; q < q1;) {
+      // a batch's LDS reads, then its ordered steps
+      seq_counted(min(kSeqBatch, q1 - q), [&](auto cnt) {
+        float x[decltype(cnt)::value];
+#pragma unroll
+        for (int u = 0; u < decltype(cnt)::value; ++u) x[u] = Cell::get(col[sl[u] * kSeqTile]);
+#pragma unroll
+        for (int u = 0; u < decltype(cnt)::value; ++u) acc = next1t<T, EXACT>(acc, w[u], x[u]);
+      });
+      q += kSeqBatch;
+      if (q < q1) {
+        seq_batch(p.op_slot, q, sl);
+        seq_batch(p.op_w, q, w);
+      }
+    }
+    const float kept = seq_store(pool + static_cast<int64_t>(orow) * ld, e, acc);
+    if (oslot >= 0) col[oslot * kSeqTile] = Cell::put(kept);  // the rows after this one read it here
+    q0 = q1;
+  }
+}
+
+// The int64 segment (a few hundred counters per model): one thread per column walks the rows in
+// order on global memory; the thread owns its column, so program order is the round's order.
+__global__ __launch_bounds__(kBlock) void k_round_seq_direct(int64_t* pool, int64_t ld, int64_t n,
+                                                             const int32_t* plan) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (e >= n) return;
+  const SeqPlanView p(plan);
+  auto load = [&](int q) -> float {
+    return Io<int64_t>::ld1(pool + static_cast<int64_t>(p.src_row[p.op_slot[q]]) * ld, e);
+  };
+  for (int r = 0; r < p.rows; ++r) {
+    const int q0 = p.row_ptr[r], q1 = p.row_ptr[r + 1];
+    float acc = first1t<int64_t, true>(p.op_w[q0], load(q0));
+    for (int q = q0 + 1; q < q1; ++q) acc = next1t<int64_t, true>(acc, p.op_w[q], load(q));
+    Io<int64_t>::st1(pool + static_cast<int64_t>(p.out_row[r]) * ld, e, acc);
+  }
+}
+
+template <typename T>
+int32_t launch_round_seq(T* pool, int64_t ld, int64_t n, const int32_t* plan, const tal_seq_plan_info& in,
+                         bool exact, hipStream_t s) {
+  if constexpr (kIsI64<T>) {
+    const int64_t blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "sequential round (int64): grid too large");
+    k_round_seq_direct<<<static_cast<unsigned>(blocks), kBlock, 0, s>>>(pool, ld, n, plan);
+    return check_launch("sequential round kernel (int64)");
+  } else {
+    const int64_t tiles = (n + kSeqTile - 1) / kSeqTile;
+    if (tiles > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "sequential round: grid too large");
+    const size_t lds = static_cast<size_t>(in.n_src) * kSeqTile * sizeof(typename SeqCell<T>::type);
+    auto k = exact ? k_round_seq<T, true> : k_round_seq<T, false>;
+    if (int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds)) return rc;
+    k<<<static_cast<unsigned>(tiles), kSeqTile, lds, s>>>(pool, ld, n, plan);
+    return check_launch("sequential round kernel");
+  }
+}
+
 template <int NT, bool EXACT>
 int32_t launch_round_stream_nt(const float* pin, int64_t ld_in, float* pout, int64_t ld_out, int64_t n4,
                                const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
@@ -4935,9 +5124,111 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
   });
 }
 
+// tal_agg_round_seq_<T>: every check before the launch; the plan's rows are known from info alone.
+template <typename T>
+int32_t agg_round_seq(const char* fn, T* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                      const tal_seq_plan_info* info, int32_t mode, void* stream) {
+  const std::string name(fn);
+  if (!pool) return fail(TAL_ERR_INVALID, name + ": null pool");
+  if (!plan_dev) return fail(TAL_ERR_INVALID, name + ": null plan_dev");
+  if (!info) return fail(TAL_ERR_INVALID, name + ": null info");
+  if (info->rows <= 0 || info->nnz < info->rows || info->n_src <= 0 || info->n_src > TAL_SEQ_MAX_SRC)
+    return fail(TAL_ERR_INVALID, name + ": info is not a sequential plan's (rows, nnz, 1 <= n_src <= " +
+                                     std::to_string(TAL_SEQ_MAX_SRC) + ")");
+  if (n < 0) return fail(TAL_ERR_INVALID, name + ": n < 0");
+  if (ld < n) return fail(TAL_ERR_INVALID, name + ": ld < n");
+  if (info->max_row >= pool_rows)
+    return fail(TAL_ERR_INVALID, name + ": plan row " + std::to_string(info->max_row) + " >= pool_rows");
+  if (n == 0) { g_err.clear(); return TAL_OK; }
+  return launch_round_seq<T>(pool, ld, n, plan_dev, *info, mode == TAL_MODE_EXACT, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t tal_seq_plan_words(int32_t rows, int64_t nnz) {
+  if (rows < 0 || nnz < 0) return 0;
+  // header, src_row (at most one per operand), row_ptr, op_slot, op_w, out_row, out_slot, padding
+  return kSeqHeader + nnz + (static_cast<int64_t>(rows) + 1) + 2 * nnz + 2 * static_cast<int64_t>(rows) + kSeqBatch;
+}
+
+int32_t tal_seq_plan_build(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
+                           const double* w_host, const int32_t* out_row_host, int32_t* plan_host,
+                           int64_t capacity_words, tal_seq_plan_info* info) {
+  const char* fn = "tal_seq_plan_build";
+  if (!info) return fail(TAL_ERR_INVALID, std::string(fn) + ": null info");
+  Csr c{rows, row_ptr_host, col_host, w_host, out_row_host};
+  if (int32_t rc = check_csr(fn, &c)) return rc;
+  const int32_t nnz = static_cast<int32_t>(c.nnz());
+  int32_t max_row = c.max_col, max_ops = 0;
+  std::vector<int32_t> outs(out_row_host, out_row_host + rows);
+  for (int r = 0; r < rows; ++r) {
+    if (out_row_host[r] < 0) return fail(TAL_ERR_INVALID, std::string(fn) + ": negative out_row");
+    max_row = std::max(max_row, out_row_host[r]);
+    max_ops = std::max(max_ops, c.ops(r));
+  }
+  std::sort(outs.begin(), outs.end());
+  if (std::adjacent_find(outs.begin(), outs.end()) != outs.end())
+    return fail(TAL_ERR_INVALID, std::string(fn) + ": an out_row is listed twice");
+  std::vector<int32_t> srcs(col_host, col_host + nnz);
+  std::sort(srcs.begin(), srcs.end());
+  srcs.erase(std::unique(srcs.begin(), srcs.end()), srcs.end());
+  const int32_t n_src = static_cast<int32_t>(srcs.size());
+  memset(info, 0, sizeof(*info));
+  info->rows = rows;
+  info->nnz = nnz;
+  info->n_src = n_src;
+  info->max_row = max_row;
+  info->max_ops = max_ops;
+  info->off_src_row = kSeqHeader;
+  info->off_row_ptr = info->off_src_row + n_src;
+  info->off_op_slot = info->off_row_ptr + rows + 1;
+  info->off_op_w = info->off_op_slot + nnz;
+  info->off_out_row = info->off_op_w + nnz;
+  info->off_out_slot = info->off_out_row + rows;
+  info->words = static_cast<int64_t>(info->off_out_slot) + rows + kSeqBatch;  // zero words: see seq_batch
+  if (n_src > TAL_SEQ_MAX_SRC)
+    return fail(TAL_ERR_CAPACITY, std::string(fn) + ": " + std::to_string(n_src) + " distinct sources, the kernel's tile holds " +
+                                      std::to_string(TAL_SEQ_MAX_SRC));
+  if (!plan_host || capacity_words < info->words)
+    return fail(TAL_ERR_CAPACITY, std::string(fn) + ": plan buffer too small (info->words)");
+  auto slot_of = [&](int32_t row) -> int32_t {
+    const auto it = std::lower_bound(srcs.begin(), srcs.end(), row);
+    return it != srcs.end() && *it == row ? static_cast<int32_t>(it - srcs.begin()) : -1;
+  };
+  int32_t* b = plan_host;
+  const int32_t header[kSeqHeader] = {rows, nnz, n_src, static_cast<int32_t>(info->words), max_row, max_ops, 0, 0};
+  memcpy(b, header, sizeof(header));
+  std::copy(srcs.begin(), srcs.end(), b + info->off_src_row);
+  std::copy(row_ptr_host, row_ptr_host + rows + 1, b + info->off_row_ptr);
+  for (int32_t k = 0; k < nnz; ++k) {
+    b[info->off_op_slot + k] = slot_of(col_host[k]);
+    b[info->off_op_w + k] = f32_bits(w_host[k]);
+  }
+  for (int r = 0; r < rows; ++r) {
+    b[info->off_out_row + r] = out_row_host[r];
+    b[info->off_out_slot + r] = slot_of(out_row_host[r]);
+  }
+  std::fill(b + info->off_out_slot + rows, b + info->words, 0);
+  g_err.clear();
+  return TAL_OK;
+}
+
+int32_t tal_agg_round_seq_f32(float* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                              const tal_seq_plan_info* info, int32_t mode, void* stream) {
+  return agg_round_seq<float>("tal_agg_round_seq_f32", pool, ld, pool_rows, n, plan_dev, info, mode, stream);
+}
+
+int32_t tal_agg_round_seq_bf16(uint16_t* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                               const tal_seq_plan_info* info, int32_t mode, void* stream) {
+  return agg_round_seq<uint16_t>("tal_agg_round_seq_bf16", pool, ld, pool_rows, n, plan_dev, info, mode, stream);
+}
+
+int32_t tal_agg_round_seq_i64(int64_t* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                              const tal_seq_plan_info* info, void* stream) {
+  return agg_round_seq<int64_t>("tal_agg_round_seq_i64", pool, ld, pool_rows, n, plan_dev, info, TAL_MODE_EXACT, stream);
+}
 
 int32_t tal_round_plan_build(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
                              const double* w_host, const int32_t* out_row_host, int32_t c4,

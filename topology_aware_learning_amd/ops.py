@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import RoundPlanInfo, check
+from ._lib import RoundPlanInfo, SeqPlanInfo, check
 
 MODE_EXACT = _lib.TAL_MODE_EXACT
 MODE_FMA = _lib.TAL_MODE_FMA
@@ -1062,6 +1062,113 @@ def _round(pool_in, pool_out, plan, n, dtype, mode, stream):
     args.append(_stream(pool_in.device, stream))
     check(fn(*args))
     return pool_out
+
+
+# ------------------------------------------------------------------------------------------
+# K3q: a sequential round in one launch
+# ------------------------------------------------------------------------------------------
+SEQ_MAX_SRC = 256  # TAL_SEQ_MAX_SRC: distinct source rows of one sequential plan
+# (bf16, mode): whether RoundExecutor.run(sequential=True) runs the round as one K3q launch per
+# segment instead of one K1 call per client: True only where the kernel's median beat the K1
+# loop's by more than tune_plan's 1 % margin on every round of tools/seq_round_rate.py
+# (profiles/r18; medians of 20 interleaved runs, ms, kernel / K1 loop on ring 32 at ResNet-18
+# width, random-regular(8, 64) and barbell(60, 8) at ResNet-50 width, BA(33, 2) at CIFAR-CNN width):
+#   fp32 EXACT  0.842 / 1.037   5.672 / 11.136   136.09 / 119.05   0.505 / 0.898
+#   fp32 FMA    0.793 / 1.032   5.365 / 11.130   128.39 / 119.00   0.476 / 0.898
+#   bf16 EXACT  0.702 / 0.732   3.810 /  5.989    67.27 /  64.40   0.410 / 0.705
+#   bf16 FMA    0.682 / 0.722   3.488 /  5.844    61.38 /  62.77   0.398 / 0.709
+# - bf16 FMA alone, by 1.02x (the barbell) to 1.78x.  The others lose the barbell round (its
+# 61-operand rows are one dependent chain per lane with few waves resident on a CU) while winning
+# the sparse rounds by 1.04x to 2.07x, the forms agreeing bit for bit; DESIGN §4 "K3q"
+SEQ_DEFAULT = {(False, MODE_EXACT): False, (False, MODE_FMA): False,
+               (True, MODE_EXACT): False, (True, MODE_FMA): True}
+
+
+@dataclass
+class SeqPlan:
+    """A sequential round (tal_agg.h K3q): rows in the caller's order, each reading the pool as
+    the rows before it left it."""
+    info: SeqPlanInfo
+    host: np.ndarray           # int32 blob
+    device: Optional[torch.Tensor] = None
+    rows: int = 0
+    nnz: int = 0
+    spec: Optional[dict] = None
+
+    def to(self, device) -> "SeqPlan":
+        self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
+        return self
+
+    def staged_rows(self) -> int:
+        """Source rows read from HBM per column tile."""
+        return int(self.info.n_src)
+
+
+def build_seq_plan(row_ptr, col, w, out_row) -> SeqPlan:
+    """The plan of a sequential round given as CSR (row r: operands col[row_ptr[r]:row_ptr[r+1]]
+    with float64 weights w, written to pool row out_row[r]; rows run in this order).  Raises
+    TalError with TAL_ERR_CAPACITY for more than SEQ_MAX_SRC distinct source rows."""
+    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
+    rows = len(out_row)
+    L = _lib.load()
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    size = int(L.tal_seq_plan_words(rows, len(col)))
+    info = SeqPlanInfo()
+    blob = np.zeros(size, dtype=np.int32)
+    check(L.tal_seq_plan_build(rows, row_ptr.ctypes.data_as(P32), col.ctypes.data_as(P32),
+                               w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out_row.ctypes.data_as(P32),
+                               blob.ctypes.data_as(P32), size, ctypes.byref(info)))
+    return SeqPlan(info=info, host=blob[: info.words].copy(), rows=rows, nnz=len(col), spec={"seq": 1})
+
+
+_ROUND_SEQ_FN = {torch.float32: "tal_agg_round_seq_f32", torch.int64: "tal_agg_round_seq_i64",
+                 torch.bfloat16: "tal_agg_round_seq_bf16"}
+
+
+def _round_seq(pool, plan: SeqPlan, n, dtype, mode, stream):
+    if not isinstance(plan, SeqPlan):
+        raise TypeError("a sequential round takes a SeqPlan (build_seq_plan)")
+    if not isinstance(pool, torch.Tensor):
+        raise TypeError("pool must be a torch.Tensor")
+    if pool.device.type != "cuda":
+        raise ValueError(f"pool must be a GPU tensor (got {pool.device}); the aggregation has no CPU path")
+    if pool.dtype != dtype:
+        raise ValueError(f"pool must be {dtype} (got {pool.dtype})")
+    if pool.dim() != 2 or pool.stride(1) != 1:
+        raise ValueError("pool must be 2-D [models, ld] with unit column stride")
+    n = pool.shape[1] if n is None else int(n)
+    if not 0 <= n <= pool.shape[1]:
+        raise ValueError(f"n = {n} outside the pool's {pool.shape[1]} columns")
+    if plan.info.max_row >= pool.shape[0]:
+        raise ValueError("plan reads or writes a pool row beyond the pool")
+    if plan.device is None or plan.device.device != pool.device:
+        plan.to(pool.device)
+    L = _lib.load()
+    args = [ctypes.c_void_p(pool.data_ptr()), pool.stride(0), pool.shape[0], n,
+            ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)]
+    if dtype != torch.int64:
+        args.append(int(mode))
+    args.append(_stream(pool.device, stream))
+    check(getattr(L, _ROUND_SEQ_FN[dtype])(*args))
+    return pool
+
+
+def round_seq_f32(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, mode: int = MODE_EXACT,
+                  stream=None) -> torch.Tensor:
+    """K3q on a [models, ld] fp32 pool, in place: the plan's rows in order, each the chain of
+    agg_f32 on the pool as the rows before it left it (any row stride, element-aligned)."""
+    return _round_seq(pool, plan, n, torch.float32, mode, stream)
+
+
+def round_seq_bf16(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, mode: int = MODE_EXACT,
+                   stream=None) -> torch.Tensor:
+    """K3q on a bf16 pool (chains as agg_bf16 per mode; later rows read the stored bf16 value)."""
+    return _round_seq(pool, plan, n, torch.bfloat16, mode, stream)
+
+
+def round_seq_i64(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, stream=None) -> torch.Tensor:
+    """K3q on an int64 pool (chains as agg_i64; later rows read the truncated integer)."""
+    return _round_seq(pool, plan, n, torch.int64, MODE_EXACT, stream)
 
 
 # ------------------------------------------------------------------------------------------

@@ -11,7 +11,10 @@ model once per column tile instead of once per aggregation that uses it.
 Round semantics ("snapshot"): every aggregation of the round reads the models as they were
 before the round.  The reference's in-place writes from two threads make
 its own round order-dependent; ``sequential=True`` reproduces its single-thread order
-(client index order, each call seeing the previous calls' writes) as one K1 call per client.
+(client index order, each call seeing the previous calls' writes): one K3q launch per segment,
+in place, where ``ops.SEQ_DEFAULT`` has the kernel on and the round has at most
+``ops.SEQ_MAX_SRC`` distinct sources, else one K1 call per client (``sequential="calls"``
+always).
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .arena import ModelPool
 
 
@@ -70,6 +73,7 @@ class RoundExecutor:
         self.placement_trials = placement_trials
         self.placement: Optional[dict] = None
         self._plans: Dict[Tuple, ops.RoundPlan] = {}
+        self._seq_plans: Dict[Tuple, Optional[ops.SeqPlan]] = {}  # None: the round does not fit K3q
         if double_buffer is None:
             double_buffer = scratch is None and pool.device.type == "cuda" and pool.whole_storage()
         self.double_buffer = double_buffer
@@ -129,18 +133,50 @@ class RoundExecutor:
             self._plans[key] = p
         return p
 
+    def seq_plan(self, orders, weights, out_rows) -> Optional[ops.SeqPlan]:
+        """The K3q plan of these lists, built once; None for a round of more distinct sources
+        than the kernel's tile holds (TAL_ERR_CAPACITY)."""
+        key = (tuple(map(tuple, orders)), tuple(tuple(map(float, w)) for w in weights), tuple(out_rows))
+        if key not in self._seq_plans:
+            row_ptr, col, w = csr_from_lists(orders, weights)
+            try:
+                p = ops.build_seq_plan(row_ptr, col, w, np.asarray(out_rows, np.int32)).to(self.pool.device)
+            except _lib.TalError as exc:
+                if exc.code != _lib.TAL_ERR_CAPACITY:
+                    raise
+                p = None
+            if len(self._seq_plans) > 64:
+                self._seq_plans.clear()
+            self._seq_plans[key] = p
+        return self._seq_plans[key]
+
     def run(self, orders: Sequence[Sequence[int]], weights: Sequence[Sequence[float]],
-            out_rows: Optional[Sequence[int]] = None, sequential: bool = False,
+            out_rows: Optional[Sequence[int]] = None, sequential=False,
             plan: Optional[ops.RoundPlan] = None) -> None:
         """Aggregate pool rows: out_rows[r] <- sum_k weights[r][k] * pool[orders[r][k]].
         plan: what self.plan(orders, weights, out_rows) returned for these same lists (a caller
-        that repeats a round passes it back instead of having the lists hashed again)."""
+        that repeats a round passes it back instead of having the lists hashed again).
+        sequential: True - rows in order, each reading the rows before it as they left them, in
+        place (K3q where ops.SEQ_DEFAULT has it on for the pool's dtype and mode and the plan
+        fits, else the K1 loop); "calls" - the K1 loop, one call per row and segment."""
         if out_rows is None:
             out_rows = list(range(len(orders)))
         if len(orders) == 0:
             return
         lay = self.pool.layout
         if sequential:
+            sp = None
+            if sequential != "calls" and self.pool.device.type == "cuda" and \
+                    ops.SEQ_DEFAULT[(bool(lay.n_b16), self.mode)]:
+                sp = self.seq_plan(orders, weights, out_rows)
+            if sp is not None:
+                if lay.n_f32:
+                    ops.round_seq_f32(self.pool.f32, sp, n=lay.n_f32, mode=self.mode)
+                if lay.n_b16:
+                    ops.round_seq_bf16(self.pool.b16, sp, n=lay.n_b16, mode=self.mode)
+                if lay.n_i64:
+                    ops.round_seq_i64(self.pool.i64, sp, n=lay.n_i64)
+                return
             for r, o, w in zip(out_rows, orders, weights):
                 if lay.n_f32:
                     ops.agg_f32([self.pool.row_f32(j) for j in o], w, self.pool.row_f32(r), mode=self.mode)
