@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .arena import ModelPool, StateLayout, bound_row
+from .arena import SEG, ModelPool, StateLayout, bound_row
 
 _tls = threading.local()
 _layout_cache: dict = {}
@@ -81,12 +81,7 @@ def _mark_used(tag: str, device) -> None:
     _tls.events[tag] = ev
 
 
-_SEG_DTYPE = {"f32": torch.float32, "b16": torch.bfloat16, "i64": torch.int64}
 _D2H_CHUNK = 16 << 20  # bytes per write-back chunk
-
-
-def _seg_sizes(layout: StateLayout):
-    return {"f32": layout.n_f32, "b16": layout.n_b16, "i64": layout.n_i64}
 
 
 class _OperandCache:
@@ -237,7 +232,7 @@ def _bind_pinned(model: nn.Module, layout: StateLayout) -> Optional[Tuple[ModelP
         layout.check_compatible(sd, "model")
     except ValueError:
         return None
-    nbytes = 4 * layout.ld_f32 + 8 * layout.ld_i64 + 2 * layout.ld_b16
+    nbytes = layout.row_bytes
     if _PIN["used"] + nbytes > _pin_budget():
         return None
 
@@ -261,9 +256,9 @@ def _pinned_signature(model: nn.Module, pool: ModelPool) -> tuple:
     return (pool.f32.data_ptr(),) + tuple(table[attr]._version for table, attr in model._tal_slots)
 
 
-def _row_segments(pool: ModelPool, r: int, sizes) -> dict:
-    rows = {"f32": pool.row_f32, "b16": pool.row_b16, "i64": pool.row_i64}
-    return {g: rows[g](r) for g in sizes}
+def _empty_segments(sizes: dict, device=None) -> dict:
+    """{segment: uninitialised flat tensor of its dtype and size} on `device` (None: the CPU)."""
+    return {g: torch.empty(n, dtype=SEG[g].dtype, device=device) for g, n in sizes.items()}
 
 
 def _stage(models: Sequence[nn.Module], layout: StateLayout, device) -> List[dict]:
@@ -273,7 +268,7 @@ def _stage(models: Sequence[nn.Module], layout: StateLayout, device) -> List[dic
     buffer per segment, each operand's H2D copy issued as soon as that operand is packed so the
     copy overlaps packing the next one (the host-memory path of the reference's CPU models);
     with TAL_HOST_CACHE_GB set, an unchanged host model copied before is not copied again."""
-    sizes = {g: n for g, n in _seg_sizes(layout).items() if n}
+    sizes = layout.sizes
     cache = _host_cache()
     out: List[dict] = [None] * len(models)  # type: ignore[list-item]
     host_rows, sds, sigs = [], [], []
@@ -285,10 +280,9 @@ def _stage(models: Sequence[nn.Module], layout: StateLayout, device) -> List[dic
             if hit is not None:
                 out[j] = hit
                 continue
-            src = _row_segments(hb[0], hb[1], sizes)
-            out[j] = {g: torch.empty(n, dtype=_SEG_DTYPE[g], device=device) for g, n in sizes.items()}
+            out[j] = _empty_segments(sizes, device)
             for g in sizes:
-                out[j][g].copy_(src[g], non_blocking=True)
+                out[j][g].copy_(hb[0].row(g, hb[1]), non_blocking=True)
             if cache is not None:
                 cache.put(m, sig, device, out[j])
             sds.append(None)
@@ -311,10 +305,9 @@ def _stage(models: Sequence[nn.Module], layout: StateLayout, device) -> List[dic
     if host_rows:
         h = len(host_rows)
         for j in host_rows:
-            out[j] = {g: torch.empty(n, dtype=_SEG_DTYPE[g], device=device) for g, n in sizes.items()}
+            out[j] = _empty_segments(sizes, device)
         for g, n in sizes.items():
-            esz = torch.empty((), dtype=_SEG_DTYPE[g]).element_size()
-            hb = _pinned(esz * h * n, "in_" + g).view(_SEG_DTYPE[g]).view(h, n)
+            hb = _pinned(SEG[g].esize * h * n, "in_" + g).view(SEG[g].dtype).view(h, n)
             for q, j in enumerate(host_rows):
                 torch.cat([t.detach().to("cpu") for t in layout.flatten_cat(sds[j], g)], out=hb[q])
                 out[j][g].copy_(hb[q], non_blocking=True)  # in flight while the next one packs
@@ -341,34 +334,25 @@ def _pipe_streams(device: torch.device):
     return st
 
 
-def _k1(g: str, xs, w, out, mode, stream) -> None:
-    if g == "i64":
-        ops.agg_i64(xs, w, out, stream=stream)
-    elif g == "b16":
-        ops.agg_bf16(xs, w, out, mode=mode, stream=stream)
-    else:
-        ops.agg_f32(xs, w, out, mode=mode, stream=stream)
-
-
 def _pipelined_host_call(hbs, target_hb, layout: StateLayout, w: List[float], mode: int, device) -> None:
     """target's row <- sum_i w_i * row of hbs[i], every model a pinned host row (the reference's
     CPU models after their first call): per segment, column chunks flow H2D -> K1 -> D2H on three
     streams.  K1 on a chunk is the same per-element arithmetic as on the whole segment."""
-    sizes = {g: n for g, n in _seg_sizes(layout).items() if n}
+    sizes = layout.sizes
     h2d, comp, d2h = _pipe_streams(device)
     start = torch.cuda.Event()
     start.record(torch.cuda.current_stream(device))
     for st in (h2d, comp, d2h):
         st.wait_event(start)
     m = len(hbs)
-    src = [_row_segments(hb[0], hb[1], sizes) for hb in hbs]
-    dst = _row_segments(target_hb[0], target_hb[1], sizes)
+    src = [{g: hb[0].row(g, hb[1]) for g in sizes} for hb in hbs]
+    dst = {g: target_hb[0].row(g, target_hb[1]) for g in sizes}
     keep = []
     try:
         for g, n in sizes.items():
             ld = (n + 63) // 64 * 64  # 256-B aligned operand rows: chunks keep K1's vector path
-            dev = torch.empty((m, ld), dtype=_SEG_DTYPE[g], device=device)
-            out = torch.empty(ld, dtype=_SEG_DTYPE[g], device=device)
+            dev = torch.empty((m, ld), dtype=SEG[g].dtype, device=device)
+            out = torch.empty(ld, dtype=SEG[g].dtype, device=device)
             keep += [dev, out]
             step = n if g == "i64" else _PIPE_CHUNK
             for a in range(0, n, step):
@@ -379,7 +363,7 @@ def _pipelined_host_call(hbs, target_hb, layout: StateLayout, w: List[float], mo
                 landed = torch.cuda.Event()
                 landed.record(h2d)
                 comp.wait_event(landed)
-                _k1(g, [dev[j, a:b] for j in range(m)], w, out[a:b], mode, comp)
+                ops.agg([dev[j, a:b] for j in range(m)], w, out[a:b], mode, comp, seg=g)
                 done = torch.cuda.Event()
                 done.record(comp)
                 d2h.wait_event(done)
@@ -392,11 +376,6 @@ def _pipelined_host_call(hbs, target_hb, layout: StateLayout, w: List[float], mo
         for st in (h2d, comp, d2h):
             st.synchronize()
         del keep
-
-
-_AGG = {"f32": lambda xs, w, out, mode: ops.agg_f32(xs, w, out, mode=mode),
-        "b16": lambda xs, w, out, mode: ops.agg_bf16(xs, w, out, mode=mode),
-        "i64": lambda xs, w, out, mode: ops.agg_i64(xs, w, out)}
 
 
 def aggregate_models(operands: Sequence[nn.Module], weights: Sequence[float], target: nn.Module,
@@ -431,7 +410,7 @@ def aggregate_models(operands: Sequence[nn.Module], weights: Sequence[float], ta
     if device is None:
         device = _device_for(list(operands) + [target])
     host_target = _host_binding(target, layout) if tb is None or tb[0].device.type == "cpu" else None
-    sizes = {g: n for g, n in _seg_sizes(layout).items() if n}
+    sizes = layout.sizes
     if host_target is not None and _host_cache() is None and _pipe_enabled():
         hbs = [_host_binding(m, layout) for m in operands]
         if all(h is not None for h in hbs):  # every model in a pinned host row
@@ -443,10 +422,8 @@ def aggregate_models(operands: Sequence[nn.Module], weights: Sequence[float], ta
     for j, m in enumerate(operands):
         b = bounds[j]
         if b is not None and b[0].device == device and b[0].layout == layout:  # device pool row
-            pool, r = b
-            rows = {"f32": pool.row_f32, "b16": pool.row_b16, "i64": pool.row_i64}
             for g in sizes:
-                ptrs[g][j] = rows[g](r)
+                ptrs[g][j] = b[0].row(g, b[1])
         else:
             unbound.append(j)
     if unbound:
@@ -456,25 +433,23 @@ def aggregate_models(operands: Sequence[nn.Module], weights: Sequence[float], ta
                 ptrs[g][j] = staged[k][g]
 
     if tb is not None and tb[0].device == device and tb[0].layout == layout:
-        rows = {"f32": tb[0].row_f32, "b16": tb[0].row_b16, "i64": tb[0].row_i64}
-        outs = {g: rows[g](tb[1]) for g in sizes}
+        outs = {g: tb[0].row(g, tb[1]) for g in sizes}
         in_place = True
     else:
-        outs = {g: torch.empty(n, dtype=_SEG_DTYPE[g], device=device) for g, n in sizes.items()}
+        outs = _empty_segments(sizes, device)
         in_place = False
 
     w = [float(x) for x in weights]
-    if set(sizes) == {"f32", "i64"}:  # a ResNet-like model: both segments in one launch
+    if layout.single_launch:
         ops.agg_model_f32(ptrs["f32"], ptrs["i64"], w, outs["f32"], outs["i64"], mode)
     else:
         for g in sizes:
-            _AGG[g](ptrs[g], w, outs[g], mode)
+            ops.agg(ptrs[g], w, outs[g], mode, seg=g)
 
     synced = False
     if host_target is not None:  # pinned row: one D2H per segment straight into it
-        dst = _row_segments(host_target[0], host_target[1], sizes)
         for g in sizes:
-            dst[g].copy_(outs[g], non_blocking=True)
+            host_target[0].row(g, host_target[1]).copy_(outs[g], non_blocking=True)
         torch.cuda.current_stream(device).synchronize()
         synced = True
         cache = _host_cache()
@@ -497,11 +472,10 @@ def aggregate_models(operands: Sequence[nn.Module], weights: Sequence[float], ta
 def _write_back(target: nn.Module, layout: StateLayout, outs: dict) -> None:
     """load_state_dict(avg) equivalent: copy_ into the target's existing tensors."""
     sd = target.state_dict()
-    empty = {g: torch.empty(0, dtype=_SEG_DTYPE[g]) for g in _SEG_DTYPE}
+    empty = _empty_segments(dict.fromkeys(SEG, 0))
     on_gpu = [t.device.type == "cuda" for t in sd.values()]
     if all(on_gpu):
-        segs = {g: outs.get(g, empty[g]) for g in _SEG_DTYPE}
-        views = layout.views(segs["f32"], segs["i64"], segs["b16"])
+        views = layout.views(**{**empty, **outs})
         with torch.no_grad():
             for name, t in sd.items():
                 t.copy_(views[name])
@@ -525,7 +499,7 @@ def _write_back(target: nn.Module, layout: StateLayout, outs: dict) -> None:
                 ev.record(stream)
                 pending.append((ev, names))
                 names, start = [], end
-    views = layout.views(host["f32"], host["i64"], host["b16"])
+    views = layout.views(**host)
     with torch.no_grad():
         for ev, names in pending:
             ev.synchronize()
@@ -542,7 +516,7 @@ def _aggregate_host(operands: Sequence[nn.Module], weights: Sequence[float], tar
     reduction (ops.host_agg), and the result copied into the target's own tensors as
     load_state_dict(avg) would (decentralized_client.py:399-413 on CPU models)."""
     layout = layout_of_module(target)
-    sizes = {g: n for g, n in _seg_sizes(layout).items() if n}
+    sizes = layout.sizes
     flats = []
     for j, m in enumerate(operands):
         sd = m.state_dict()
@@ -551,11 +525,10 @@ def _aggregate_host(operands: Sequence[nn.Module], weights: Sequence[float], tar
             raise RuntimeError("no GPU is visible, but an operand has tensors off the CPU")
         flats.append({g: torch.cat([t.detach() for t in layout.flatten_cat(sd, g)]) for g in sizes})
     w = [float(x) for x in weights]
-    outs = {g: torch.empty(n, dtype=_SEG_DTYPE[g]) for g, n in sizes.items()}
+    outs = _empty_segments(sizes)
     for g in sizes:
         ops.host_agg([f[g] for f in flats], w, outs[g], mode)
-    empty = {g: torch.empty(0, dtype=_SEG_DTYPE[g]) for g in _SEG_DTYPE}
-    views = layout.views(outs.get("f32", empty["f32"]), outs.get("i64", empty["i64"]), outs.get("b16", empty["b16"]))
+    views = layout.views(**{**_empty_segments(dict.fromkeys(SEG, 0)), **outs})
     sd = target.state_dict()
     with torch.no_grad():
         for name, t in sd.items():

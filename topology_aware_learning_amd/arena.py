@@ -13,12 +13,40 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass
+from types import MappingProxyType
 from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
-SUPPORTED = {torch.float32: "f32", torch.int64: "i64", torch.bfloat16: "b16"}
+
+@dataclass(frozen=True)
+class Segment:
+    """One pool segment and everything that follows from its element type."""
+    name: str             # "f32" | "b16" | "i64": the ModelPool attribute, the key of every per-segment dict
+    dtype: torch.dtype
+    bits: torch.dtype     # the integer dtype of the same width (bitwise comparison, hashing)
+    esize: int            # bytes per element
+    suffix: str           # of the C-ABI entries of this element type (tal_agg_f32, tal_agg_round_bf16, ...)
+    takes_mode: bool      # whether those entries take a `mode` (the int64 ones do not)
+    synth: str            # synth's dtype name
+
+
+SEGMENTS = (Segment("f32", torch.float32, torch.int32, 4, "_f32", True, "float32"),
+            Segment("b16", torch.bfloat16, torch.int16, 2, "_bf16", True, "bfloat16"),
+            Segment("i64", torch.int64, torch.int64, 8, "_i64", False, "int64"))
+SEG = {s.name: s for s in SEGMENTS}
+_BY_DTYPE = {s.dtype: s for s in SEGMENTS}
+
+
+def segment_of(dtype: torch.dtype) -> Segment:
+    """The segment that holds entries of `dtype`; a dtype the kernels do not handle is a ValueError."""
+    try:
+        return _BY_DTYPE[dtype]
+    except KeyError:
+        raise ValueError(f"the aggregation kernels handle float32, bfloat16 and int64 (got {dtype})") from None
+
+
 ROW_ALIGN = 64  # elements: 256 B for fp32 rows, 128 B for bf16 rows
 
 
@@ -43,9 +71,13 @@ class StateLayout:
     def __init__(self, entries: Sequence[Entry]):
         self.entries: List[Entry] = list(entries)
         self.by_name: Dict[str, Entry] = {e.name: e for e in self.entries}
-        self.n_f32 = sum(e.numel for e in self.entries if e.seg == "f32" and e.alias_of is None)
-        self.n_i64 = sum(e.numel for e in self.entries if e.seg == "i64" and e.alias_of is None)
-        self.n_b16 = sum(e.numel for e in self.entries if e.seg == "b16" and e.alias_of is None)
+        count = {s.name: sum(e.numel for e in self.entries if e.seg == s.name and e.alias_of is None) for s in SEGMENTS}
+        self.n_f32, self.n_b16, self.n_i64 = count["f32"], count["b16"], count["i64"]
+        # the non-empty segments, elements per model (read-only: single_launch and the pools follow it)
+        self.sizes: Mapping[str, int] = MappingProxyType({g: n for g, n in count.items() if n})
+        # a ResNet-like model, fp32 entries and int64 counters and nothing else: K1 takes both
+        # segments in one launch (tal_agg_model_f32)
+        self.single_launch = set(self.sizes) == {"f32", "i64"}
         self.ld_f32 = max(_round_up(self.n_f32, ROW_ALIGN), ROW_ALIGN)
         self.ld_i64 = max(_round_up(self.n_i64, 8), 8)
         self.ld_b16 = max(_round_up(self.n_b16, ROW_ALIGN), ROW_ALIGN)
@@ -60,14 +92,14 @@ class StateLayout:
     @classmethod
     def from_state_dict(cls, sd: Mapping[str, torch.Tensor]) -> "StateLayout":
         entries: List[Entry] = []
-        off = {"f32": 0, "i64": 0, "b16": 0}
+        off = dict.fromkeys(SEG, 0)
         seen: Dict[Tuple[int, int, Tuple[int, ...]], str] = {}
         for name, t in sd.items():
-            if t.dtype not in SUPPORTED:
+            if t.dtype not in _BY_DTYPE:
                 raise NotImplementedError(
                     f"state_dict entry {name!r} has dtype {t.dtype}; the aggregation kernels handle "
                     "float32, bfloat16 and int64 entries")
-            seg = SUPPORTED[t.dtype]
+            seg = _BY_DTYPE[t.dtype].name
             key = (t.data_ptr(), t.storage_offset(), tuple(t.shape)) if t.numel() else None
             if key is not None and key in seen and t.is_contiguous():
                 entries.append(Entry(name, tuple(t.shape), t.dtype, seg, by_name_offset(entries, seen[key]),
@@ -81,12 +113,12 @@ class StateLayout:
 
     @classmethod
     def from_layout(cls, layout: Sequence[Tuple[str, Sequence[int], str]]) -> "StateLayout":
-        dt = {"float32": torch.float32, "int64": torch.int64, "bfloat16": torch.bfloat16}
+        dt = {s.synth: s.dtype for s in SEGMENTS}
         sd = OrderedDict((n, torch.empty(tuple(s), dtype=dt[d], device="meta")) for n, s, d in layout)
         entries: List[Entry] = []
-        off = {"f32": 0, "i64": 0, "b16": 0}
+        off = dict.fromkeys(SEG, 0)
         for name, t in sd.items():
-            seg = SUPPORTED[t.dtype]
+            seg = _BY_DTYPE[t.dtype].name
             n = 1
             for s in t.shape:
                 n *= int(s)
@@ -121,6 +153,11 @@ class StateLayout:
             if e.alias_of is not None:
                 continue
             segs[e.seg][e.offset: e.offset + e.numel].copy_(sd[e.name].reshape(-1), non_blocking=non_blocking)
+
+    @property
+    def row_bytes(self) -> int:
+        """Bytes of one pool row over the three segments, padding included."""
+        return sum(s.esize * getattr(self, "ld_" + s.name) for s in SEGMENTS)
 
     def flatten_cat(self, sd: Mapping[str, torch.Tensor], seg: str) -> List[torch.Tensor]:
         return [sd[e.name].reshape(-1) for e in self.entries if e.seg == seg and e.alias_of is None]
@@ -261,6 +298,16 @@ class ModelPool:
         self.i64 = i64 if i64 is not None else torch.zeros(rows, layout.ld_i64, dtype=torch.int64, device=self.device)
         self.b16 = b16 if b16 is not None else torch.zeros(rows, layout.ld_b16, dtype=torch.bfloat16, device=self.device)
         self._bound: Dict[int, int] = {}  # id(module) -> row
+        # fixed for the pool's life: swap_with exchanges the tensors' storages, not the tensors
+        self._segments = tuple((g, getattr(self, g), n) for g, n in layout.sizes.items())
+
+    def seg(self, name: str) -> torch.Tensor:
+        """The pool tensor [rows, ld] of segment `name`."""
+        return getattr(self, name)
+
+    def row(self, name: str, r: int) -> torch.Tensor:
+        """Row r's elements of segment `name` (without the row padding)."""
+        return getattr(self, name)[r, : getattr(self.layout, "n_" + name)]
 
     def row_f32(self, r: int) -> torch.Tensor:
         return self.f32[r, : self.layout.n_f32]
@@ -280,9 +327,7 @@ class ModelPool:
 
     def segments(self):
         """(name, pool tensor, elements per row) of the layout's non-empty segments."""
-        lay = self.layout
-        return [(k, t, n) for k, t, n in (("f32", self.f32, lay.n_f32), ("b16", self.b16, lay.n_b16),
-                                          ("i64", self.i64, lay.n_i64)) if n]
+        return self._segments
 
     def load_row(self, r: int, sd: Mapping[str, torch.Tensor]) -> None:
         self.layout.check_compatible(sd)
@@ -342,13 +387,13 @@ class ModelPool:
             raise ValueError("swap_with: pools differ in layout, rows or device")
         if not (self.whole_storage() and other.whole_storage()):
             raise ValueError("swap_with: a pool segment that is not a whole storage")
-        for k in ("f32", "b16", "i64"):
+        for k in SEG:
             swap_storage(getattr(self, k), getattr(other, k))
 
     def whole_storage(self) -> bool:
         """Every segment tensor is its storage, whole (what swap_with exchanges)."""
         return all(not t.storage_offset() and t.untyped_storage().nbytes() == t.numel() * t.element_size()
-                   for t in (self.f32, self.b16, self.i64))
+                   for t in map(self.seg, SEG))
 
     def row_of(self, module: nn.Module) -> Optional[int]:
         """Row the module is bound to, if its state still lives there: O(1) while no re-pointing
@@ -378,7 +423,7 @@ class ModelPool:
                 mod = mods[path]
                 table = mod._parameters if attr in mod._parameters else mod._buffers
                 fresh.append((table, attr))
-            base = {k: getattr(self, k).data_ptr() for k in ("f32", "b16", "i64")}
+            base = {k: getattr(self, k).data_ptr() for k in SEG}
             offs = [table[attr].data_ptr() - base[k] for (table, attr), k in zip(fresh, module._tal_segs)]
         except (KeyError, AttributeError):  # an entry removed or set to None
             return None

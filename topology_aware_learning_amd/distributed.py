@@ -24,8 +24,8 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .arena import ModelPool, StateLayout
-from .round import csr_from_lists
+from .arena import SEG, ModelPool, StateLayout
+from .round import csr_from_lists, tune_segment  # noqa: F401  (tune_segment: re-exported)
 
 
 def partition_contiguous(n: int, world: int) -> np.ndarray:
@@ -142,38 +142,19 @@ def post_exchange(spec: ShardSpec, tensors: Sequence[torch.Tensor], group=None,
     return dist.batch_isend_irecv(p2p)
 
 
-_ESIZE = {"f32": 4, "b16": 2, "i64": 8}
-
-
 def float_segments(layout: StateLayout):
     """(name, elements) of the layout's non-empty floating-point segments."""
-    return [(g, n) for g, n in (("f32", layout.n_f32), ("b16", layout.n_b16)) if n]
-
-
-def tune_segment(layout: StateLayout) -> str:
-    """The segment a round plan is tuned on: bf16 when there is one (its plan forms - sparse,
-    narrow, clique - also run fp32 and int64), else fp32."""
-    return "b16" if layout.n_b16 else "f32"
+    return [(g, n) for g, n in layout.sizes.items() if g != "i64"]
 
 
 def run_round_segments(layout: StateLayout, seg_in: dict, seg_out: dict, plan, mode: int,
                        n_of: Optional[dict] = None) -> None:
     """The K3 round of `plan` on every non-empty segment (seg_*: name -> [rows, ld] tensor;
     n_of: name -> columns, default the layout's elements per model)."""
-    for g, n in (("f32", layout.n_f32), ("b16", layout.n_b16), ("i64", layout.n_i64)):
+    for g, n in layout.sizes.items():
         n = n if n_of is None else n_of.get(g, 0)
-        if not n:
-            continue
-        if g == "f32":
-            ops.round_f32(seg_in[g], seg_out[g], plan, n=n, mode=mode)
-        elif g == "b16":
-            ops.round_bf16(seg_in[g], seg_out[g], plan, n=n, mode=mode)
-        else:
-            ops.round_i64(seg_in[g], seg_out[g], plan, n=n)
-
-
-def _pool_segs(pool: ModelPool) -> dict:
-    return {"f32": pool.f32, "b16": pool.b16, "i64": pool.i64}
+        if n:
+            ops.round_pool(seg_in[g], seg_out[g], plan, n=n, mode=mode, seg=g)
 
 
 def spot_check_row(layout: StateLayout, operands: dict, weights, got: dict, mode: int, n_of=None) -> bool:
@@ -182,11 +163,9 @@ def spot_check_row(layout: StateLayout, operands: dict, weights, got: dict, mode
         n = n if n_of is None else n_of.get(g, 0)
         if not n:
             continue
-        dt = torch.float32 if g == "f32" else torch.bfloat16
-        chk = torch.empty(n, dtype=dt, device=got[g].device)
-        (ops.agg_f32 if g == "f32" else ops.agg_bf16)([x[:n] for x in operands[g]], weights, chk, mode=mode)
-        iv = torch.int32 if g == "f32" else torch.int16
-        if not torch.equal(chk.view(iv), got[g][:n].contiguous().view(iv)):
+        chk = torch.empty(n, dtype=SEG[g].dtype, device=got[g].device)
+        ops.agg([x[:n] for x in operands[g]], weights, chk, mode=mode, seg=g)
+        if not torch.equal(chk.view(SEG[g].bits), got[g][:n].contiguous().view(SEG[g].bits)):
             return False
     return True
 
@@ -310,7 +289,7 @@ class ShardedRound:
                                             [self.spec.weights[k] for k in idx])
                 out = np.asarray(idx, np.int32)
                 self.plans[name] = (
-                    ops.tune_plan(rp, col, w, out, _pool_segs(self.pool_a)[tg], _pool_segs(self.pool_b)[tg],
+                    ops.tune_plan(rp, col, w, out, self.pool_a.seg(tg), self.pool_b.seg(tg),
                                   n=getattr(layout, "n_" + tg), mode=mode)
                     if tune else ops.default_plan(rp, col, w, out, bf16=bool(layout.n_b16), mode=mode).to(self.device))
         if exchange is None and dist.is_available() and dist.is_initialized():
@@ -326,7 +305,8 @@ class ShardedRound:
         plan = self.plans.get(name)
         if plan is None:
             return
-        run_round_segments(self.layout, _pool_segs(a), _pool_segs(b), plan, self.mode)
+        run_round_segments(self.layout, {g: t for g, t, _ in a.segments()}, {g: t for g, t, _ in b.segments()},
+                           plan, self.mode)
 
     def step(self, timed: bool = False) -> None:
         """One round: halo exchange overlapped with the interior rows, then the boundary rows.
@@ -367,18 +347,17 @@ class ShardedRound:
     @property
     def kernel_bytes(self) -> int:
         """Algorithmic HBM bytes of one round's local kernels (staged sources + written rows)."""
-        return sum(_ESIZE[g] * n for g, n in float_segments(self.layout)) * (self.staged_sources + self.local_rows)
+        return sum(SEG[g].esize * n for g, n in float_segments(self.layout)) * (self.staged_sources + self.local_rows)
 
     @property
     def link_bytes(self) -> int:
         """Bytes this rank receives over the links per round."""
-        lay = self.layout
-        return self.halo_rows_in * (4 * lay.n_f32 + 2 * lay.n_b16 + 8 * lay.n_i64)
+        return self.halo_rows_in * sum(SEG[g].esize * n for g, n in self.layout.sizes.items())
 
     def spot_check(self) -> bool:
         """After a step: one (boundary if any) row == K1 on its operands as they were received
         (bitwise; the operands are the previous buffer, now pool_b)."""
         k = (self.spec.boundary or self.spec.interior)[0]
-        a, b = _pool_segs(self.pool_a), _pool_segs(self.pool_b)
-        ops_ = {g: [b[g][j] for j in self.spec.orders_local[k]] for g in ("f32", "b16")}
-        return spot_check_row(self.layout, ops_, self.spec.weights[k], {g: a[g][k] for g in a}, self.mode)
+        a, b = self.pool_a, self.pool_b
+        ops_ = {g: [b.seg(g)[j] for j in self.spec.orders_local[k]] for g, _ in float_segments(self.layout)}
+        return spot_check_row(self.layout, ops_, self.spec.weights[k], {g: a.seg(g)[k] for g in ops_}, self.mode)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
+from functools import cached_property
 from typing import Optional, Sequence
 
 import numpy as np
@@ -15,9 +16,11 @@ import torch
 
 from . import _lib
 from ._lib import RoundPlanInfo, SeqPlanInfo, check
+from .arena import SEG, SEGMENTS, Segment, segment_of
 
 MODE_EXACT = _lib.TAL_MODE_EXACT
 MODE_FMA = _lib.TAL_MODE_FMA
+_F32, _B16, _I64 = SEGMENTS
 
 
 def _stream(device: torch.device, stream: Optional[torch.cuda.Stream] = None) -> ctypes.c_void_p:
@@ -25,15 +28,24 @@ def _stream(device: torch.device, stream: Optional[torch.cuda.Stream] = None) ->
     return ctypes.c_void_p(s.cuda_stream)
 
 
-def _require_gpu(t: torch.Tensor, name: str, dtype: torch.dtype) -> None:
+def _require_gpu(t: torch.Tensor, name: str, dtype: torch.dtype, contiguous: bool = True) -> None:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if t.device.type != "cuda":
         raise ValueError(f"{name} must be a GPU tensor (got {t.device}); the aggregation has no CPU path")
     if t.dtype != dtype:
         raise ValueError(f"{name} must be {dtype} (got {t.dtype})")
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
+
+
+def _call(family: str, seg: Segment, head: Sequence, mode: int, *tail) -> None:
+    """One checked call of the C-ABI entry `family` + the element type's suffix (tal_agg_f32,
+    tal_agg_round_seq_i64, ...): `head`, then `mode` where the entry takes one (the int64 entries
+    do not), then `tail`.  The entry is looked up by name at every call."""
+    rc = getattr(_lib.load(), family + seg.suffix)(*head, *(int(mode),) * seg.takes_mode, *tail)
+    if rc != _lib.TAL_OK:
+        check(rc)
 
 
 def _ptrs_and_weights(xs, weights, n, dtype, out):
@@ -41,36 +53,64 @@ def _ptrs_and_weights(xs, weights, n, dtype, out):
         raise ValueError("at least one operand is required")
     if len(weights) != len(xs):
         raise ValueError(f"{len(xs)} operands but {len(weights)} weights")
+    dev = out.device  # (a GPU: out is checked first)
     for i, x in enumerate(xs):
-        _require_gpu(x, f"operand {i}", dtype)
+        if isinstance(x, torch.Tensor) and x.device == dev and x.dtype == dtype and x.is_contiguous() and x.numel() == n:
+            continue
+        _require_gpu(x, f"operand {i}", dtype)  # which rule it breaks, in the order of the checks
         if x.numel() != n:
             raise ValueError(f"operand {i} has {x.numel()} elements, expected {n}")
-        if x.device != out.device:
-            raise ValueError(f"operand {i} is on {x.device}, out on {out.device}")
+        raise ValueError(f"operand {i} is on {x.device}, out on {out.device}")
     return _lib.ptr_array([x.data_ptr() for x in xs]), _lib.double_array(weights)
+
+
+def _segment(t, name: str) -> Segment:
+    """The segment of tensor t's dtype, for a dispatcher (agg, round_pool, round_seq) whose caller
+    names none."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    return segment_of(t.dtype)
+
+
+# agg, round_pool and round_seq call the per-dtype function by its name in this module (agg_f32,
+# round_bf16, round_seq_i64, ...), looked up at the call: a name that was replaced (the CPU tests
+# put the oracle there, the driver test a counter) is honoured by every caller that dispatches on
+# dtype.  `mode` goes only to the functions that take one: (mode,) * False is ().
+def agg(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Tensor, mode: int = MODE_EXACT,
+        stream=None, seg: Optional[str] = None) -> torch.Tensor:
+    """K1 on float32, bfloat16 or int64 buffers: agg_f32, agg_bf16 or agg_i64 (which has no modes:
+    `mode` is ignored there) by out's dtype, or for the segment `seg` ("f32", "b16", "i64") the
+    caller keeps the buffers under - buffers of another dtype are then refused."""
+    s = SEG[seg] if seg is not None else _segment(out, "out")
+    return globals()["agg" + s.suffix](xs, weights, out, *(mode,) * s.takes_mode, stream=stream)
+
+
+def _agg(seg: Segment, xs, weights, out, mode, stream) -> torch.Tensor:
+    _require_gpu(out, "out", seg.dtype)
+    n = out.numel()
+    P, W = _ptrs_and_weights(xs, weights, n, seg.dtype, out)
+    _call("tal_agg", seg, (P, W, len(xs), ctypes.c_void_p(out.data_ptr()), n), mode, _stream(out.device, stream))
+    return out
 
 
 def agg_f32(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Tensor,
             mode: int = MODE_EXACT, stream=None) -> torch.Tensor:
     """K1: out = sum_i fp32(w_i) * xs[i] (reference order; decentralized_client.py:399-411)."""
-    _require_gpu(out, "out", torch.float32)
-    n = out.numel()
-    P, W = _ptrs_and_weights(xs, weights, n, torch.float32, out)
-    L = _lib.load()
-    check(L.tal_agg_f32(P, W, len(xs), ctypes.c_void_p(out.data_ptr()), n, int(mode),
-                        _stream(out.device, stream)))
-    return out
+    return _agg(_F32, xs, weights, out, mode, stream)
 
 
 def agg_i64(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Tensor,
             stream=None) -> torch.Tensor:
     """K1 on int64 buffers: fp32 accumulate, truncation (decentralized_client.py:407-413)."""
-    _require_gpu(out, "out", torch.int64)
-    n = out.numel()
-    P, W = _ptrs_and_weights(xs, weights, n, torch.int64, out)
-    L = _lib.load()
-    check(L.tal_agg_i64(P, W, len(xs), ctypes.c_void_p(out.data_ptr()), n, _stream(out.device, stream)))
-    return out
+    return _agg(_I64, xs, weights, out, MODE_EXACT, stream)
+
+
+def agg_bf16(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Tensor,
+             mode: int = MODE_EXACT, stream=None) -> torch.Tensor:
+    """K1 on bf16 buffers.  MODE_EXACT: the reference's torch ops on bf16 tensors (every product
+    and partial sum rounded to bf16; decentralized_client.py:407-411); MODE_FMA: fp32 fused
+    accumulation rounded once."""
+    return _agg(_B16, xs, weights, out, mode, stream)
 
 
 def agg_model_f32(xs: Sequence[torch.Tensor], xis: Sequence[torch.Tensor], weights: Sequence[float],
@@ -112,53 +152,28 @@ def agg_pool_rows(pool, rows: Sequence[int], weights: Sequence[float], out_row: 
             raise ValueError(f"pool segment {seg} must be [rows, ld] with unit column stride")
     W = _lib.double_array(weights)
     s = _stream(pool.device, stream)
-    L = _lib.load()
     rows = [int(r) for r in rows]
-    if lay.n_f32 and lay.n_i64 and not lay.n_b16:
-        check(L.tal_agg_model_f32(_lib.ptr_array(pool.row_ptrs("f32", rows)), _lib.ptr_array(pool.row_ptrs("i64", rows)),
-                                  W, m, ctypes.c_void_p(pool.row_ptrs("f32", [out_row])[0]), lay.n_f32,
-                                  ctypes.c_void_p(pool.row_ptrs("i64", [out_row])[0]), lay.n_i64, int(mode), s))
+    if lay.single_launch:
+        check(_lib.load().tal_agg_model_f32(
+            _lib.ptr_array(pool.row_ptrs("f32", rows)), _lib.ptr_array(pool.row_ptrs("i64", rows)), W, m,
+            ctypes.c_void_p(pool.row_ptrs("f32", [out_row])[0]), lay.n_f32,
+            ctypes.c_void_p(pool.row_ptrs("i64", [out_row])[0]), lay.n_i64, int(mode), s))
         return
-    for seg, n in (("f32", lay.n_f32), ("b16", lay.n_b16), ("i64", lay.n_i64)):
-        if not n:
-            continue
-        P = _lib.ptr_array(pool.row_ptrs(seg, rows))
-        out = ctypes.c_void_p(pool.row_ptrs(seg, [out_row])[0])
-        if seg == "i64":
-            check(L.tal_agg_i64(P, W, m, out, n, s))
-        else:
-            fn = L.tal_agg_f32 if seg == "f32" else L.tal_agg_bf16
-            check(fn(P, W, m, out, n, int(mode), s))
-
-
-def agg_bf16(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Tensor,
-             mode: int = MODE_EXACT, stream=None) -> torch.Tensor:
-    """K1 on bf16 buffers.  MODE_EXACT: the reference's torch ops on bf16 tensors (every product
-    and partial sum rounded to bf16; decentralized_client.py:407-411); MODE_FMA: fp32 fused
-    accumulation rounded once."""
-    _require_gpu(out, "out", torch.bfloat16)
-    n = out.numel()
-    P, W = _ptrs_and_weights(xs, weights, n, torch.bfloat16, out)
-    L = _lib.load()
-    check(L.tal_agg_bf16(P, W, len(xs), ctypes.c_void_p(out.data_ptr()), n, int(mode),
-                         _stream(out.device, stream)))
-    return out
+    for g, n in lay.sizes.items():
+        _call("tal_agg", SEG[g], (_lib.ptr_array(pool.row_ptrs(g, rows)), W, m,
+                                  ctypes.c_void_p(pool.row_ptrs(g, [out_row])[0]), n), mode, s)
 
 
 # ------------------------------------------------------------------------------------------
 # Host reduction (a process that sees no GPU: BASELINE config 1)
 # ------------------------------------------------------------------------------------------
-_HOST_FN = {torch.float32: "tal_host_agg_f32", torch.int64: "tal_host_agg_i64",
-            torch.bfloat16: "tal_host_agg_bf16"}
-
-
 def host_agg(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Tensor,
              mode: int = MODE_EXACT) -> torch.Tensor:
     """The library's host reduction (tal_host_agg_*) on contiguous CPU tensors of one dtype:
     out = sum_i fp32(w_i) * xs[i] with the kernels' arithmetic (fp32 / int64 / bf16, modes as
     agg_f32 / agg_i64 / agg_bf16).  For processes without a GPU only (aggregate.py dispatches
     on torch.cuda.is_available()); GPU tensors are refused."""
-    if out.device.type != "cpu" or not out.is_contiguous() or out.dtype not in _HOST_FN:
+    if out.device.type != "cpu" or not out.is_contiguous() or out.dtype not in (s.dtype for s in SEGMENTS):
         raise ValueError("host_agg: out must be a contiguous CPU float32 / int64 / bfloat16 tensor")
     if len(xs) == 0 or len(weights) != len(xs):
         raise ValueError("host_agg: one weight per operand, at least one operand")
@@ -166,12 +181,8 @@ def host_agg(xs: Sequence[torch.Tensor], weights: Sequence[float], out: torch.Te
     for i, x in enumerate(xs):
         if x.device.type != "cpu" or x.dtype != out.dtype or not x.is_contiguous() or x.numel() != n:
             raise ValueError(f"host_agg: operand {i} must be a contiguous CPU {out.dtype} tensor of {n} elements")
-    L = _lib.load()
     P, W = _lib.ptr_array([x.data_ptr() for x in xs]), _lib.double_array(weights)
-    args = [P, W, len(xs), ctypes.c_void_p(out.data_ptr()), n]
-    if out.dtype != torch.int64:
-        args.append(int(mode))
-    check(getattr(L, _HOST_FN[out.dtype])(*args))
+    _call("tal_host_agg", segment_of(out.dtype), (P, W, len(xs), ctypes.c_void_p(out.data_ptr()), n), mode)
     return out
 
 
@@ -205,6 +216,14 @@ class RoundPlan:
     @property
     def single_group(self) -> bool:
         return self.info.n_groups == 1
+
+    @cached_property
+    def row_bounds(self):
+        """(largest pool row the plan reads, largest it writes); -1 for none.  Read from the blob
+        once: a plan's blob does not change after it is built."""
+        h, i = self.host, self.info
+        return (int(h[i.off_src_row: i.off_src_row + i.total_src].max(initial=-1)),
+                int(h[i.off_out_row: i.off_out_row + i.rows].max(initial=-1)))
 
     def to(self, device) -> "RoundPlan":
         self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
@@ -254,27 +273,37 @@ def row_call_plan(row_ptr, col, w, out_row) -> RowCallPlan:
     return RowCallPlan(rp, cl, ww, orow, spec={"rows_k1": 1})
 
 
-def _round_rows(pool_in, pool_out, plan: RowCallPlan, n, dtype, mode, stream):
+def _check_pools(seg: Segment, pool_in, pool_out=None, what: Optional[str] = None, devices: bool = True) -> None:
+    """The pool checks of the four round paths.  One pool (K3q, in place): a GPU tensor of the
+    segment's dtype, 2-D with unit column stride, any row stride.  Two pools: contiguous 2-D GPU
+    tensors of that dtype,
+    on one device where `devices` (the per-row round leaves that to its K1 calls), and - `what`
+    names a round that must run out of place - not the same memory."""
+    dtype = seg.dtype
+    if pool_out is None:
+        _require_gpu(pool_in, "pool", dtype, contiguous=False)
+        if pool_in.dim() != 2 or pool_in.stride(1) != 1:
+            raise ValueError("pool must be 2-D [models, ld] with unit column stride")
+        return
     _require_gpu(pool_in, "pool_in", dtype)
     _require_gpu(pool_out, "pool_out", dtype)
     if pool_in.dim() != 2 or pool_out.dim() != 2:
         raise ValueError("pools must be 2-D [models, ld]")
-    if pool_in.data_ptr() == pool_out.data_ptr():
-        raise ValueError("a per-row round runs out of place (snapshot semantics)")
+    if devices and pool_in.device != pool_out.device:
+        raise ValueError("pools on different devices")
+    if what is not None and pool_in.data_ptr() == pool_out.data_ptr():
+        raise ValueError(f"a {what} round runs out of place (snapshot semantics)")
+
+
+def _round_rows(seg: Segment, pool_in, pool_out, plan: RowCallPlan, n, mode, stream):
+    _check_pools(seg, pool_in, pool_out, what="per-row", devices=False)
     n = pool_in.shape[1] if n is None else int(n)
     if plan.col.max(initial=-1) >= pool_in.shape[0] or plan.out_row.max(initial=-1) >= pool_out.shape[0]:
         raise ValueError("plan rows beyond the pools")
     for r in range(plan.rows):
         a, b = int(plan.row_ptr[r]), int(plan.row_ptr[r + 1])
-        xs = [pool_in[int(j), :n] for j in plan.col[a:b]]
-        out = pool_out[int(plan.out_row[r]), :n]
-        ws = plan.w[a:b].tolist()
-        if dtype == torch.int64:
-            agg_i64(xs, ws, out, stream=stream)
-        elif dtype == torch.bfloat16:
-            agg_bf16(xs, ws, out, mode=mode, stream=stream)
-        else:
-            agg_f32(xs, ws, out, mode=mode, stream=stream)
+        agg([pool_in[int(j), :n] for j in plan.col[a:b]], plan.w[a:b].tolist(), pool_out[int(plan.out_row[r]), :n],
+            mode, stream, seg.name)
     return pool_out
 
 
@@ -551,8 +580,10 @@ class CliquePlan:
         self.full.to(device)
         return self
 
+    @cached_property
     def row_bounds(self):
-        """(largest pool row the clique blocks read, largest they write); -1 for none."""
+        """(largest pool row the clique blocks read, largest they write); -1 for none.  Read from
+        the tables once: they do not change after the plan is built."""
         t = self.table.reshape(self.n_cliques, CLIQUE_WORDS)
         att = t[:, 4 + 2 * CLIQUE_MAX:].reshape(self.n_cliques, CLIQUE_EXTRA, CLIQUE_EXTRA_WORDS)
         att = att[np.arange(CLIQUE_EXTRA)[None, :] < t[:, 2:3]]  # attached records in use
@@ -783,7 +814,7 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("tune_plan needs distinct input / output pools")
     bf16 = pool_in.dtype == torch.bfloat16  # bf16 rounds: sparse, narrow and clique plans
-    run = round_bf16 if bf16 else round_f32
+    run = round_bf16 if bf16 else round_f32  # (not round_pool: an int64 pool is refused)
     cands = tune_candidates(row_ptr, col, w, out_row, bf16=bf16, mode=mode)
     base = cands[0][1]
     if isinstance(base, CliquePlan) and base.rest is not None:  # the rows outside the cliques: tuned too
@@ -958,62 +989,13 @@ def round_f32(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[i
               mode: int = MODE_EXACT, stream=None) -> torch.Tensor:
     """K3 on [models, ld] fp32 pools (snapshot semantics; see tal_agg.h).  A CliquePlan runs
     its clique blocks with K3c and its other rows with their regular plan (out of place)."""
-    if isinstance(plan, CliquePlan):
-        return _round_clique(pool_in, pool_out, plan, n, torch.float32, mode, stream)
-    if isinstance(plan, RowCallPlan):
-        return _round_rows(pool_in, pool_out, plan, n, torch.float32, mode, stream)
-    return _round(pool_in, pool_out, plan, n, torch.float32, mode, stream)
-
-
-_CLIQUE_SUFFIX = {torch.float32: "_f32", torch.bfloat16: "_bf16"}
-
-
-def _round_clique(pool_in, pool_out, plan: CliquePlan, n, dtype, mode, stream):
-    _require_gpu(pool_in, "pool_in", dtype)
-    _require_gpu(pool_out, "pool_out", dtype)
-    if pool_in.dim() != 2 or pool_out.dim() != 2:
-        raise ValueError("pools must be 2-D [models, ld]")
-    if pool_in.device != pool_out.device:
-        raise ValueError("pools on different devices")
-    if pool_in.data_ptr() == pool_out.data_ptr():
-        raise ValueError("a clique round runs out of place (snapshot semantics)")
-    if plan.on != pool_in.device:
-        plan.to(pool_in.device)
-    n = pool_in.shape[1] if n is None else int(n)
-    pair = 2 * pool_in.element_size()
-    if plan.n_cliques > 0 and ((pool_in.stride(0) | pool_out.stride(0)) % 2
-                               or (pool_in.data_ptr() | pool_out.data_ptr()) % pair):
-        # K3c reads and writes column pairs (8 B fp32, 4 B bf16): rows not aligned to one take the full plan
-        # (K3c1 has no such rule: a plan of 65..128-member blocks alone never gets here)
-        return _round(pool_in, pool_out, plan.full, n, dtype, mode, stream)
-    reads, writes = plan.row_bounds()
-    if reads >= pool_in.shape[0]:
-        raise ValueError("plan reads a pool row beyond pool_in")
-    if writes >= pool_out.shape[0]:
-        raise ValueError("plan writes a pool row beyond pool_out")
-    L = _lib.load()
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    # K3c for the blocks of <= 64 members, then K3c1 for those of 65..128, each with per-source
-    # weights where the plan carries them; the entry is looked up by name at every call
-    for col_form, table, blocks, mmax, wtab in (
-            (False, plan.device, plan.n_cliques, plan.mmax, plan.wdevice if plan.wtable is not None else None),
-            (True, plan.col_device, plan.n_col, plan.col_mmax, plan.col_wdevice if plan.col_wtable is not None else None)):
-        if blocks > 0:
-            fn = getattr(L, "tal_agg_round_clique" + "_col" * col_form + "_w" * (wtab is not None) + _CLIQUE_SUFFIX[dtype])
-            check(fn(ptr(pool_in), pool_in.stride(0), ptr(pool_out), pool_out.stride(0), n, ptr(table), blocks, mmax,
-                     int(mode), _stream(pool_in.device, stream), *((ptr(wtab),) if wtab is not None else ())))
-    if plan.rest is not None:
-        _round(pool_in, pool_out, plan.rest, n, dtype, mode, stream)
-    return pool_out
+    return _round(_F32, pool_in, pool_out, plan, n, mode, stream)
 
 
 def round_i64(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n: Optional[int] = None,
               stream=None) -> torch.Tensor:
-    if isinstance(plan, CliquePlan):
-        plan = plan.full
-    if isinstance(plan, RowCallPlan):
-        return _round_rows(pool_in, pool_out, plan, n, torch.int64, MODE_EXACT, stream)
-    return _round(pool_in, pool_out, plan, n, torch.int64, MODE_EXACT, stream)
+    """K3 on [models, ld] int64 pools (chains as agg_i64); a CliquePlan runs its `full` plan."""
+    return _round(_I64, pool_in, pool_out, plan, n, MODE_EXACT, stream)
 
 
 def round_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n: Optional[int] = None,
@@ -1024,43 +1006,72 @@ def round_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: RoundPlan, n
     their regular plan, out of place; pools that miss the 4-B column-pair alignment take
     `plan.full`.  Blocks of 65..128 members (`col_table`) run K3c1 (tal_agg_round_clique_col_bf16),
     which has no alignment rule."""
+    return _round(_B16, pool_in, pool_out, plan, n, mode, stream)
+
+
+def round_pool(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[int] = None, mode: int = MODE_EXACT,
+               stream=None, seg: Optional[str] = None) -> torch.Tensor:
+    """K3 on [models, ld] pools of float32, bfloat16 or int64: round_f32, round_bf16 or round_i64
+    (which has no modes: `mode` is ignored there) by pool_in's dtype, or for the segment `seg` the
+    caller keeps the pools under - pools of another dtype are then refused."""
+    s = SEG[seg] if seg is not None else _segment(pool_in, "pool_in")
+    return globals()["round" + s.suffix](pool_in, pool_out, plan, n, *(mode,) * s.takes_mode, stream=stream)
+
+
+def _round(seg: Segment, pool_in, pool_out, plan, n, mode, stream) -> torch.Tensor:
+    """The round by the plan's kind: a CliquePlan runs K3c / K3c1 and its rest plan (on int64
+    pools, which the clique kernels do not take, its `full` plan), a RowCallPlan one K1 call per
+    row, any other plan the round kernel."""
     if isinstance(plan, CliquePlan):
-        return _round_clique(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
+        if seg is not _I64:
+            return _round_clique(seg, pool_in, pool_out, plan, n, mode, stream)
+        plan = plan.full
     if isinstance(plan, RowCallPlan):
-        return _round_rows(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
-    return _round(pool_in, pool_out, plan, n, torch.bfloat16, mode, stream)
-
-
-_ROUND_FN = {torch.float32: "tal_agg_round_f32", torch.int64: "tal_agg_round_i64",
-             torch.bfloat16: "tal_agg_round_bf16"}
-
-
-def _round(pool_in, pool_out, plan, n, dtype, mode, stream):
-    _require_gpu(pool_in, "pool_in", dtype)
-    _require_gpu(pool_out, "pool_out", dtype)
-    if pool_in.dim() != 2 or pool_out.dim() != 2:
-        raise ValueError("pools must be 2-D [models, ld]")
-    if pool_in.device != pool_out.device:
-        raise ValueError("pools on different devices")
+        return _round_rows(seg, pool_in, pool_out, plan, n, mode, stream)
+    _check_pools(seg, pool_in, pool_out)
     if plan.device is None or plan.device.device != pool_in.device:
         plan.to(pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
-    rows_in = pool_in.shape[0]
-    rows_out = pool_out.shape[0]
-    h = plan.host
-    i = plan.info
-    if h[i.off_src_row: i.off_src_row + i.total_src].max(initial=-1) >= rows_in:
+    reads, writes = plan.row_bounds
+    if reads >= pool_in.shape[0]:
         raise ValueError("plan reads a pool row beyond pool_in")
-    if h[i.off_out_row: i.off_out_row + i.rows].max(initial=-1) >= rows_out:
+    if writes >= pool_out.shape[0]:
         raise ValueError("plan writes a pool row beyond pool_out")
-    L = _lib.load()
-    fn = getattr(L, _ROUND_FN[dtype])
-    args = [ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
-            pool_out.stride(0), n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)]
-    if dtype != torch.int64:
-        args.append(int(mode))
-    args.append(_stream(pool_in.device, stream))
-    check(fn(*args))
+    _call("tal_agg_round", seg,
+          (ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
+           pool_out.stride(0), n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)),
+          mode, _stream(pool_in.device, stream))
+    return pool_out
+
+
+def _round_clique(seg: Segment, pool_in, pool_out, plan: CliquePlan, n, mode, stream):
+    _check_pools(seg, pool_in, pool_out, what="clique")
+    if plan.on != pool_in.device:
+        plan.to(pool_in.device)
+    n = pool_in.shape[1] if n is None else int(n)
+    pair = 2 * seg.esize
+    if plan.n_cliques > 0 and ((pool_in.stride(0) | pool_out.stride(0)) % 2
+                               or (pool_in.data_ptr() | pool_out.data_ptr()) % pair):
+        # K3c reads and writes column pairs (8 B fp32, 4 B bf16): rows not aligned to one take the full plan
+        # (K3c1 has no such rule: a plan of 65..128-member blocks alone never gets here)
+        return _round(seg, pool_in, pool_out, plan.full, n, mode, stream)
+    reads, writes = plan.row_bounds
+    if reads >= pool_in.shape[0]:
+        raise ValueError("plan reads a pool row beyond pool_in")
+    if writes >= pool_out.shape[0]:
+        raise ValueError("plan writes a pool row beyond pool_out")
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    # K3c for the blocks of <= 64 members, then K3c1 for those of 65..128, each with per-source
+    # weights where the plan carries them
+    for col_form, table, blocks, mmax, wtab in (
+            (False, plan.device, plan.n_cliques, plan.mmax, plan.wdevice if plan.wtable is not None else None),
+            (True, plan.col_device, plan.n_col, plan.col_mmax, plan.col_wdevice if plan.col_wtable is not None else None)):
+        if blocks > 0:
+            _call("tal_agg_round_clique" + "_col" * col_form + "_w" * (wtab is not None), seg,
+                  (ptr(pool_in), pool_in.stride(0), ptr(pool_out), pool_out.stride(0), n, ptr(table), blocks, mmax),
+                  mode, _stream(pool_in.device, stream), *((ptr(wtab),) if wtab is not None else ()))
+    if plan.rest is not None:
+        _round(seg, pool_in, pool_out, plan.rest, n, mode, stream)
     return pool_out
 
 
@@ -1121,21 +1132,19 @@ def build_seq_plan(row_ptr, col, w, out_row) -> SeqPlan:
     return SeqPlan(info=info, host=blob[: info.words].copy(), rows=rows, nnz=len(col), spec={"seq": 1})
 
 
-_ROUND_SEQ_FN = {torch.float32: "tal_agg_round_seq_f32", torch.int64: "tal_agg_round_seq_i64",
-                 torch.bfloat16: "tal_agg_round_seq_bf16"}
+def round_seq(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, mode: int = MODE_EXACT,
+              stream=None, seg: Optional[str] = None) -> torch.Tensor:
+    """K3q on a [models, ld] pool of float32, bfloat16 or int64, in place: round_seq_f32,
+    round_seq_bf16 or round_seq_i64 (which has no modes: `mode` is ignored there) by the pool's
+    dtype, or for the segment `seg` the caller keeps the pool under."""
+    s = SEG[seg] if seg is not None else _segment(pool, "pool")
+    return globals()["round_seq" + s.suffix](pool, plan, n, *(mode,) * s.takes_mode, stream=stream)
 
 
-def _round_seq(pool, plan: SeqPlan, n, dtype, mode, stream):
+def _round_seq(seg: Segment, pool, plan: SeqPlan, n, mode, stream) -> torch.Tensor:
     if not isinstance(plan, SeqPlan):
         raise TypeError("a sequential round takes a SeqPlan (build_seq_plan)")
-    if not isinstance(pool, torch.Tensor):
-        raise TypeError("pool must be a torch.Tensor")
-    if pool.device.type != "cuda":
-        raise ValueError(f"pool must be a GPU tensor (got {pool.device}); the aggregation has no CPU path")
-    if pool.dtype != dtype:
-        raise ValueError(f"pool must be {dtype} (got {pool.dtype})")
-    if pool.dim() != 2 or pool.stride(1) != 1:
-        raise ValueError("pool must be 2-D [models, ld] with unit column stride")
+    _check_pools(seg, pool)
     n = pool.shape[1] if n is None else int(n)
     if not 0 <= n <= pool.shape[1]:
         raise ValueError(f"n = {n} outside the pool's {pool.shape[1]} columns")
@@ -1143,13 +1152,9 @@ def _round_seq(pool, plan: SeqPlan, n, dtype, mode, stream):
         raise ValueError("plan reads or writes a pool row beyond the pool")
     if plan.device is None or plan.device.device != pool.device:
         plan.to(pool.device)
-    L = _lib.load()
-    args = [ctypes.c_void_p(pool.data_ptr()), pool.stride(0), pool.shape[0], n,
-            ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)]
-    if dtype != torch.int64:
-        args.append(int(mode))
-    args.append(_stream(pool.device, stream))
-    check(getattr(L, _ROUND_SEQ_FN[dtype])(*args))
+    _call("tal_agg_round_seq", seg,
+          (ctypes.c_void_p(pool.data_ptr()), pool.stride(0), pool.shape[0], n,
+           ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)), mode, _stream(pool.device, stream))
     return pool
 
 
@@ -1157,18 +1162,18 @@ def round_seq_f32(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, mo
                   stream=None) -> torch.Tensor:
     """K3q on a [models, ld] fp32 pool, in place: the plan's rows in order, each the chain of
     agg_f32 on the pool as the rows before it left it (any row stride, element-aligned)."""
-    return _round_seq(pool, plan, n, torch.float32, mode, stream)
+    return _round_seq(_F32, pool, plan, n, mode, stream)
 
 
 def round_seq_bf16(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, mode: int = MODE_EXACT,
                    stream=None) -> torch.Tensor:
     """K3q on a bf16 pool (chains as agg_bf16 per mode; later rows read the stored bf16 value)."""
-    return _round_seq(pool, plan, n, torch.bfloat16, mode, stream)
+    return _round_seq(_B16, pool, plan, n, mode, stream)
 
 
 def round_seq_i64(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, stream=None) -> torch.Tensor:
     """K3q on an int64 pool (chains as agg_i64; later rows read the truncated integer)."""
-    return _round_seq(pool, plan, n, torch.int64, MODE_EXACT, stream)
+    return _round_seq(_I64, pool, plan, n, MODE_EXACT, stream)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1377,14 +1382,15 @@ def host_cosine_round(pool_f32: torch.Tensor, pairs_or_table, plan: CosinePlan) 
 # ------------------------------------------------------------------------------------------
 # Synthetic pool rows (benchmark / full-size test inputs)
 # ------------------------------------------------------------------------------------------
-_FILL_TORCH = {0: torch.float32, 1: torch.bfloat16, 2: torch.int64}
-
-
 def fill_counter(seg: torch.Tensor, table: np.ndarray, dtype_code: int, stream=None) -> torch.Tensor:
     """tal_fill_counter: rows 0..n_rows-1 of the [rows, ld] segment `seg` = synth's counter
-    generator per `table` (synth.fill_table), one launch for all rows."""
-    if seg.device.type != "cuda" or seg.dtype != _FILL_TORCH[int(dtype_code)]:
-        raise ValueError(f"fill_counter needs a GPU {_FILL_TORCH[int(dtype_code)]} segment (got {seg.device} {seg.dtype})")
+    generator per `table` (synth.fill_table), one launch for all rows.  dtype_code: the library's
+    element-type code, the segment's place in arena.SEGMENTS (0 fp32, 1 bf16, 2 int64)."""
+    if not 0 <= int(dtype_code) < len(SEGMENTS):
+        raise KeyError(dtype_code)
+    dtype = SEGMENTS[int(dtype_code)].dtype
+    if seg.device.type != "cuda" or seg.dtype != dtype:
+        raise ValueError(f"fill_counter needs a GPU {dtype} segment (got {seg.device} {seg.dtype})")
     tab = np.ascontiguousarray(table, dtype=np.int64)
     n_rows, n = int(tab[0]), int(tab[1])
     if seg.dim() != 2 or seg.stride(1) != 1 or seg.shape[0] < n_rows or seg.shape[1] < n:

@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .arena import StateLayout, bound_row
+from .arena import SEG, StateLayout, bound_row
 
 _MAX_NB = 64  # neighbors per launch (kProxMaxNb): past it tal_prox_grad_bf16 needs its fp32 scratch
 
@@ -85,18 +85,11 @@ def _stream(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def _rows(pool, kind: str):
-    """(row accessor, row pitch in elements, torch dtype) of the segment the plan's kind names."""
-    if kind == "b16":
-        return pool.row_b16, pool.layout.ld_b16, torch.bfloat16
-    return pool.row_f32, pool.layout.ld_f32, torch.float32
-
-
 def prox_norms(pool, row: int, neighbor_rows: Sequence[int], plan: ProxPlan) -> torch.Tensor:
     """norms[t, p] = ||w_p - wt_p||_2 for the pool rows (float32 [K, P], for bf16 rows too)."""
     L = _lib.load()
     k = len(neighbor_rows)
-    row_of = _rows(pool, plan.kind)[0]
+    row_of = lambda r: pool.row(plan.kind, r)  # noqa: E731
     fn = L.tal_prox_norms_bf16 if plan.kind == "b16" else L.tal_prox_norms
     scratch = torch.empty(int(L.tal_prox_scratch_bytes(plan.n_chunks, k)), dtype=torch.uint8, device=pool.device)
     norms = torch.empty((k, plan.n_seg), dtype=torch.float32, device=pool.device)
@@ -123,7 +116,8 @@ class _ProxFn(torch.autograd.Function):
         plan, pool, k, P = ctx.plan, ctx.pool, len(ctx.neighbor_rows), ctx.n_client
         L = _lib.load()
         scale = g.detach().to(torch.float32).reshape(1).contiguous()
-        row_of, n, dtype = _rows(pool, plan.kind)
+        row_of = lambda r: pool.row(plan.kind, r)  # noqa: E731
+        n, dtype = getattr(pool.layout, "ld_" + plan.kind), SEG[plan.kind].dtype
         gw = torch.zeros(n, dtype=dtype, device=pool.device)
         want_t = [any(ctx.needs[P + t * P: P + (t + 1) * P]) for t in range(k)]
         gwt = [torch.zeros(n, dtype=dtype, device=pool.device) if wnt else None for wnt in want_t]

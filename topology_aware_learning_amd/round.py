@@ -40,6 +40,34 @@ def csr_from_lists(orders: Sequence[Sequence[int]], weights: Sequence[Sequence[f
     return np.array(row_ptr, np.int32), np.array(col, np.int32), np.array(w, np.float64)
 
 
+def tune_segment(layout) -> str:
+    """The segment a round plan is tuned and a pool's placement timed on: bf16 when there is one
+    (its plan forms - sparse, narrow, clique - also run fp32 and int64), else fp32."""
+    return "b16" if layout.n_b16 else "f32"
+
+
+def _plan_key(orders, weights, out_rows) -> Tuple:
+    return tuple(map(tuple, orders)), tuple(tuple(map(float, w)) for w in weights), tuple(out_rows)
+
+
+def _time_placements(make, run_round, trials: int):
+    """`trials` pools from make(), each warmed with one run_round(candidate) and timed over two
+    more with device events: (candidates, ms per round rounded to 3 decimals)."""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    cands, ms = [], []
+    for _ in range(trials):
+        c = make()
+        run_round(c)
+        s.record()
+        for _ in range(2):
+            run_round(c)
+        e.record()
+        e.synchronize()
+        cands.append(c)
+        ms.append(round(s.elapsed_time(e) / 2, 3))
+    return cands, ms
+
+
 class RoundExecutor:
     """Rounds over one pool.
 
@@ -96,30 +124,18 @@ class RoundExecutor:
         trials = min(self.placement_trials, fit)
         if trials <= 1:
             return make()
-        seg = "b16" if lay.n_b16 else "f32"
-        n = lay.n_b16 if lay.n_b16 else lay.n_f32
-        run = ops.round_bf16 if lay.n_b16 else ops.round_f32
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        cands, ms = [], []
-        for _ in range(trials):
-            c = make()
-            run(getattr(self.pool, seg), getattr(c, seg), plan, n=n, mode=self.mode)
-            s.record()
-            for _ in range(2):
-                run(getattr(self.pool, seg), getattr(c, seg), plan, n=n, mode=self.mode)
-            e.record()
-            e.synchronize()
-            cands.append(c)
-            ms.append(round(s.elapsed_time(e) / 2, 3))
+        seg = tune_segment(lay)
+        cands, ms = _time_placements(make, lambda c: ops.round_pool(self.pool.seg(seg), c.seg(seg), plan,
+                                                                    n=lay.sizes.get(seg, 0), mode=self.mode, seg=seg), trials)
         best = int(np.argmin(ms))
         self.placement = dict(scratch_ms=ms, chosen=best)
         keep = cands[best]
-        del cands, c  # (the loop variable still held the last candidate)
+        del cands
         torch.cuda.empty_cache()
         return keep
 
     def plan(self, orders, weights, out_rows) -> ops.RoundPlan:
-        key = (tuple(map(tuple, orders)), tuple(tuple(map(float, w)) for w in weights), tuple(out_rows))
+        key = _plan_key(orders, weights, out_rows)
         p = self._plans.get(key)
         if p is None:
             row_ptr, col, w = csr_from_lists(orders, weights)
@@ -136,7 +152,7 @@ class RoundExecutor:
     def seq_plan(self, orders, weights, out_rows) -> Optional[ops.SeqPlan]:
         """The K3q plan of these lists, built once; None for a round of more distinct sources
         than the kernel's tile holds (TAL_ERR_CAPACITY)."""
-        key = (tuple(map(tuple, orders)), tuple(tuple(map(float, w)) for w in weights), tuple(out_rows))
+        key = _plan_key(orders, weights, out_rows)
         if key not in self._seq_plans:
             row_ptr, col, w = csr_from_lists(orders, weights)
             try:
@@ -170,20 +186,12 @@ class RoundExecutor:
                     ops.SEQ_DEFAULT[(bool(lay.n_b16), self.mode)]:
                 sp = self.seq_plan(orders, weights, out_rows)
             if sp is not None:
-                if lay.n_f32:
-                    ops.round_seq_f32(self.pool.f32, sp, n=lay.n_f32, mode=self.mode)
-                if lay.n_b16:
-                    ops.round_seq_bf16(self.pool.b16, sp, n=lay.n_b16, mode=self.mode)
-                if lay.n_i64:
-                    ops.round_seq_i64(self.pool.i64, sp, n=lay.n_i64)
+                for g, t, n in self.pool.segments():
+                    ops.round_seq(t, sp, n, self.mode, seg=g)
                 return
             for r, o, w in zip(out_rows, orders, weights):
-                if lay.n_f32:
-                    ops.agg_f32([self.pool.row_f32(j) for j in o], w, self.pool.row_f32(r), mode=self.mode)
-                if lay.n_b16:
-                    ops.agg_bf16([self.pool.row_b16(j) for j in o], w, self.pool.row_b16(r), mode=self.mode)
-                if lay.n_i64:
-                    ops.agg_i64([self.pool.row_i64(j) for j in o], w, self.pool.row_i64(r))
+                for g, t, n in self.pool.segments():
+                    ops.agg([t[j, :n] for j in o], w, t[r, :n], self.mode, seg=g)
             return
         if plan is None:
             plan = self.plan(orders, weights, out_rows)
@@ -210,20 +218,12 @@ class RoundExecutor:
         if dst is self.pool:
             return
         idx = torch.as_tensor(list(out_rows), dtype=torch.long, device=self.pool.device)
-        for _, t, _ in self.pool.segments():
-            src = {id(self.pool.f32): self.scratch.f32, id(self.pool.b16): self.scratch.b16,
-                   id(self.pool.i64): self.scratch.i64}[id(t)]
+        for (_, t, _), (_, src, _) in zip(self.pool.segments(), self.scratch.segments()):
             t.index_copy_(0, idx, src.index_select(0, idx))
 
-
     def _launch(self, plan, dst: ModelPool) -> None:
-        lay = self.pool.layout
-        if lay.n_f32:
-            ops.round_f32(self.pool.f32, dst.f32, plan, n=lay.n_f32, mode=self.mode)
-        if lay.n_b16:
-            ops.round_bf16(self.pool.b16, dst.b16, plan, n=lay.n_b16, mode=self.mode)
-        if lay.n_i64:
-            ops.round_i64(self.pool.i64, dst.i64, plan, n=lay.n_i64)
+        for (g, src, n), (_, out, _) in zip(self.pool.segments(), dst.segments()):
+            ops.round_pool(src, out, plan, n, self.mode, seg=g)
 
 
 def calibrated_pool(layout, rows: int, device, trials: int = 8, degree: int = 8) -> ModelPool:
@@ -239,9 +239,8 @@ def calibrated_pool(layout, rows: int, device, trials: int = 8, degree: int = 8)
 
     device = torch.device(device)
     make = lambda: ModelPool(layout, rows, device)  # noqa: E731
-    row_bytes = 4 * layout.ld_f32 + 2 * layout.ld_b16 + 8 * layout.ld_i64
     if device.type == "cuda":
-        trials = min(trials, int(0.6 * torch.cuda.mem_get_info(device)[0] // max(1, rows * row_bytes)))
+        trials = min(trials, int(0.6 * torch.cuda.mem_get_info(device)[0] // max(1, rows * layout.row_bytes)))
     if trials <= 1 or rows < 3:
         return make()
     d = min(degree, rows - 1)
@@ -253,24 +252,12 @@ def calibrated_pool(layout, rows: int, device, trials: int = 8, degree: int = 8)
     plan = ops.default_plan(rp, col, w, np.arange(rows, dtype=np.int32), bf16=bool(layout.n_b16)).to(device)
     if not plan.single_group:
         return make()
-    seg, n = ("b16", layout.n_b16) if layout.n_b16 else ("f32", layout.n_f32)
-    run = ops.round_bf16 if layout.n_b16 else ops.round_f32
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    cands, ms = [], []
-    for _ in range(trials):
-        c = make()
-        t = getattr(c, seg)
-        run(t, t, plan, n=n)
-        s.record()
-        for _ in range(2):
-            run(t, t, plan, n=n)
-        e.record()
-        e.synchronize()
-        cands.append(c)
-        ms.append(round(s.elapsed_time(e) / 2, 3))
+    seg = tune_segment(layout)
+    cands, ms = _time_placements(make, lambda c: ops.round_pool(c.seg(seg), c.seg(seg), plan,
+                                                                n=layout.sizes.get(seg, 0), seg=seg), trials)
     best = int(np.argmin(ms))
     keep = cands[best]  # still all zeros: the rounds mixed zero rows
     keep.placement_ms = dict(in_place_ms=ms, chosen=best)
-    del cands, c, t  # (the loop variables still held the last candidate)
+    del cands
     torch.cuda.empty_cache()
     return keep

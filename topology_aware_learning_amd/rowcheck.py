@@ -25,16 +25,14 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 
 from . import ops, synth
-
-_DT = {"f32": ("float32", torch.float32, torch.int32), "b16": ("bfloat16", torch.bfloat16, torch.int16),
-       "i64": ("int64", torch.int64, torch.int64)}
+from .arena import SEG
 
 
 def fill_owned(pool, lay, own_ids: Sequence[int], seed_base: int) -> None:
     """Rows 0..len(own_ids)-1 of `pool` = the models of devices own_ids (seed seed_base + id)."""
     seeds = [seed_base + int(g) for g in own_ids]
     for g, t, n in pool.segments():
-        synth.fill_rows_torch(t[: len(seeds)], lay, seeds, dtype=_DT[g][0])
+        synth.fill_rows_torch(t[: len(seeds)], lay, seeds, dtype=SEG[g].synth)
 
 
 def row_digests(seg: torch.Tensor, rows: Sequence[int], ranges, view) -> List[List[str]]:
@@ -70,15 +68,11 @@ def check_against_digests(out_pool, own_ids: Sequence[int], expected: Dict[str, 
     for g, t, n in out_pool.segments():
         if g not in expected:
             continue
-        got = row_digests(t, range(len(own_ids)), ranges[g], _DT[g][2])
+        got = row_digests(t, range(len(own_ids)), ranges[g], SEG[g].bits)
         for k, gid in enumerate(own_ids):
             if got[k] != expected[g][int(gid)]:
                 bad.add(int(gid))
     return sorted(bad)
-
-
-def _k1(seg: str):
-    return {"f32": ops.agg_f32, "b16": ops.agg_bf16}.get(seg)
 
 
 def check_against_k1(out_pool, own_ids: Sequence[int], lay, orders, weights, seed_base: int, mode: int,
@@ -86,21 +80,15 @@ def check_against_k1(out_pool, own_ids: Sequence[int], lay, orders, weights, see
     """Own output rows that differ (bitwise, every segment) from K1 on their operands
     regenerated from the seeds.  Operands are generated once per batch of output rows (as many
     rows as keep the batch's distinct operands within `budget_bytes`) into a scratch pool.
-    agg(seg, operand rows, weights, out, mode): the reducer (default K1: ops.agg_f32 /
-    agg_bf16 / agg_i64); tests on a host without a GPU pass the oracle.  Returns differing ids."""
+    agg(seg, operand rows, weights, out, mode): the reducer (default K1: ops.agg); tests on a
+    host without a GPU pass the oracle.  Returns differing ids."""
     from .arena import ModelPool
 
     layout = out_pool.layout
     row_bytes = 4 * layout.ld_f32 * bool(layout.n_f32) + 2 * layout.ld_b16 * bool(layout.n_b16) + 8 * layout.ld_i64
     cap = max(max(len(orders[int(g)]) for g in own_ids), int(budget_bytes // max(row_bytes, 1)))
 
-    def default_agg(seg, xs, w, out, m):
-        if seg == "i64":
-            ops.agg_i64(xs, w, out)
-        else:
-            _k1(seg)(xs, w, out, mode=m)
-
-    agg = agg or default_agg
+    agg = agg or (lambda seg, xs, w, out, m: ops.agg(xs, w, out, mode=m, seg=seg))
     bad = []
     batch: List[int] = []
     need: Dict[int, int] = {}
@@ -116,11 +104,10 @@ def check_against_k1(out_pool, own_ids: Sequence[int], lay, orders, weights, see
             gid = int(own_ids[k])
             same = True
             for g, t, n in out_pool.segments():
-                src = dict((s, tt) for s, tt, _ in scratch.segments())[g]
+                src = scratch.seg(g)
                 chk = torch.empty(n, dtype=t.dtype, device=t.device)
                 agg(g, [src[slot[j], :n] for j in orders[gid]], list(weights[gid]), chk, mode)
-                iv = _DT[g][2]
-                same = same and torch.equal(chk.view(iv), t[k, :n].view(iv))
+                same = same and torch.equal(chk.view(SEG[g].bits), t[k, :n].view(SEG[g].bits))
             if not same:
                 bad.append(gid)
         batch.clear()

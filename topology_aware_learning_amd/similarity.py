@@ -35,10 +35,6 @@ def _param_names(model: nn.Module) -> List[str]:
     return [n for n, _ in model.named_parameters()]
 
 
-def _row(pool, r: int, kind: str) -> torch.Tensor:
-    return pool.row_f32(r) if kind == "f32" else pool.row_b16(r)
-
-
 def _flat(models: Sequence[nn.Module], layout, device, kind: str) -> List[torch.Tensor]:
     """Each model's parameter segment (kind: "f32" or "b16") on `device`."""
     out: List = [None] * len(models)
@@ -46,7 +42,7 @@ def _flat(models: Sequence[nn.Module], layout, device, kind: str) -> List[torch.
     for j, m in enumerate(models):
         b = bound_row(m)
         if b is not None and b[0].device == device and b[0].layout == layout:
-            out[j] = _row(b[0], b[1], kind)
+            out[j] = b[0].row(kind, b[1])
         else:
             rest.append(j)
     if rest:
@@ -85,7 +81,7 @@ def cosine_round(pool, pairs: Sequence[Tuple[int, int]], model: nn.Module) -> Li
     if layout_of_module(model) != layout:
         raise ValueError("cosine_round: the model does not have the pool's layout")
     plan, kind = _plan_for(layout, _param_names(model))
-    seg = pool.f32 if kind == "f32" else pool.b16
+    seg = pool.seg(kind)
     if not torch.cuda.is_available():
         return [float(x) for x in ops.host_cosine_round(seg, pairs, plan).tolist()]
     with torch.cuda.device(pool.device):
@@ -111,7 +107,7 @@ def cosine_pairs(model: nn.Module, others: Sequence[nn.Module]) -> List[float]:
         pool = b0[0]
         with torch.cuda.device(pool.device):
             rows = mp[0].rows_for(mp[1], bounds)
-            res = ops.cosine([_row(pool, b0[1], kind)] * len(others), [_row(pool, r, kind) for r in rows], plan)
+            res = ops.cosine([pool.row(kind, b0[1])] * len(others), [pool.row(kind, r) for r in rows], plan)
             return [float(x) for x in res.cpu().tolist()]
     flats = _flat([model, *others], layout, device, kind)
     res = ops.cosine([flats[0]] * len(others), flats[1:], plan)
@@ -126,7 +122,7 @@ def _host_flat(models: Sequence[nn.Module], layout, kind: str) -> List[torch.Ten
     for j, m in enumerate(models):
         b = bound_row(m)
         if b is not None and b[0].device.type == "cpu" and b[0].layout == layout:
-            out.append(_row(b[0], b[1], kind))
+            out.append(b[0].row(kind, b[1]))
             continue
         sd = m.state_dict()
         layout.check_compatible(sd, f"model {j}")

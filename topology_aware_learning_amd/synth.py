@@ -18,6 +18,8 @@ from typing import Iterable, List, Sequence, Tuple
 import numpy as np
 import torch
 
+from .arena import SEGMENTS
+
 Layout = List[Tuple[str, Tuple[int, ...], str]]  # dtype in {"float32", "bfloat16", "int64"}
 
 _M1 = np.uint64(0x9E3779B97F4A7C15)
@@ -172,7 +174,7 @@ def _row_plan(layout: Layout, dtype: str, device):
     return hit
 
 
-_FILL_DT = {"float32": 0, "bfloat16": 1, "int64": 2}
+_FILL_DT = {s.synth: k for k, s in enumerate(SEGMENTS)}  # tal_fill_counter's element-type codes
 _FILL_HI = 1_000_000  # counter_i64's default range
 
 

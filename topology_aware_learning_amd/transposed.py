@@ -29,10 +29,10 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .arena import ModelPool, StateLayout
-from .distributed import (_ESIZE, ShardedRound, _pool_segs, build_shard, float_segments, partition_contiguous,
-                          run_round_segments, spot_check_row, tune_segment)
-from .round import csr_from_lists
+from .arena import SEG, ModelPool, StateLayout
+from .distributed import (ShardedRound, build_shard, float_segments, partition_contiguous, run_round_segments,
+                          spot_check_row)
+from .round import csr_from_lists, tune_segment
 
 
 def _round_up(x: int, a: int) -> int:
@@ -244,15 +244,12 @@ class TransposedRound:
         self.pool_a = ModelPool(layout, self.local_rows, self.device)
         self.chunks = max(1, int(chunks if chunks is not None else 4))
         self.segs: Dict[str, _ColSeg] = {}
-        for g, n, dt in (("f32", layout.n_f32, torch.float32), ("b16", layout.n_b16, torch.bfloat16),
-                         ("i64", layout.n_i64, torch.int64)):
-            if not n:
-                continue
+        for g, n in layout.sizes.items():
             b, blocks = column_blocks(n, world)
             c = 1 if g == "i64" else max(1, min(self.chunks, b // 4))
             bc = _round_up(-(-b // c), 4)
 
-            def z(*shape, dt=dt):
+            def z(*shape, dt=SEG[g].dtype):
                 return torch.zeros(*shape, dtype=dt, device=self.device)
 
             peers = max(1, world - 1)
@@ -298,7 +295,7 @@ class TransposedRound:
     def pack(self, k: int = 0) -> None:
         """Chunk k of my models: block p into send (peer p), my own block straight into the
         head rows of work_in (it never leaves this GPU)."""
-        pools = _pool_segs(self.pool_a)
+        pools = {g: t for g, t, _ in self.pool_a.segments()}
         own = self.rows_of(self.rank)
         for g, s in self._segs_at(k):
             cb = s.chunk_blocks(k)
@@ -391,7 +388,7 @@ class TransposedRound:
     def unpack(self, k: int = 0) -> None:
         """My models' output chunk k: block p from back (peer p), my own block straight from the
         head rows of work_out."""
-        pools = _pool_segs(self.pool_a)
+        pools = {g: t for g, t, _ in self.pool_a.segments()}
         own = self.rows_of(self.rank)
         for g, s in self._segs_at(k):
             cb = s.chunk_blocks(k)
@@ -452,7 +449,7 @@ class TransposedRound:
     @property
     def kernel_bytes(self) -> int:
         """Algorithmic HBM bytes of one round's K3 launches (staged sources + written rows)."""
-        return sum(_ESIZE[g] * self.w_me[g] for g, _ in float_segments(self.layout)) * (
+        return sum(SEG[g].esize * self.w_me[g] for g, _ in float_segments(self.layout)) * (
             self.staged_sources + self.rows_all)
 
     @property
@@ -461,7 +458,7 @@ class TransposedRound:
         is copied on the GPU, not sent)."""
         r = 0
         for g, s in self.segs.items():
-            r += _ESIZE[g] * s.chunks * s.bc * ((self.rows_all - self.local_rows) + self.local_rows * (self.world - 1))
+            r += SEG[g].esize * s.chunks * s.bc * ((self.rows_all - self.local_rows) + self.local_rows * (self.world - 1))
         return r
 
     def spot_check(self) -> bool:
