@@ -53,6 +53,7 @@ extern "C" {
 
 #define TAL_MODE_FMA 0
 #define TAL_MODE_EXACT 1
+#define TAL_MODE_MATRIX 2   /* bf16 pools only: rounds on the matrix cores (K3m, tal_agg_round_matrix_bf16) */
 
 /* Thread-local text of the last error on this thread ("" if none). */
 const char* tal_last_error(void);
@@ -60,7 +61,8 @@ const char* tal_last_error(void);
  * register-resident source groups (K3r) with its entry point: no plan the library picks ever
  * selected it.  ABI 34 added the column clique entries with per-source weights
  * (tal_agg_round_clique_col_w_*).  ABI 35 added the sequential round in one launch (K3q:
- * tal_seq_plan_*, tal_agg_round_seq_*). */
+ * tal_seq_plan_*, tal_agg_round_seq_*).  ABI 36 added TAL_MODE_MATRIX: rounds on bf16 pools on the
+ * matrix cores (K3m: tal_matrix_plan_*, tal_agg_round_matrix_bf16). */
 int32_t tal_abi_version(void);
 
 /* ---- K1: one aggregation call over M flattened operands --------------------------------
@@ -440,6 +442,114 @@ int32_t tal_agg_round_seq_bf16(uint16_t* pool, int64_t ld, int64_t pool_rows, in
                                const tal_seq_plan_info* info, int32_t mode, void* stream);
 int32_t tal_agg_round_seq_i64(int64_t* pool, int64_t ld, int64_t pool_rows, int64_t n, const int32_t* plan_dev,
                               const tal_seq_plan_info* info, void* stream);
+
+/* ---- K3m: a round on bf16 pools on the matrix cores, TAL_MODE_MATRIX (ABI 36) ---------------
+ * A snapshot round, out of place, over the CSR of tal_agg_round_bf16: row r writes
+ *
+ *   pool_out[out_row[r]][e] = sum_k fp32(w[k]) * pool_in[col[k]][e]      (e < n)
+ *
+ * as OUT = W . X on v_mfma_f32_32x32x16_bf16: every bf16 x bf16 product is exact in fp32, the sum
+ * is accumulated in fp32 in the order the instruction and the tiling give (deterministic for a
+ * given plan), and the result is rounded to bf16 once at the store (nearest even, NaN stored as
+ * 0xFFFF).  It is NOT bit-comparable to TAL_MODE_FMA or TAL_MODE_EXACT: the mode is opt-in for a
+ * caller that has accepted a tolerance.  Against the float64 sum ref of fp32(w_k) * x_k over the
+ * row's M operands:
+ *
+ *   |out - ref| <= 2^-8 |ref| + (3M + 2) 2^-23 sum_k |w_k x_k| + (3M + 1) 2^-126
+ *
+ * 2^-8 |ref|: the store's one rounding.  3M terms: a weight that is not one per row is split
+ * exactly into three bf16 planes w1 = bf16(w), w2 = bf16(w - w1), w3 = bf16(w - w1 - w2) (nearest
+ * even; w1 + w2 + w3 == fp32(w) for normal w), each a term of the sum; + 2: the epilogue's scale
+ * and slack.  2^-23: one fp32 ulp per step, since the instruction's internal adds are not
+ * documented as round-to-nearest.  2^-126 per term: the matrix cores may flush subnormal inputs
+ * and outputs.
+ *
+ * Weights.  A row tile (32 consecutive rows of the round) whose rows each carry ONE fp32 weight
+ * for all their operands (the unweighted strategy, scale_agg) is "uniform": its A operand holds
+ * 1.0 / 0.0 and the row's fp32 weight multiplies the accumulator once in the epilogue.  Any other
+ * tile is "general": its k-blocks are emitted once per plane (a plane whose A tile is all zero is
+ * left out) and the epilogue scale is 1.0.
+ *
+ * Non-finite values.  0 x inf is NaN on the matrix cores, so a diverged source would poison rows
+ * that do not list it.  Every output element that is not finite after the k-loop and the scale is
+ * recomputed as tal_agg_bf16's TAL_MODE_FMA chain over the row's own CSR operands: a non-finite
+ * output is exactly FMA mode's, and a source a row does not use cannot reach it.  The same chain
+ * computes the columns the 4-column vector path cannot take: the n % 4 tail, and the whole round
+ * for pools that are not 8-B aligned with ld % 4 == 0 (slow, but served).
+ *
+ * Work split.  Rows in the caller's order, 32 to a tile; up to TAL_MATRIX_GROUP_TILES tiles to a
+ * group (one workgroup per group and 128-column strip, one wavefront per tile); a group's
+ * distinct sources, ascending, cut into chunks of TAL_MATRIX_CHUNK that are staged raw into LDS,
+ * double-buffered, the accumulators living across chunks - so neither the source count nor the
+ * row count of a round is bounded.  A (source, occurrence) pair is one k entry, so a row may list
+ * a source twice.
+ *
+ * Plan blob (int32 words; built on the host, copied to the device by the caller; every array at
+ * the offset tal_matrix_plan_info names):
+ *   header[16]     {rows, nnz, n_groups, n_tiles, n_chunks, n_kblocks, n_src, max_row, words, 0...}
+ *   grp_tile_ptr[n_groups+1]   tiles of each group
+ *   grp_chunk_ptr[n_groups+1]  chunks of each group
+ *   chunk_src_ptr[n_chunks+1]  into src_row: the sources of each chunk (<= TAL_MATRIX_CHUNK)
+ *   src_row[n_src]             pool_in row of each staged source (a group's: ascending)
+ *   tile_kb_ptr[n_tiles]       index into kb_ptr of the tile's first entry; the tile has one entry
+ *                              per chunk of its group plus one
+ *   kb_ptr[...]                k-block ranges: tile t visits k-blocks kb_ptr[tile_kb_ptr[t] + c] ..
+ *                              kb_ptr[tile_kb_ptr[t] + c + 1] - 1 while chunk c of its group is in LDS
+ *   tile_info[n_tiles][4]      {first row of the round, rows (1..32), planes (1 uniform, 3 general), 0}
+ *   tile_w[n_tiles][32]        fp32 bits of the epilogue scale of each row (general: 1.0)
+ *   kb_slots[n_kblocks][4]     16 bytes: the LDS slot (0 .. TAL_MATRIX_CHUNK-1, within the chunk)
+ *                              of k = 0..15; TAL_MATRIX_PAD (0xFF) marks a padding slot, whose B
+ *                              operand is zero from registers (the kernel reads LDS slot 0xFF %
+ *                              TAL_MATRIX_CHUNK, which always holds data or zeros, and drops it:
+ *                              its k-loop has no branch; no memory beyond the chunk is touched)
+ *   a_tiles[n_kblocks][256]    (16-B aligned) the A operand in lane order: lane l holds 8 bf16,
+ *                              A[row l % 32][k = 8 (l / 32) .. + 7], two per word, low half first
+ *   row_ptr[rows+1], col[nnz], w[nnz] (fp32 bits), out_row[rows]   the CSR, for the chain
+ * tal_matrix_plan_build: the checks of tal_seq_plan_build (TAL_ERR_INVALID for a null array, rows
+ * <= 0, an empty row, a negative pool row or an out_row listed twice); TAL_ERR_CAPACITY when
+ * plan_host is null or capacity_words too small - info->words then holds the size needed, and info
+ * is filled in both cases.  tal_matrix_plan_words is an upper bound for any such round.
+ *
+ * tal_agg_round_matrix_bf16: pool_rows = rows of the smaller of the two pools (as
+ * tal_agg_round_seq_*).  TAL_ERR_INVALID, with no launch, for a null pointer, pool_out == pool_in,
+ * n < 0, ld < n, an info that is not a matrix plan's or a plan row >= pool_rows (info->max_row, the
+ * largest row read or written); n == 0 returns TAL_OK without a launch. */
+#define TAL_MATRIX_CHUNK 64
+#define TAL_MATRIX_GROUP_TILES 8
+#define TAL_MATRIX_PAD 0xFF
+typedef struct tal_matrix_plan_info {
+  int32_t rows;          /* rows of the round */
+  int32_t nnz;           /* operands over all rows */
+  int32_t n_groups;
+  int32_t n_tiles;       /* row tiles over all groups */
+  int32_t n_chunks;      /* source chunks over all groups */
+  int32_t n_kblocks;     /* k-blocks (A tiles) over all tiles, planes included */
+  int32_t n_src;         /* staged sources over all groups */
+  int32_t max_row;       /* largest pool row read or written */
+  /* offsets (int32 words) of the arrays inside the blob */
+  int32_t off_grp_tile_ptr;
+  int32_t off_grp_chunk_ptr;
+  int32_t off_chunk_src_ptr;
+  int32_t off_src_row;
+  int32_t off_tile_kb_ptr;
+  int32_t off_kb_ptr;
+  int32_t off_tile_info;
+  int32_t off_tile_w;
+  int32_t off_kb_slots;
+  int32_t off_a_tiles;
+  int32_t off_row_ptr;
+  int32_t off_col;
+  int32_t off_w;
+  int32_t off_out_row;
+  int64_t words;         /* total int32 words of the blob */
+} tal_matrix_plan_info;
+int64_t tal_matrix_plan_words(int32_t rows, int64_t nnz);
+int32_t tal_matrix_plan_build(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
+                              const double* w_host, const int32_t* out_row_host, int32_t* plan_host,
+                              int64_t capacity_words, tal_matrix_plan_info* info);
+int32_t tal_agg_round_matrix_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                  int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                                  const tal_matrix_plan_info* info, void* stream);
 
 /* tal_agg_round_f32's round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or

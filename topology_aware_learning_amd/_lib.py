@@ -27,7 +27,8 @@ TAL_ERR_COMM = 4
 TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
-ABI_VERSION = 35
+TAL_MODE_MATRIX = 2
+ABI_VERSION = 36
 
 EXPORTED = (
     "tal_last_error",
@@ -58,6 +59,9 @@ EXPORTED = (
     "tal_agg_round_seq_f32",
     "tal_agg_round_seq_bf16",
     "tal_agg_round_seq_i64",
+    "tal_matrix_plan_words",
+    "tal_matrix_plan_build",
+    "tal_agg_round_matrix_bf16",
     "tal_cosine_plan_words",
     "tal_cosine_plan_build",
     "tal_cosine_plan_set_threads",
@@ -167,6 +171,16 @@ class SeqPlanInfo(ctypes.Structure):
     ]
 
 
+class MatrixPlanInfo(ctypes.Structure):
+    """tal_matrix_plan_info (tal_agg.h K3m)."""
+
+    _fields_ = [(f, ctypes.c_int32) for f in (
+        "rows", "nnz", "n_groups", "n_tiles", "n_chunks", "n_kblocks", "n_src", "max_row",
+        "off_grp_tile_ptr", "off_grp_chunk_ptr", "off_chunk_src_ptr", "off_src_row", "off_tile_kb_ptr",
+        "off_kb_ptr", "off_tile_info", "off_tile_w", "off_kb_slots", "off_a_tiles", "off_row_ptr", "off_col",
+        "off_w", "off_out_row")] + [("words", ctypes.c_int64)]
+
+
 class CosineRoundInfo(ctypes.Structure):
     """tal_cosine_round_info (tal_agg.h K2r)."""
 
@@ -229,6 +243,9 @@ _SIGS = {
     "tal_agg_round_seq_f32": (_I32, [_P, _I64, _I64, _I64, _P, ctypes.POINTER(SeqPlanInfo), _I32, _P]),
     "tal_agg_round_seq_bf16": (_I32, [_P, _I64, _I64, _I64, _P, ctypes.POINTER(SeqPlanInfo), _I32, _P]),
     "tal_agg_round_seq_i64": (_I32, [_P, _I64, _I64, _I64, _P, ctypes.POINTER(SeqPlanInfo), _P]),
+    "tal_matrix_plan_words": (_I64, [_I32, _I64]),
+    "tal_matrix_plan_build": (_I32, [_I32, _PI32, _PI32, _PD, _PI32, _PI32, _I64, ctypes.POINTER(MatrixPlanInfo)]),
+    "tal_agg_round_matrix_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _I64, _P, ctypes.POINTER(MatrixPlanInfo), _P]),
     "tal_cosine_plan_words": (_I64, [_PI64, _I32]),
     "tal_cosine_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),
     "tal_cosine_plan_set_threads": (_I32, [_PI64, _I32]),

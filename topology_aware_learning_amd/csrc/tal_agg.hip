@@ -11,8 +11,9 @@
 // with -ffp-contract=off and the exact kernels use explicit __fmul_rn / __fadd_rn so no FMA can
 // be formed; the FMA mode uses __builtin_fmaf explicitly.
 //
-// The op is element-wise with arithmetic intensity ~0.1 flop/B: every kernel here is bound by
-// HBM3E bandwidth (no MFMA — nothing here is a contraction).
+// The op is element-wise with arithmetic intensity ~0.1 flop/B: the EXACT and FMA kernels are
+// ordered chains on the vector ALU.  A whole round is the contraction OUT = W . X, and the opt-in
+// TAL_MODE_MATRIX round (K3m, bf16 pools) runs it on the matrix cores.
 
 #include <hip/hip_runtime.h>
 
@@ -46,7 +47,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 35;
+constexpr int kAbiVersion = 36;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -5499,6 +5500,479 @@ static bool cos_stream_wait(hipStream_t to, hipStream_t from) {
   const bool ok = hipEventRecord(e, from) == hipSuccess && hipStreamWaitEvent(to, e, 0) == hipSuccess;
   hipEventDestroy(e);
   return ok;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// K3m: a round on bf16 pools on the matrix cores (TAL_MODE_MATRIX; contract, error bound and plan
+// blob in tal_agg.h).  OUT = W . X with v_mfma_f32_32x32x16_bf16: M = 32 output rows (a row
+// tile), N = 32 element columns, K = 16 sources (a k-block).
+//
+// Work split: grid = (128-column strips, row groups).  A workgroup of kMxWaves wavefronts owns
+// one strip for one group of up to kMxWaves row tiles, one tile per wavefront: 4 column sub-tiles
+// x 16 fp32 accumulators per lane.  The group's sources pass through LDS in chunks of kMxChunk,
+// raw (the strip's 256 B of a source as they lie in HBM; kMxStage = 4 8-B loads per thread and
+// chunk), two buffers:
+// the loads of chunk c + 1 are in flight while chunk c is multiplied, one barrier per chunk, and
+// the accumulators live across chunks.
+//
+// The transposition: the B operand wants, per lane, eight consecutive k (sources) of ONE column;
+// LDS holds consecutive columns of one source.  Lane l takes columns 4 (l % 32) .. + 3 and the
+// k-block's slots 8 (l / 32) .. + 7: it reads its 8 B of each of its eight slots and turns the
+// eight 2-dword pieces into the four 4-dword B operands of the four sub-tiles with 16 v_perm_b32
+// (sub-tile c = column 4 (l % 32) + c of every lane), for 4 MFMAs.  So the four accumulators of a
+// lane for one row are four consecutive columns: one 8-B store.
+//
+// C / D layout of the instruction: lane l, register v holds row 8 (v / 4) + 4 (l / 32) + v % 4,
+// column l % 32.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kMxTileRows = 32;
+constexpr int kMxK = 16;
+constexpr int kMxChunk = TAL_MATRIX_CHUNK;
+constexpr int kMxWaves = TAL_MATRIX_GROUP_TILES;
+constexpr int kMxThreads = 64 * kMxWaves;
+constexpr int kMxStripC4 = 32;                                   // 4-column groups of a strip (128 columns)
+constexpr int kMxStage = kMxChunk * kMxStripC4 / kMxThreads;     // 8-B staging loads per thread and chunk
+constexpr int kMxHeader = 16;
+constexpr int kMxATile = 256;                                    // words of one A tile: 64 lanes x 8 bf16
+static_assert(kMxChunk * kMxStripC4 % kMxThreads == 0, "a chunk is a whole number of loads per thread");
+static_assert(kMxChunk <= TAL_MATRIX_PAD, "a slot is one byte and 0xFF marks padding");
+static_assert(kMxChunk % kMxK == 0 && (kMxChunk & (kMxChunk - 1)) == 0, "chunk: whole k-blocks, a power of two");
+
+typedef __bf16 mx_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float mx_f32x16 __attribute__((ext_vector_type(16)));
+
+// K3m's device code is compiled without the packed fp32 instructions.  Its only fp32 VALU work is
+// the epilogue's scale - 4 multiplies per stored 8 B, which the vectorizer would pair into two
+// v_pk_mul_f32 with an op_sel broadcast of the scale - and the values it produces are the ones the
+// per-element finite test and the chain fallback decide on.  The packed form saves two VALU
+// instructions per stored row and nothing in the k-loop, so the plain v_mul_f32 is kept and the new
+// mode's results depend on no packed operand form.  Everything this code inlines (Io<uint16_t>,
+// first1t / next1t in FMA form) is scalar fp32 or integer code, so the attribute changes only that
+// multiply.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TAL_MX_DEVICE __attribute__((target("no-packed-fp32-ops")))
+#else
+#define TAL_MX_DEVICE
+#endif
+
+// The blob's arrays as device pointers (wave-uniform ones are read through the constant space).
+struct MxPlan {
+  const int32_t* grp_tile_ptr;
+  const int32_t* grp_chunk_ptr;
+  const int32_t* chunk_src_ptr;
+  const int32_t* src_row;
+  const int32_t* tile_kb_ptr;
+  const int32_t* kb_ptr;
+  const int32_t* tile_info;
+  const float* tile_w;
+  const int32_t* kb_slots;
+  const u32x4* a_tiles;
+  const int32_t* row_ptr;
+  const int32_t* col;
+  const float* w;
+  const int32_t* out_row;
+};
+
+// One output element as tal_agg_bf16's TAL_MODE_FMA chain over operands q0 .. q1-1 of the CSR:
+// the columns no strip takes and every element the matrix cores left non-finite.
+__device__ __noinline__ TAL_MX_DEVICE float mx_chain(const uint16_t* pin, int64_t ld_in, const int32_t* col, const float* w,
+                                       int q0, int q1, int64_t e) {
+  float acc = first1t<uint16_t, false>(w[q0], Io<uint16_t>::ld1(pin + static_cast<int64_t>(col[q0]) * ld_in, e));
+  for (int q = q0 + 1; q < q1; ++q)
+    acc = next1t<uint16_t, false>(acc, w[q], Io<uint16_t>::ld1(pin + static_cast<int64_t>(col[q]) * ld_in, e));
+  return acc;
+}
+
+__device__ __forceinline__ bool mx_finite(float v) { return __builtin_fabsf(v) <= 3.402823466e38f; }  // false for NaN
+
+__global__ __launch_bounds__(kMxThreads) TAL_MX_DEVICE void k_round_matrix(const uint16_t* pin, int64_t ld_in, uint16_t* pout,
+                                                             int64_t ld_out, int64_t n4, MxPlan p) {
+  __shared__ u32x2 s_x[2][kMxChunk * kMxStripC4];  // two chunks: slot s, 4-column group c at [s * 32 + c]
+  const int g = blockIdx.y;
+  const int64_t c0 = static_cast<int64_t>(blockIdx.x) * kMxStripC4;  // the strip's first 4-column group
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, half = lane >> 5, cg = lane & 31;
+  const ConstI32 grp_tile_ptr = (ConstI32)p.grp_tile_ptr, grp_chunk_ptr = (ConstI32)p.grp_chunk_ptr;
+  const ConstI32 chunk_src_ptr = (ConstI32)p.chunk_src_ptr, kb_ptr = (ConstI32)p.kb_ptr;
+  const ConstI32 kb_slots = (ConstI32)p.kb_slots, tile_info = (ConstI32)p.tile_info;
+  const int t0 = grp_tile_ptr[g], ch0 = grp_chunk_ptr[g], nch = grp_chunk_ptr[g + 1] - ch0;
+  const bool has_tile = wave < grp_tile_ptr[g + 1] - t0;  // a wavefront without a tile only stages
+  const int tile = t0 + wave;
+  const int kbp = has_tile ? ((ConstI32)p.tile_kb_ptr)[tile] : 0;
+
+  u32x2 st[kMxStage];
+  auto load_chunk = [&](int c) {
+    // branch-free, so that the four index loads and then the four data loads are in flight
+    // together: a slot past the chunk's sources or a column past the round re-reads the chunk's
+    // last source / the round's last 4-column group (in bounds, the same cache lines) and is zeroed
+    const int s0 = chunk_src_ptr[ch0 + c], ns = chunk_src_ptr[ch0 + c + 1] - s0;
+    int32_t row[kMxStage];
+#pragma unroll
+    for (int i = 0; i < kMxStage; ++i)
+      row[i] = p.src_row[s0 + min(static_cast<int>(threadIdx.x + i * kMxThreads) / kMxStripC4, ns - 1)];
+#pragma unroll
+    for (int i = 0; i < kMxStage; ++i) {
+      const int idx = threadIdx.x + i * kMxThreads, s = idx / kMxStripC4, c4 = idx % kMxStripC4;
+      const u32x2 v = Io<uint16_t>::ld_raw(pin + static_cast<int64_t>(row[i]) * ld_in, std::min<int64_t>(c0 + c4, n4 - 1));
+      st[i] = s < ns && c0 + c4 < n4 ? v : u32x2{0u, 0u};
+    }
+  };
+  auto store_chunk = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < kMxStage; ++i) s_x[buf][threadIdx.x + i * kMxThreads] = st[i];
+  };
+
+  mx_f32x16 acc[4] = {};
+  auto multiply = [&](int buf, int c) {
+    const int kb1 = kb_ptr[kbp + c + 1];
+    for (int kb = kb_ptr[kbp + c]; kb < kb1; ++kb) {
+      // the k-block's 16 slot bytes are wave-uniform; a lane's eight are the half its k belong to
+      const uint32_t sl_lo = half ? kb_slots[4 * kb + 2] : kb_slots[4 * kb];
+      const uint32_t sl_hi = half ? kb_slots[4 * kb + 3] : kb_slots[4 * kb + 1];
+      const u32x4 a = p.a_tiles[static_cast<int64_t>(kb) * 64 + lane];
+      u32x2 x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t s = ((j < 4 ? sl_lo : sl_hi) >> (8 * (j & 3))) & 0xffu;
+        // a padding slot: B = 0 from registers (its read, of an LDS slot that always holds data
+        // or zeros, is dropped: no branch in the loop)
+        const u32x2 v = s_x[buf][(s & (kMxChunk - 1)) * kMxStripC4 + cg];
+        x[j] = s != TAL_MATRIX_PAD ? v : u32x2{0u, 0u};
+      }
+      u32x4 b[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {  // k = 2q (low half) and 2q + 1 (high half) of each column
+        b[0][q] = __builtin_amdgcn_perm(x[2 * q + 1].x, x[2 * q].x, 0x05040100u);
+        b[1][q] = __builtin_amdgcn_perm(x[2 * q + 1].x, x[2 * q].x, 0x07060302u);
+        b[2][q] = __builtin_amdgcn_perm(x[2 * q + 1].y, x[2 * q].y, 0x05040100u);
+        b[3][q] = __builtin_amdgcn_perm(x[2 * q + 1].y, x[2 * q].y, 0x07060302u);
+      }
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4)
+        acc[c4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mx_bf16x8, a),
+                                                          __builtin_bit_cast(mx_bf16x8, b[c4]), acc[c4], 0, 0, 0);
+    }
+  };
+
+  load_chunk(0);
+  store_chunk(0);
+  __syncthreads();
+  for (int c = 0; c < nch; ++c) {
+    // chunk c + 1 goes into the buffer chunk c - 1 was multiplied from: every wavefront left it
+    // before the barrier that ended the previous pass
+    if (c + 1 < nch) load_chunk(c + 1);
+    if (has_tile) multiply(c & 1, c);
+    if (c + 1 < nch) store_chunk((c + 1) & 1);
+    __syncthreads();
+  }
+
+  if (!has_tile || c0 + cg >= n4) return;
+  const int r0 = tile_info[4 * tile], nr = tile_info[4 * tile + 1];
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int i = 8 * (v >> 2) + 4 * half + (v & 3);
+    if (i >= nr) continue;  // rows of the tile beyond the round are never stored
+    const float s = p.tile_w[tile * kMxTileRows + i];
+    float4 o = make_float4(__fmul_rn(acc[0][v], s), __fmul_rn(acc[1][v], s), __fmul_rn(acc[2][v], s),
+                           __fmul_rn(acc[3][v], s));
+    const int r = r0 + i;
+    if (!(mx_finite(o.x) && mx_finite(o.y) && mx_finite(o.z) && mx_finite(o.w))) {
+      // rare and divergent: an inf or NaN source (0 x inf = NaN reaches rows that do not list it)
+      // or an overflow; the element becomes FMA mode's, from the row's own operands
+      const int q0 = p.row_ptr[r], q1 = p.row_ptr[r + 1];
+      const int64_t e = 4 * (c0 + cg);
+      if (!mx_finite(o.x)) o.x = mx_chain(pin, ld_in, p.col, p.w, q0, q1, e);
+      if (!mx_finite(o.y)) o.y = mx_chain(pin, ld_in, p.col, p.w, q0, q1, e + 1);
+      if (!mx_finite(o.z)) o.z = mx_chain(pin, ld_in, p.col, p.w, q0, q1, e + 2);
+      if (!mx_finite(o.w)) o.w = mx_chain(pin, ld_in, p.col, p.w, q0, q1, e + 3);
+    }
+    Io<uint16_t>::st(pout + static_cast<int64_t>(p.out_row[r]) * ld_out, c0 + cg, o);
+  }
+}
+
+// Columns e0 .. n-1 of every row by the chain: the n % 4 tail, or the whole round (e0 = 0) for
+// pools the 8-B loads cannot take.  One thread per element, a row's columns on consecutive lanes.
+__global__ __launch_bounds__(kBlock) TAL_MX_DEVICE void k_round_matrix_chain(const uint16_t* pin, int64_t ld_in, uint16_t* pout,
+                                                               int64_t ld_out, int64_t e0, int64_t n, int32_t rows,
+                                                               MxPlan p) {
+  const int64_t nc = n - e0, idx = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (idx >= nc * rows) return;
+  const int r = static_cast<int>(idx / nc);
+  const int64_t e = e0 + idx % nc;
+  Io<uint16_t>::st1(pout + static_cast<int64_t>(p.out_row[r]) * ld_out, e,
+                    mx_chain(pin, ld_in, p.col, p.w, p.row_ptr[r], p.row_ptr[r + 1], e));
+}
+
+MxPlan mx_view(const int32_t* plan, const tal_matrix_plan_info& in) {
+  MxPlan v;
+  v.grp_tile_ptr = plan + in.off_grp_tile_ptr;
+  v.grp_chunk_ptr = plan + in.off_grp_chunk_ptr;
+  v.chunk_src_ptr = plan + in.off_chunk_src_ptr;
+  v.src_row = plan + in.off_src_row;
+  v.tile_kb_ptr = plan + in.off_tile_kb_ptr;
+  v.kb_ptr = plan + in.off_kb_ptr;
+  v.tile_info = plan + in.off_tile_info;
+  v.tile_w = reinterpret_cast<const float*>(plan + in.off_tile_w);
+  v.kb_slots = plan + in.off_kb_slots;
+  v.a_tiles = reinterpret_cast<const u32x4*>(plan + in.off_a_tiles);
+  v.row_ptr = plan + in.off_row_ptr;
+  v.col = plan + in.off_col;
+  v.w = reinterpret_cast<const float*>(plan + in.off_w);
+  v.out_row = plan + in.off_out_row;
+  return v;
+}
+
+int32_t launch_round_matrix(const uint16_t* pin, int64_t ld_in, uint16_t* pout, int64_t ld_out, int64_t n,
+                            const int32_t* plan, const tal_matrix_plan_info& in, hipStream_t s) {
+  const MxPlan v = mx_view(plan, in);
+  const bool vec = ((reinterpret_cast<uintptr_t>(pin) | reinterpret_cast<uintptr_t>(pout)) & 7u) == 0 &&
+                   ld_in % 4 == 0 && ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(plan) & 15u) == 0;
+  const int64_t n4 = vec ? n / 4 : 0;
+  if (n4 > 0) {
+    const int64_t strips = (n4 + kMxStripC4 - 1) / kMxStripC4;
+    if (strips > 0x7fffffffLL || in.n_groups > 65535) return fail(TAL_ERR_INVALID, "matrix round: grid too large");
+    const dim3 grid(static_cast<unsigned>(strips), static_cast<unsigned>(in.n_groups));
+    k_round_matrix<<<grid, kMxThreads, 0, s>>>(pin, ld_in, pout, ld_out, n4, v);
+    if (int32_t rc = check_launch("matrix round kernel")) return rc;
+  }
+  if (4 * n4 < n) {
+    const int64_t blocks = ((n - 4 * n4) * in.rows + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "matrix round (chain columns): grid too large");
+    k_round_matrix_chain<<<static_cast<unsigned>(blocks), kBlock, 0, s>>>(pin, ld_in, pout, ld_out, 4 * n4, n, in.rows, v);
+    return check_launch("matrix round kernel (chain columns)");
+  }
+  return TAL_OK;
+}
+
+// fp32 -> bf16 bits, nearest even (host; NaN keeps a quiet payload)
+uint16_t mx_bf16_bits(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40u);
+  return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+float mx_bf16_value(uint16_t b) {
+  const uint32_t u = static_cast<uint32_t>(b) << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+// fp32 w as three bf16 planes, each the nearest-even rounding of what the planes before it left:
+// the differences are exact in fp32, so the planes sum to w exactly for normal w.  A weight whose
+// first plane is not finite stays in that plane alone (the output is then non-finite and the
+// chain recomputes it).
+void mx_planes(float w, uint16_t out[3]) {
+  out[0] = mx_bf16_bits(w);
+  out[1] = out[2] = 0;
+  const float w1 = mx_bf16_value(out[0]);
+  if (!std::isfinite(w1)) return;
+  const float r1 = w - w1;
+  out[1] = mx_bf16_bits(r1);
+  out[2] = mx_bf16_bits(r1 - mx_bf16_value(out[1]));
+}
+
+// The arrays of a matrix plan as they are built, in blob order.
+struct MxBuild {
+  std::vector<int32_t> grp_tile_ptr{0}, grp_chunk_ptr{0}, chunk_src_ptr{0}, src_row, tile_kb_ptr, kb_ptr, tile_info,
+      tile_w, kb_slots, a_tiles;
+  int32_t kblocks() const { return static_cast<int32_t>(kb_slots.size() / 4); }
+};
+
+// One row tile (rows r0 .. r0+nr-1) of a group whose ascending distinct sources are `srcs`.
+void mx_encode_tile(const Csr& c, int32_t r0, int32_t nr, const std::vector<int32_t>& srcs, int32_t n_chunks,
+                    std::vector<int32_t>* occ_count, MxBuild* b) {
+  // a k entry is a (source index, occurrence within its row) pair: a row may list a source twice
+  auto src_of = [&](int32_t row) { return static_cast<int32_t>(std::lower_bound(srcs.begin(), srcs.end(), row) - srcs.begin()); };
+  std::vector<int64_t> key(static_cast<size_t>(c.ops(r0, nr)));
+  bool uniform = true;
+  const int32_t k_first = c.row_ptr[r0];
+  for (int32_t r = r0; r < r0 + nr; ++r) {
+    for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) {
+      const int32_t s = src_of(c.col[k]);
+      key[k - k_first] = static_cast<int64_t>(s) << 32 | static_cast<uint32_t>((*occ_count)[s]++);
+      uniform = uniform && f32_bits(c.w[k]) == f32_bits(c.w[c.row_ptr[r]]);
+    }
+    for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) (*occ_count)[src_of(c.col[k])] = 0;
+  }
+  std::vector<int64_t> ent(key);
+  std::sort(ent.begin(), ent.end());
+  ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
+  const int32_t ne = static_cast<int32_t>(ent.size());
+  // the tile's dense weights [row][entry] as the A planes, 0 where a row does not list the entry
+  const int planes = uniform ? 1 : 3;
+  std::vector<uint16_t> wt(static_cast<size_t>(nr) * ne * 3, 0);
+  for (int32_t r = r0; r < r0 + nr; ++r)
+    for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) {
+      const int32_t j = static_cast<int32_t>(std::lower_bound(ent.begin(), ent.end(), key[k - k_first]) - ent.begin());
+      uint16_t* pl = &wt[(static_cast<size_t>(r - r0) * ne + j) * 3];
+      if (uniform) pl[0] = 0x3f80;  // 1.0: the row's weight scales the accumulator in the epilogue
+      else mx_planes(static_cast<float>(c.w[k]), pl);
+    }
+  b->tile_kb_ptr.push_back(static_cast<int32_t>(b->kb_ptr.size()));
+  int32_t ja = 0;
+  for (int32_t ch = 0; ch < n_chunks; ++ch) {
+    b->kb_ptr.push_back(b->kblocks());
+    int32_t jb = ja;
+    while (jb < ne && (ent[jb] >> 32) / kMxChunk == ch) ++jb;  // the entries whose source is in chunk ch
+    for (int pl = 0; pl < planes; ++pl)
+      for (int32_t j0 = ja; j0 < jb; j0 += kMxK) {
+        int32_t a[kMxATile] = {0};
+        bool any = false;
+        for (int lane = 0; lane < 64; ++lane)
+          for (int u = 0; u < 8; ++u) {
+            const int32_t i = lane % 32, j = j0 + 8 * (lane / 32) + u;
+            const uint32_t v = i < nr && j < jb ? wt[(static_cast<size_t>(i) * ne + j) * 3 + pl] : 0u;
+            any = any || v != 0;
+            a[lane * 4 + u / 2] |= static_cast<int32_t>(v << (16 * (u % 2)));
+          }
+        if (pl > 0 && !any) continue;  // a plane that is all zero here is no k-block
+        uint8_t slots[kMxK];
+        for (int k = 0; k < kMxK; ++k)
+          slots[k] = j0 + k < jb ? static_cast<uint8_t>((ent[j0 + k] >> 32) % kMxChunk) : TAL_MATRIX_PAD;
+        int32_t sw[4];
+        memcpy(sw, slots, sizeof(sw));
+        b->kb_slots.insert(b->kb_slots.end(), sw, sw + 4);
+        b->a_tiles.insert(b->a_tiles.end(), a, a + kMxATile);
+      }
+    ja = jb;
+  }
+  b->kb_ptr.push_back(b->kblocks());
+  const int32_t ti[4] = {r0, nr, planes, 0};
+  b->tile_info.insert(b->tile_info.end(), ti, ti + 4);
+  for (int32_t i = 0; i < kMxTileRows; ++i)
+    b->tile_w.push_back(i >= nr ? 0 : uniform ? f32_bits(c.w[c.row_ptr[r0 + i]]) : f32_bits(1.0));
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t tal_matrix_plan_words(int32_t rows, int64_t nnz) {
+  if (rows < 0 || nnz < 0) return 0;
+  // tiles T, groups <= T, staged sources <= nnz, chunks <= nnz + T, k-blocks <= 3 nnz (each holds
+  // an operand), a tile's k-block ranges <= its group's chunks + 1
+  const int64_t t = (static_cast<int64_t>(rows) + kMxTileRows - 1) / kMxTileRows;
+  return kMxHeader + 2 * (t + 1) + (nnz + t + 1) + nnz + t + t * (nnz + 2) + 4 * t + kMxTileRows * t +
+         3 * nnz * (4 + kMxATile) + 4 + (static_cast<int64_t>(rows) + 1) + 2 * nnz + rows;
+}
+
+int32_t tal_matrix_plan_build(int32_t rows, const int32_t* row_ptr_host, const int32_t* col_host,
+                              const double* w_host, const int32_t* out_row_host, int32_t* plan_host,
+                              int64_t capacity_words, tal_matrix_plan_info* info) {
+  const std::string fn("tal_matrix_plan_build");
+  if (!info) return fail(TAL_ERR_INVALID, fn + ": null info");
+  Csr c{rows, row_ptr_host, col_host, w_host, out_row_host};
+  if (int32_t rc = check_csr(fn.c_str(), &c)) return rc;
+  const int32_t nnz = static_cast<int32_t>(c.nnz());
+  int32_t max_row = c.max_col;
+  std::vector<int32_t> outs(out_row_host, out_row_host + rows);
+  for (int r = 0; r < rows; ++r) {
+    if (out_row_host[r] < 0) return fail(TAL_ERR_INVALID, fn + ": negative out_row");
+    max_row = std::max(max_row, out_row_host[r]);
+  }
+  std::sort(outs.begin(), outs.end());
+  if (std::adjacent_find(outs.begin(), outs.end()) != outs.end())
+    return fail(TAL_ERR_INVALID, fn + ": an out_row is listed twice");
+
+  MxBuild b;
+  std::vector<int32_t> occ_count;
+  const int32_t n_tiles = (rows + kMxTileRows - 1) / kMxTileRows;
+  for (int32_t t0 = 0; t0 < n_tiles; t0 += kMxWaves) {
+    const int32_t t1 = std::min(n_tiles, t0 + kMxWaves), ra = t0 * kMxTileRows, rb = std::min(rows, t1 * kMxTileRows);
+    std::vector<int32_t> srcs(col_host + row_ptr_host[ra], col_host + row_ptr_host[rb]);
+    std::sort(srcs.begin(), srcs.end());
+    srcs.erase(std::unique(srcs.begin(), srcs.end()), srcs.end());
+    const int32_t ns = static_cast<int32_t>(srcs.size()), n_chunks = (ns + kMxChunk - 1) / kMxChunk;
+    for (int32_t ch = 0; ch < n_chunks; ++ch)
+      b.chunk_src_ptr.push_back(static_cast<int32_t>(b.src_row.size()) + std::min(ns, (ch + 1) * kMxChunk));
+    b.src_row.insert(b.src_row.end(), srcs.begin(), srcs.end());
+    occ_count.assign(srcs.size(), 0);
+    for (int32_t t = t0; t < t1; ++t)
+      mx_encode_tile(c, t * kMxTileRows, std::min(kMxTileRows, rows - t * kMxTileRows), srcs, n_chunks, &occ_count, &b);
+    b.grp_tile_ptr.push_back(t1);
+    b.grp_chunk_ptr.push_back(static_cast<int32_t>(b.chunk_src_ptr.size()) - 1);
+  }
+
+  memset(info, 0, sizeof(*info));
+  info->rows = rows;
+  info->nnz = nnz;
+  info->n_groups = static_cast<int32_t>(b.grp_tile_ptr.size()) - 1;
+  info->n_tiles = n_tiles;
+  info->n_chunks = static_cast<int32_t>(b.chunk_src_ptr.size()) - 1;
+  info->n_kblocks = b.kblocks();
+  info->n_src = static_cast<int32_t>(b.src_row.size());
+  info->max_row = max_row;
+  int64_t off = kMxHeader;
+  auto place = [&](int32_t* field, size_t words, int64_t align = 1) {
+    off = (off + align - 1) / align * align;
+    *field = static_cast<int32_t>(off);
+    off += static_cast<int64_t>(words);
+  };
+  place(&info->off_grp_tile_ptr, b.grp_tile_ptr.size());
+  place(&info->off_grp_chunk_ptr, b.grp_chunk_ptr.size());
+  place(&info->off_chunk_src_ptr, b.chunk_src_ptr.size());
+  place(&info->off_src_row, b.src_row.size());
+  place(&info->off_tile_kb_ptr, b.tile_kb_ptr.size());
+  place(&info->off_kb_ptr, b.kb_ptr.size());
+  place(&info->off_tile_info, b.tile_info.size());
+  place(&info->off_tile_w, b.tile_w.size());
+  place(&info->off_kb_slots, b.kb_slots.size());
+  place(&info->off_a_tiles, b.a_tiles.size(), 4);
+  place(&info->off_row_ptr, static_cast<size_t>(rows) + 1);
+  place(&info->off_col, static_cast<size_t>(nnz));
+  place(&info->off_w, static_cast<size_t>(nnz));
+  place(&info->off_out_row, static_cast<size_t>(rows));
+  info->words = off;
+  if (off > 0x7fffffffLL) return fail(TAL_ERR_CAPACITY, fn + ": the plan passes 2^31 words");
+  if (!plan_host || capacity_words < info->words)
+    return fail(TAL_ERR_CAPACITY, fn + ": plan buffer too small (info->words)");
+  std::fill(plan_host, plan_host + info->words, 0);
+  const int32_t header[kMxHeader] = {rows, nnz, info->n_groups, n_tiles, info->n_chunks, info->n_kblocks, info->n_src,
+                                     max_row, static_cast<int32_t>(info->words)};
+  memcpy(plan_host, header, sizeof(header));
+  auto put = [&](int32_t at, const std::vector<int32_t>& a) { std::copy(a.begin(), a.end(), plan_host + at); };
+  put(info->off_grp_tile_ptr, b.grp_tile_ptr);
+  put(info->off_grp_chunk_ptr, b.grp_chunk_ptr);
+  put(info->off_chunk_src_ptr, b.chunk_src_ptr);
+  put(info->off_src_row, b.src_row);
+  put(info->off_tile_kb_ptr, b.tile_kb_ptr);
+  put(info->off_kb_ptr, b.kb_ptr);
+  put(info->off_tile_info, b.tile_info);
+  put(info->off_tile_w, b.tile_w);
+  put(info->off_kb_slots, b.kb_slots);
+  put(info->off_a_tiles, b.a_tiles);
+  std::copy(row_ptr_host, row_ptr_host + rows + 1, plan_host + info->off_row_ptr);
+  std::copy(col_host, col_host + nnz, plan_host + info->off_col);
+  for (int32_t k = 0; k < nnz; ++k) plan_host[info->off_w + k] = f32_bits(w_host[k]);
+  std::copy(out_row_host, out_row_host + rows, plan_host + info->off_out_row);
+  g_err.clear();
+  return TAL_OK;
+}
+
+int32_t tal_agg_round_matrix_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                  int64_t pool_rows, int64_t n, const int32_t* plan_dev,
+                                  const tal_matrix_plan_info* info, void* stream) {
+  const std::string fn("tal_agg_round_matrix_bf16");
+  if (!pool_in || !pool_out) return fail(TAL_ERR_INVALID, fn + ": null pool");
+  if (!plan_dev) return fail(TAL_ERR_INVALID, fn + ": null plan_dev");
+  if (!info) return fail(TAL_ERR_INVALID, fn + ": null info");
+  if (pool_out == pool_in) return fail(TAL_ERR_INVALID, fn + ": pool_out == pool_in (the round is a snapshot, out of place)");
+  if (info->rows <= 0 || info->nnz < info->rows || info->n_groups <= 0 || info->n_tiles < info->n_groups ||
+      info->n_chunks < info->n_groups || info->n_kblocks < info->n_tiles || info->max_row < 0 ||
+      info->off_grp_tile_ptr != kMxHeader || info->off_a_tiles % 4 != 0 || info->words <= info->off_out_row)
+    return fail(TAL_ERR_INVALID, fn + ": info is not a matrix plan's");
+  if (n < 0) return fail(TAL_ERR_INVALID, fn + ": n < 0");
+  if (ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, fn + ": ld < n");
+  if (info->max_row >= pool_rows)
+    return fail(TAL_ERR_INVALID, fn + ": plan row " + std::to_string(info->max_row) + " >= pool_rows");
+  if (n == 0) { g_err.clear(); return TAL_OK; }
+  return launch_round_matrix(pool_in, ld_in, pool_out, ld_out, n, plan_dev, *info, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

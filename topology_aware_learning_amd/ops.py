@@ -15,11 +15,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import RoundPlanInfo, SeqPlanInfo, check
+from ._lib import MatrixPlanInfo, RoundPlanInfo, SeqPlanInfo, check
 from .arena import SEG, SEGMENTS, Segment, segment_of
 
 MODE_EXACT = _lib.TAL_MODE_EXACT
 MODE_FMA = _lib.TAL_MODE_FMA
+MODE_MATRIX = _lib.TAL_MODE_MATRIX  # bf16 pools only: rounds on the matrix cores (K3m, a MatrixPlan)
 _F32, _B16, _I64 = SEGMENTS
 
 
@@ -913,7 +914,12 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     scratch pool.  A round with a row of more distinct sources than one LDS tile holds (e.g.
     `unweighted_fl` over > ~620 clients) gets a streamed plan - the fp32 streamed kernel, or for
     bf16 pools the wide-row kernel - or, rows out of reference order, one K1 call per row
-    (RowCallPlan)."""
+    (RowCallPlan).  mode=MODE_MATRIX (opt-in, bf16 pools only: ValueError otherwise) is none of
+    this: the round's MatrixPlan (build_matrix_plan), whatever its graph."""
+    if mode == MODE_MATRIX:
+        if not bf16:
+            raise ValueError("MODE_MATRIX runs bf16 pools only (tal_agg.h K3m)")
+        return build_matrix_plan(row_ptr, col, w, out_row)
     try:
         for name in ("clique128", "clique", "wclique128", "wclique"):
             gate = _CLIQUE_VARIANTS[name][1]
@@ -1021,7 +1027,16 @@ def round_pool(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[
 def _round(seg: Segment, pool_in, pool_out, plan, n, mode, stream) -> torch.Tensor:
     """The round by the plan's kind: a CliquePlan runs K3c / K3c1 and its rest plan (on int64
     pools, which the clique kernels do not take, its `full` plan), a RowCallPlan one K1 call per
-    row, any other plan the round kernel."""
+    row, any other plan the round kernel.  A MatrixPlan runs K3m on bf16 pools and its `full` plan
+    on int64 ones; MODE_MATRIX with any other plan is refused (there is no quiet FMA round)."""
+    if isinstance(plan, MatrixPlan):
+        if seg is _B16:
+            return round_matrix_bf16(pool_in, pool_out, plan, n, stream)
+        if seg is not _I64:
+            raise ValueError("a MatrixPlan runs bf16 pools (int64 ones through its full plan), not fp32")
+        plan = plan.full
+    elif mode == MODE_MATRIX and seg.takes_mode:
+        raise ValueError("MODE_MATRIX takes a MatrixPlan (build_matrix_plan)")
     if isinstance(plan, CliquePlan):
         if seg is not _I64:
             return _round_clique(seg, pool_in, pool_out, plan, n, mode, stream)
@@ -1174,6 +1189,98 @@ def round_seq_bf16(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, m
 def round_seq_i64(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, stream=None) -> torch.Tensor:
     """K3q on an int64 pool (chains as agg_i64; later rows read the truncated integer)."""
     return _round_seq(_I64, pool, plan, n, MODE_EXACT, stream)
+
+
+# ------------------------------------------------------------------------------------------
+# K3m: a round on bf16 pools on the matrix cores (MODE_MATRIX)
+# ------------------------------------------------------------------------------------------
+MATRIX_CHUNK = 64        # TAL_MATRIX_CHUNK: sources per LDS chunk of k_round_matrix
+MATRIX_GROUP_TILES = 8   # TAL_MATRIX_GROUP_TILES: row tiles (of 32 rows) per group
+MATRIX_PAD = 0xFF        # TAL_MATRIX_PAD: the slot byte of a k-block's padding entries
+MATRIX_PLAN_ONE_PASS = 1 << 24  # int32 words (64 MiB): build_matrix_plan's one-pass limit
+
+
+@dataclass
+class MatrixPlan:
+    """A snapshot round for the matrix cores (tal_agg.h K3m): OUT = W . X on bf16 pools, opt-in
+    (MODE_MATRIX) and not bit-comparable to the other modes.  `full` is a regular plan over all
+    rows for the int64 segment, as a CliquePlan's."""
+    info: MatrixPlanInfo
+    host: np.ndarray           # int32 blob
+    full: object
+    device: Optional[torch.Tensor] = None
+    rows: int = 0
+    nnz: int = 0
+    tuned_ms: Optional[float] = None
+    candidates: Optional[list] = None
+    spec: Optional[dict] = None
+
+    @property
+    def single_group(self) -> bool:
+        return False  # out of place always
+
+    def staged_rows(self) -> int:
+        """Source rows read from HBM per column strip (sum over groups)."""
+        return int(self.info.n_src)
+
+    def to(self, device) -> "MatrixPlan":
+        self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
+        self.full.to(device)
+        return self
+
+
+def build_matrix_plan(row_ptr, col, w, out_row) -> MatrixPlan:
+    """The K3m plan of a round given as CSR (row r: operands col[row_ptr[r]:row_ptr[r+1]] with
+    float64 weights w, written to pool row out_row[r]).  Any operand count and order; neither
+    the rows nor the sources of a round are bounded."""
+    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
+    rows = len(out_row)
+    L = _lib.load()
+    P32 = ctypes.POINTER(ctypes.c_int32)
+    args = (rows, row_ptr.ctypes.data_as(P32), col.ctypes.data_as(P32),
+            w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out_row.ctypes.data_as(P32))
+    info = MatrixPlanInfo()
+    # one planner pass into a buffer of tal_matrix_plan_words' upper bound where that is small (it
+    # allows 3 k-blocks of 1 KiB per operand: 780 words each); past MATRIX_PLAN_ONE_PASS words the
+    # capacity protocol instead - a pass without a buffer reports the words needed, a second one
+    # fills them: twice the planner's host time (the 700-client round: 490,000 operands), once per plan
+    size = int(L.tal_matrix_plan_words(rows, len(col)))
+    if size > MATRIX_PLAN_ONE_PASS:
+        rc = L.tal_matrix_plan_build(*args, None, 0, ctypes.byref(info))
+        if rc != _lib.TAL_ERR_CAPACITY or info.words <= 0:
+            check(rc)
+        size = int(info.words)
+    blob = np.zeros(size, dtype=np.int32)
+    check(L.tal_matrix_plan_build(*args, blob.ctypes.data_as(P32), size, ctypes.byref(info)))
+    blob = blob[: info.words].copy()
+    full = default_plan(row_ptr, col, w, out_row, bf16=True)
+    if isinstance(full, CliquePlan):
+        full = full.full
+    return MatrixPlan(info=info, host=blob, full=full, rows=rows, nnz=len(col), spec={"matrix": 1})
+
+
+def round_matrix_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: MatrixPlan, n: Optional[int] = None,
+                      stream=None) -> torch.Tensor:
+    """K3m on [models, ld] bf16 pools, out of place: pool_out[out_row[r]] = sum_k fp32(w_k) *
+    pool_in[col_k] on the matrix cores, fp32 accumulation, one bf16 rounding at the store; error
+    bound in tal_agg.h.  Pools that miss the 8-B row alignment and the n % 4 tail run the ordered
+    FMA chain instead, as does every element the matrix cores leave non-finite."""
+    if not isinstance(plan, MatrixPlan):
+        raise TypeError("a matrix round takes a MatrixPlan (build_matrix_plan)")
+    _check_pools(_B16, pool_in, pool_out, what="matrix")
+    n = pool_in.shape[1] if n is None else int(n)
+    if not 0 <= n <= min(pool_in.shape[1], pool_out.shape[1]):
+        raise ValueError(f"n = {n} outside the pools' columns")
+    pool_rows = min(pool_in.shape[0], pool_out.shape[0])
+    if plan.info.max_row >= pool_rows:  # (the C entry refuses it too: TAL_ERR_INVALID, no launch)
+        raise ValueError("plan reads or writes a pool row beyond the pools")
+    if plan.device is None or plan.device.device != pool_in.device:
+        plan.to(pool_in.device)
+    check(_lib.load().tal_agg_round_matrix_bf16(
+        ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
+        pool_out.stride(0), pool_rows, n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info),
+        _stream(pool_in.device, stream)))
+    return pool_out
 
 
 # ------------------------------------------------------------------------------------------

@@ -15,6 +15,11 @@ its own round order-dependent; ``sequential=True`` reproduces its single-thread 
 in place, where ``ops.SEQ_DEFAULT`` has the kernel on and the round has at most
 ``ops.SEQ_MAX_SRC`` distinct sources, else one K1 call per client (``sequential="calls"``
 always).
+
+``mode=ops.MODE_MATRIX`` (opt-in, bf16 pools without an fp32 segment) runs the b16 segment on
+the matrix cores (K3m, ``ops.MatrixPlan``; a tolerance, not the other modes' bits: tal_agg.h)
+and the int64 segment through the plan's ``full`` regular plan; always out of place (the spare
+or the scratch pool), snapshot rounds only.
 """
 from __future__ import annotations
 
@@ -95,6 +100,9 @@ class RoundExecutor:
     def __init__(self, pool: ModelPool, scratch: Optional[ModelPool] = None, mode: int = ops.MODE_EXACT,
                  placement_trials: int = 4, double_buffer: Optional[bool] = None,
                  carried_rows: Optional[int] = None):
+        if mode == ops.MODE_MATRIX and (pool.layout.n_f32 or not pool.layout.n_b16):
+            raise ValueError("MODE_MATRIX runs bf16 pools: this pool has an fp32 segment or no bf16 one "
+                             "(the matrix round, K3m, exists for bf16 alone)")
         self.pool = pool
         self.scratch = scratch
         self.mode = mode
@@ -180,6 +188,8 @@ class RoundExecutor:
         if len(orders) == 0:
             return
         lay = self.pool.layout
+        if sequential and self.mode == ops.MODE_MATRIX:
+            raise ValueError("MODE_MATRIX has no sequential round: the matrix round is a snapshot, out of place")
         if sequential:
             sp = None
             if sequential != "calls" and self.pool.device.type == "cuda" and \
