@@ -459,16 +459,23 @@ int32_t tal_agg_round_seq_i64(int64_t* pool, int64_t ld, int64_t pool_rows, int6
  *
  * 2^-8 |ref|: the store's one rounding.  3M terms: a weight that is not one per row is split
  * exactly into three bf16 planes w1 = bf16(w), w2 = bf16(w - w1), w3 = bf16(w - w1 - w2) (nearest
- * even; w1 + w2 + w3 == fp32(w) for normal w), each a term of the sum; + 2: the epilogue's scale
- * and slack.  2^-23: one fp32 ulp per step, since the instruction's internal adds are not
- * documented as round-to-nearest.  2^-126 per term: the matrix cores may flush subnormal inputs
- * and outputs.
+ * even), each a term of the sum; + 2: the epilogue's scale and slack.  2^-23: one fp32 ulp per
+ * step, since the instruction's internal adds are not documented as round-to-nearest.  2^-126 per
+ * term: the matrix cores may flush subnormal inputs and outputs.
+ *
+ * The split is exact (w1 + w2 + w3 == w, every plane zero or a normal bf16) for |w| >= 2^-103; a
+ * smaller weight's lower planes would be bf16 subnormals, which cannot hold its bits below 2^-133.
+ * So a row that has such a weight is split as w 2^-e, e = min(0, max(emin + 103, emax - 127)) over
+ * the exponents of its non-zero fp32 weights, and 2^e goes into the row's epilogue scale: the
+ * split stays exact, and the bound holds, unless the non-zero weights of one row span more than
+ * 2^230 - then the smallest of them lose what lies below 2^(e - 133), which the bound does not
+ * cover.
  *
  * Weights.  A row tile (32 consecutive rows of the round) whose rows each carry ONE fp32 weight
  * for all their operands (the unweighted strategy, scale_agg) is "uniform": its A operand holds
  * 1.0 / 0.0 and the row's fp32 weight multiplies the accumulator once in the epilogue.  Any other
  * tile is "general": its k-blocks are emitted once per plane (a plane whose A tile is all zero is
- * left out) and the epilogue scale is 1.0.
+ * left out) and the epilogue scale is 1.0 (2^e for a row with a weight below 2^-103, above).
  *
  * Non-finite values.  0 x inf is NaN on the matrix cores, so a diverged source would poison rows
  * that do not list it.  Every output element that is not finite after the k-loop and the scale is
@@ -496,7 +503,7 @@ int32_t tal_agg_round_seq_i64(int64_t* pool, int64_t ld, int64_t pool_rows, int6
  *   kb_ptr[...]                k-block ranges: tile t visits k-blocks kb_ptr[tile_kb_ptr[t] + c] ..
  *                              kb_ptr[tile_kb_ptr[t] + c + 1] - 1 while chunk c of its group is in LDS
  *   tile_info[n_tiles][4]      {first row of the round, rows (1..32), planes (1 uniform, 3 general), 0}
- *   tile_w[n_tiles][32]        fp32 bits of the epilogue scale of each row (general: 1.0)
+ *   tile_w[n_tiles][32]        fp32 bits of the epilogue scale of each row (general: 1.0, or 2^e)
  *   kb_slots[n_kblocks][4]     16 bytes: the LDS slot (0 .. TAL_MATRIX_CHUNK-1, within the chunk)
  *                              of k = 0..15; TAL_MATRIX_PAD (0xFF) marks a padding slot, whose B
  *                              operand is zero from registers (the kernel reads LDS slot 0xFF %

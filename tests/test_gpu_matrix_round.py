@@ -14,18 +14,26 @@ SENTINEL = 0x4D4D  # bf16 bits no round writes by chance: rows and columns a rou
 
 
 def _dev(bits, dev):
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(torch.bfloat16).to(dev)
+    return torch.from_numpy(np.array(bits).view(np.int16)).view(torch.bfloat16).to(dev)  # (a copy: shared inputs are read-only)
 
 
-def _run(dev, bits, rp, col, w, out_row, n, ld=None, offset=0):
-    """pool_out's bits [rows, ld], SENTINEL where the round did not write; ld defaults to n rounded
-    up to 4 (8-B rows, as a ModelPool's); the pools start `offset` elements into their allocation."""
+def _run(dev, bits, rp, col, w, out_row, n, ld=None, offset=0, ld_out=None, plan=None, stream=None):
+    """pool_out's bits [rows, ld_out], SENTINEL where the round did not write; ld defaults to n rounded
+    up to 4 (8-B rows, as a ModelPool's) and ld_out to ld; the pools start `offset` elements into their
+    allocation.  plan: the round's plan, built here if None; stream: the round's, after the current one."""
     rows, ld = bits.shape[0], ld or -(-bits.shape[1] // 4) * 4
+    ld_out = ld_out or ld
     flat_in = torch.zeros(rows * ld + offset, dtype=torch.bfloat16, device=dev)
-    flat_out = _dev(np.full(rows * ld + offset, SENTINEL, np.uint16), dev)
-    pin, pout = (f[offset:].view(rows, ld) for f in (flat_in, flat_out))
+    flat_out = _dev(np.full(rows * ld_out + offset, SENTINEL, np.uint16), dev)
+    pin, pout = flat_in[offset:].view(rows, ld), flat_out[offset:].view(rows, ld_out)
     pin[:, :bits.shape[1]] = _dev(bits, dev)
-    ops.round_matrix_bf16(pin, pout, ops.build_matrix_plan(rp, col, w, out_row), n)
+    plan = plan or ops.build_matrix_plan(rp, col, w, out_row)
+    if stream is not None:
+        plan.to(dev)
+        stream.wait_stream(torch.cuda.current_stream(dev))
+    ops.round_matrix_bf16(pin, pout, plan, n, stream)
+    if stream is not None:
+        stream.synchronize()
     return pout.cpu().view(torch.int16).numpy().view(np.uint16)
 
 
@@ -80,6 +88,93 @@ def test_non_finite_sources_reach_only_the_rows_that_list_them(cuda, wname):
     assert bad[s, 257] == (wname == "ones")
     assert np.array_equal(got[bad], oracle.f32_to_bf16(fma)[bad])
     assert np.array_equal(got[~lists], got0[~lists])
+
+
+N_BIG = 389  # four strips, the last one partial, and an n % 4 tail
+
+
+@pytest.mark.parametrize("wname", mx.WEIGHTS)
+@pytest.mark.parametrize("gname", mx.BIG_GRAPHS)
+def test_big_round_within_the_bound_and_deterministic(cuda, gname, wname):
+    """Two groups, the first of eight tiles, three to five chunks: the bound, and the same bits from
+    a second run of the same plan, on another stream."""
+    bits, rp, col, w, out_row = mx.bound_case(gname, wname, N_BIG)
+    plan = ops.build_matrix_plan(rp, col, w, out_row)
+    got = _run(cuda, bits, rp, col, w, out_row, N_BIG, plan=plan)
+    again = _run(cuda, bits, rp, col, w, out_row, N_BIG, plan=plan, stream=torch.cuda.Stream(cuda))
+    assert (got[:, N_BIG:] == SENTINEL).all()
+    print("error / bound:", mx.check_bound(got[:, :N_BIG], *mx.reference(bits, rp, col, w)))
+    assert np.array_equal(got, again)
+
+
+@pytest.mark.parametrize("gname,variant", mx.EXACT_CASES)
+def test_exact_sums_bit_for_bit(cuda, gname, variant):
+    """Small integers times powers of two (or short dyadic weights): every partial sum is exact in fp32 in
+    any order, so the store's nearest-even rounding is the only one and the bits are FMA mode's
+    (mx.exact_case).  A dropped, doubled or misplaced operand changes every element it touches."""
+    bits, rp, col, w, out_row, want = mx.exact_case(gname, variant, N_BIG)
+    got = _run(cuda, bits, rp, col, w, out_row, N_BIG)
+    wrong = got[out_row, :N_BIG] != want
+    assert not wrong.any(), (int(wrong.sum()), np.argwhere(wrong)[:8].tolist())
+
+
+def test_hand_round_with_two_leading_dimensions(cuda):
+    """The hand-made round (sources outside the round, a permuted out_row into a larger pool, repeated
+    sources, a uniform and two general tiles in one group) with ld_in = 400 and ld_out = 392."""
+    bits, rp, col, w, out_row = mx.bound_case("hand", "own", N_BIG)
+    got = _run(cuda, bits, rp, col, w, out_row, N_BIG, ld=400, ld_out=392)
+    assert got.shape == (mx.HAND_POOL_ROWS, 392)
+    print("error / bound:", mx.check_bound(got[out_row, :N_BIG], *mx.reference(bits, rp, col, w)))
+    untouched = np.ones(got.shape, bool)
+    untouched[out_row, :N_BIG] = False
+    assert (got[untouched] == SENTINEL).all()
+    bits, rp, col, w, out_row, want = mx.exact_case("hand", "own", N_BIG)
+    got = _run(cuda, bits, rp, col, w, out_row, N_BIG, ld=400, ld_out=392)
+    assert np.array_equal(got[out_row, :N_BIG], want) and (got[untouched] == SENTINEL).all()
+
+
+def test_huge_weight_is_fma_modes_in_its_rows_and_reaches_no_other(cuda):
+    """3.4e38 is finite in fp32 and infinite as a bf16 plane: times the source's 0 and 2^-120 the matrix
+    cores give NaN and inf in every element of the six rows that list the source, which are therefore
+    FMA mode's (finite) bits; the other rows are bit for bit the round with that weight set to 1.0."""
+    bits, rp, col, w, w1, lists = mx.huge_weight_round(N_BIG)
+    out_row = np.arange(len(rp) - 1, dtype=np.int32)
+    got, got1 = (_run(cuda, bits, rp, col, ww, out_row, N_BIG)[:, :N_BIG] for ww in (w, w1))
+    fma = oracle.round_bf16(bits, rp, col, w, out_row, exact=False)
+    assert lists.sum() == 6 and np.isfinite(oracle.bf16_to_f32(fma[lists][:, 12:])).all()
+    assert np.array_equal(got[lists], fma[lists])
+    assert np.array_equal(got[~lists], got1[~lists])
+    mx.check_bound(got, *mx.reference(bits, rp, col, w))
+
+
+def test_tiny_weights_within_the_unchanged_bound(cuda):
+    """Normal weights of 2^-124 .. 2^-119, whose lower planes would be bf16 subnormals, on inputs around
+    2^100: the header's bound as it stands (the planner scales such rows, tests/test_matrix_plan_host.py)."""
+    bits, rp, col, w, out_row = mx.bound_case("rr40x5", "tiny", N_BIG)
+    got = _run(cuda, bits, rp, col, w, out_row, N_BIG)[:, :N_BIG]
+    ref, bound = mx.reference(bits, rp, col, w)
+    assert (np.abs(ref) > 2.0 ** -40).mean() > 0.99  # outputs far above the subnormals
+    print("error / bound:", mx.check_bound(got, ref, bound))
+
+
+def test_executor_mode_matrix_two_groups(cuda):
+    """RoundExecutor(mode=MODE_MATRIX) on ring300: two groups; b16 within the bound, int64 the oracle's."""
+    rp, col, w = mx.round_csr("ring300", "positive")
+    rows, n = len(rp) - 1, 200
+    orders = [col[rp[r]: rp[r + 1]].tolist() for r in range(rows)]
+    weights = [w[rp[r]: rp[r + 1]].tolist() for r in range(rows)]
+    bits = mx.pool_bits(rows, n, seed=41)
+    counts = np.arange(1000, 1000 + rows, dtype=np.int64).reshape(rows, 1)
+    pool = ModelPool(StateLayout.from_layout([("w", (n,), "bfloat16"), ("count", (), "int64")]), rows, cuda)
+    pool.b16[:, :n] = _dev(bits, cuda)
+    pool.i64[:, :1] = torch.from_numpy(counts).to(cuda)
+    ex = RoundExecutor(pool, mode=ops.MODE_MATRIX, placement_trials=1)
+    ex.run(orders, weights)
+    plan = ex.plan(orders, weights, list(range(rows)))
+    assert isinstance(plan, ops.MatrixPlan) and plan.info.n_groups == 2
+    mx.check_bound(pool.b16[:, :n].cpu().view(torch.int16).numpy().view(np.uint16), *mx.reference(bits, rp, col, w))
+    want = oracle.round_i64(counts, rp, col, w, np.arange(rows, dtype=np.int32))
+    assert np.array_equal(pool.i64[:, :1].cpu().numpy(), want)
 
 
 def test_executor_mode_matrix(cuda):

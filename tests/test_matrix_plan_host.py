@@ -113,11 +113,127 @@ def test_plan_decodes_to_the_csr(gname, wname, planes, kblocks, pads):
     assert i.n_kblocks == kblocks if wname == "unweighted" else i.n_kblocks <= kblocks
 
 
-@pytest.mark.parametrize("wname", mx.WEIGHTS)
-@pytest.mark.parametrize("gname", mx.GRAPHS)
+def _kb_counts(p):
+    """Per tile, the k-blocks it visits in each chunk of its group."""
+    i, b = p.info, p.host
+    gt, gc = (b[off: off + i.n_groups + 1] for off in (i.off_grp_tile_ptr, i.off_grp_chunk_ptr))
+    tkb, kbp = b[i.off_tile_kb_ptr: i.off_tile_kb_ptr + i.n_tiles], b[i.off_kb_ptr: i.off_tile_info]
+    return [np.diff(kbp[tkb[t]: tkb[t] + gc[g + 1] - gc[g] + 1]).tolist()
+            for g in range(i.n_groups) for t in range(gt[g], gt[g + 1])]
+
+
+def _csr_weights(rp, col, w):
+    """{(row, source): fp32 weight}, a source a row lists twice summed in float64."""
+    want = defaultdict(float)
+    for r in range(len(rp) - 1):
+        for k in range(rp[r], rp[r + 1]):
+            want[r, int(col[k])] += float(np.float32(w[k]))
+    return dict(want)
+
+
+# chunks per group; per tile the k-blocks per chunk (None: not pinned)
+_RING300_KB = [[3, 0, 0, 0, 1], [3, 1, 0, 0, 0], [1, 3, 0, 0, 0], [0, 3, 1, 0, 0], [0, 1, 3, 0, 0], [0, 0, 3, 1, 0],
+               [0, 0, 1, 3, 0], [0, 0, 0, 3, 1], [3], [1]]
+_BIG_PLANS = [
+    # tile t of group 0 lists the 34 sources 32 t - 1 .. 32 t + 32, 33 of them in one chunk and one in
+    # a neighbouring one (tile 0: 0..32, and 299, the 258th source: chunks 0 and 4); group 1 lists 0
+    # and 255..299, 46 sources: tile 8 34 of them (255..288), tile 9 0 and 287..299
+    ("ring300", "unweighted", [5, 1], _RING300_KB),
+    ("ring300", "positive", [5, 1], [[3 * k for k in t] for t in _RING300_KB]),
+    ("rr300x7", "unweighted", [5, 4], None),
+    ("rr300x7", "positive", [5, 4], None),
+    # 300 sources for every row: 4 x 64 + 44, so 4 k-blocks per tile and chunk and 3 in the last
+    ("complete300", "unweighted", [5, 5], [[4, 4, 4, 4, 3]] * 10),
+    ("complete300", "positive", [5, 5], [[12, 12, 12, 12, 9]] * 10),
+    ("hand", "own", [2], [[3, 2], [10, 5], [1, 3]]),
+]
+
+
+@pytest.mark.parametrize("gname,wname,chunks,kblocks", _BIG_PLANS, ids=[f"{g}-{w}" for g, w, _, _ in _BIG_PLANS])
+def test_big_plans_decode_to_the_csr(gname, wname, chunks, kblocks):
+    """Rounds of more than one group and more than two chunks, and the hand-made round (sources outside
+    the round, repeated sources, a uniform and two general tiles in one group): the blob decodes to
+    the CSR exactly, through chunk, source and k-block offsets that do not start at zero."""
+    if gname == "hand":
+        rp, col, w, out_row = mx.hand_round()
+    else:
+        rp, col, w = mx.round_csr(gname, wname)
+        out_row = np.arange(len(rp) - 1, dtype=np.int32)[::-1].copy()
+    p = ops.build_matrix_plan(rp, col, w, out_row)
+    i = p.info
+    assert i.words == len(p.host) <= _lib.load().tal_matrix_plan_words(len(rp) - 1, len(col))
+    assert i.n_groups == len(chunks) == (1 if gname == "hand" else 2)
+    assert np.diff(p.host[i.off_grp_chunk_ptr: i.off_grp_chunk_ptr + i.n_groups + 1]).tolist() == chunks
+    tiles = [3] if gname == "hand" else [8, 2]
+    assert np.diff(p.host[i.off_grp_tile_ptr: i.off_grp_tile_ptr + i.n_groups + 1]).tolist() == tiles
+    got, planes, _ = _decode(p)
+    assert got == _csr_weights(rp, col, w)
+    assert planes == ([1, 3, 3] if gname == "hand" else [1 if wname == "unweighted" else 3] * 10)
+    counts = _kb_counts(p)
+    assert sum(map(sum, counts)) == i.n_kblocks
+    assert [len(c) for c in counts] == [chunks[g] for g, nt in enumerate(tiles) for _ in range(nt)]
+    if kblocks is not None:
+        assert counts == kblocks
+    if gname == "ring300":  # five chunks of 64, 64, 64, 64 and 2 sources, then one of 46
+        assert np.diff(p.host[i.off_chunk_src_ptr: i.off_chunk_src_ptr + 7]).tolist() == [64, 64, 64, 64, 2, 46]
+    if gname == "hand":
+        assert i.n_kblocks == mx.HAND_KBLOCKS and i.n_src == mx.HAND_POOL_ROWS and i.max_row == mx.HAND_POOL_ROWS - 1
+        assert col.max() >= len(rp) - 1 and sorted(out_row) != list(range(len(rp) - 1))
+
+
+def test_two_pass_build_equals_the_one_pass_build():
+    """complete300's size bound passes MATRIX_PLAN_ONE_PASS, so build_matrix_plan asks for the size
+    first; its blob is the one a single pass writes into a buffer of exactly info.words."""
+    rp, col, w = mx.round_csr("complete300", "positive")
+    rows, L = len(rp) - 1, _lib.load()
+    assert L.tal_matrix_plan_words(rows, len(col)) > ops.MATRIX_PLAN_ONE_PASS
+    assert L.tal_matrix_plan_words(rows, len(mx.round_csr("rr300x7", "positive")[1])) <= ops.MATRIX_PLAN_ONE_PASS
+    out_row = np.arange(rows, dtype=np.int32)
+    p = ops.build_matrix_plan(rp, col, w, out_row)
+    P32, info = ctypes.POINTER(ctypes.c_int32), _lib.MatrixPlanInfo()
+    blob = np.full(p.info.words, -1, np.int32)
+    rc = L.tal_matrix_plan_build(rows, rp.ctypes.data_as(P32), col.ctypes.data_as(P32), w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                 out_row.ctypes.data_as(P32), blob.ctypes.data_as(P32), len(blob), ctypes.byref(info))
+    assert rc == _lib.TAL_OK and info.words == p.info.words == len(p.host) and np.array_equal(blob, p.host)
+    assert bytes(info) == bytes(p.info)
+
+
+def test_tiny_weights_split_exactly_into_normal_planes():
+    """Weights of 2^-124 .. 2^-119: split as they are, their second plane is a bf16 subnormal of a few
+    bits and the third is lost (the planes then miss fp32(w) by up to 2^-10.6 of it).  The planner takes
+    a power of two out of such a row into its epilogue scale: the planes are exact and normal."""
+    _, rp, col, w = mx.tiny_weight_round(8)
+    p = ops.build_matrix_plan(rp, col, w, np.arange(len(rp) - 1, dtype=np.int32))
+    got, planes, _ = _decode(p)
+    assert got == _csr_weights(rp, col, w) and planes == [3, 3]
+    i = p.info
+    a = np.abs(oracle.bf16_to_f32(p.host[i.off_a_tiles: i.off_a_tiles + 256 * i.n_kblocks].view(np.uint16)))
+    assert a[a != 0].min() >= 2.0 ** -126
+    tw = p.host[i.off_tile_w: i.off_tile_w + 64].view(np.float32)[: len(rp) - 1]
+    assert (np.frexp(tw)[0] == 0.5).all() and (tw < 2.0 ** -10).all()  # powers of two
+    # a row without such a weight keeps the scale 1.0, and a huge weight its infinite first plane
+    _, rp, col, w = mx.huge_weight_round(8)[:4]
+    p = ops.build_matrix_plan(rp, col, w, np.arange(len(rp) - 1, dtype=np.int32))
+    i = p.info
+    assert (p.host[i.off_tile_w: i.off_tile_w + 64].view(np.float32)[: len(rp) - 1] == 1.0).all()
+    assert np.isinf(oracle.bf16_to_f32(p.host[i.off_a_tiles: i.off_a_tiles + 256 * i.n_kblocks].view(np.uint16))).sum() == 6
+
+
+@pytest.mark.parametrize("gname,wname", [(g, w) for g in mx.GRAPHS for w in mx.WEIGHTS] + list(mx.NEW_BOUND_CASES))
 def test_fma_oracle_stays_inside_the_matrix_bound(gname, wname):
     """The GPU test's inputs do not break the bound by themselves: FMA mode's own result is inside it."""
-    rp, col, w = mx.round_csr(gname, wname)
-    bits = mx.pool_bits(len(rp) - 1, 389, seed=7, correlated=wname == "signed")
-    got = oracle.round_bf16(bits, rp, col, w, np.arange(len(rp) - 1, dtype=np.int32), exact=False)
+    if (gname, wname) in mx.NEW_BOUND_CASES:
+        bits, rp, col, w, out_row = mx.bound_case(gname, wname)
+    else:
+        rp, col, w = mx.round_csr(gname, wname)
+        bits = mx.pool_bits(len(rp) - 1, 389, seed=7, correlated=wname == "signed")
+        out_row = np.arange(len(rp) - 1, dtype=np.int32)
+    got = oracle.round_bf16(bits, rp, col, w, out_row, exact=False)[out_row]
     assert mx.check_bound(got, *mx.reference(bits, rp, col, w)) <= 1.0
+
+
+@pytest.mark.parametrize("gname,variant", mx.EXACT_CASES)
+def test_exact_sum_rounds_are_exact_and_land_on_ties(gname, variant):
+    """The inputs of the GPU's bit-for-bit test, judged by the reference alone: mx.exact_case asserts
+    that every sum is exact in any order, that FMA mode's oracle is the sum rounded once, and the ties."""
+    mx.exact_case(gname, variant)

@@ -5777,6 +5777,25 @@ void mx_planes(float w, uint16_t out[3]) {
   out[2] = mx_bf16_bits(r1 - mx_bf16_value(out[1]));
 }
 
+// The exponent e <= 0 of the power of two that row r of a general tile carries in its epilogue
+// scale: its weights are split as w 2^-e.  A weight below 2^-103 would leave planes below the bf16
+// normals, where the split loses the bits under 2^-133 (and the matrix cores may flush the rest),
+// so the row's smallest weight is brought up to 2^-103 - as far as its largest stays below 2^128.
+// 0, and nothing changes, for a row without such a weight.
+int mx_row_exp(const Csr& c, int32_t r) {
+  int lo = 0, hi = 0;
+  bool any = false;
+  for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) {
+    const float w = static_cast<float>(c.w[k]);
+    if (w == 0.f || !std::isfinite(w)) continue;
+    const int e = std::ilogb(w);
+    lo = any ? std::min(lo, e) : e;
+    hi = any ? std::max(hi, e) : e;
+    any = true;
+  }
+  return any ? std::min(0, std::max(lo + 103, hi - 127)) : 0;
+}
+
 // The arrays of a matrix plan as they are built, in blob order.
 struct MxBuild {
   std::vector<int32_t> grp_tile_ptr{0}, grp_chunk_ptr{0}, chunk_src_ptr{0}, src_row, tile_kb_ptr, kb_ptr, tile_info,
@@ -5807,13 +5826,16 @@ void mx_encode_tile(const Csr& c, int32_t r0, int32_t nr, const std::vector<int3
   // the tile's dense weights [row][entry] as the A planes, 0 where a row does not list the entry
   const int planes = uniform ? 1 : 3;
   std::vector<uint16_t> wt(static_cast<size_t>(nr) * ne * 3, 0);
-  for (int32_t r = r0; r < r0 + nr; ++r)
+  std::vector<int> row_exp(static_cast<size_t>(nr), 0);
+  for (int32_t r = r0; r < r0 + nr; ++r) {
+    if (!uniform) row_exp[r - r0] = mx_row_exp(c, r);
     for (int32_t k = c.row_ptr[r]; k < c.row_ptr[r + 1]; ++k) {
       const int32_t j = static_cast<int32_t>(std::lower_bound(ent.begin(), ent.end(), key[k - k_first]) - ent.begin());
       uint16_t* pl = &wt[(static_cast<size_t>(r - r0) * ne + j) * 3];
       if (uniform) pl[0] = 0x3f80;  // 1.0: the row's weight scales the accumulator in the epilogue
-      else mx_planes(static_cast<float>(c.w[k]), pl);
+      else mx_planes(std::ldexp(static_cast<float>(c.w[k]), -row_exp[r - r0]), pl);  // exact: a scale up, below 2^128
     }
+  }
   b->tile_kb_ptr.push_back(static_cast<int32_t>(b->kb_ptr.size()));
   int32_t ja = 0;
   for (int32_t ch = 0; ch < n_chunks; ++ch) {
@@ -5846,7 +5868,7 @@ void mx_encode_tile(const Csr& c, int32_t r0, int32_t nr, const std::vector<int3
   const int32_t ti[4] = {r0, nr, planes, 0};
   b->tile_info.insert(b->tile_info.end(), ti, ti + 4);
   for (int32_t i = 0; i < kMxTileRows; ++i)
-    b->tile_w.push_back(i >= nr ? 0 : uniform ? f32_bits(c.w[c.row_ptr[r0 + i]]) : f32_bits(1.0));
+    b->tile_w.push_back(i >= nr ? 0 : uniform ? f32_bits(c.w[c.row_ptr[r0 + i]]) : f32_bits(std::ldexp(1.0, row_exp[i])));
 }
 
 }  // namespace
