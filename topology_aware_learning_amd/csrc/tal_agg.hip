@@ -75,7 +75,8 @@ int32_t check_launch(const char* what) {
 }
 
 // Runtime values to template arguments: f is called with the std::integral_constant that equals
-// the value (with_int: TAL_ERR_INVALID when it is none of Vs; with_int_or0: 0 stands for the rest).
+// the value (with_int: TAL_ERR_INVALID when it is none of Vs; with_int_or0: 0 stands for the rest;
+// with_ceil_int: the first of the ascending V0, Vs that is >= the value, the last for the rest).
 template <class F>
 int32_t with_bool(bool b, F&& f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
@@ -91,6 +92,11 @@ int32_t with_int_or0(int v, F&& f) {
   int32_t rc = TAL_OK;
   const bool found = ((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...);
   return found ? rc : f(std::integral_constant<int, 0>{});
+}
+template <int V0, int... Vs, class F>
+int32_t with_ceil_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return v <= V0 ? f(std::integral_constant<int, V0>{}) : with_ceil_int<Vs...>(v, f);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -1918,9 +1924,11 @@ int32_t launch_round_direct(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
   const int64_t threads = cols * in.rows;
   if (threads > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "round direct kernel: too many elements");
   const unsigned blocks = static_cast<unsigned>((threads + kBlock - 1) / kBlock);
-  auto k = (std::is_same<T, int64_t>::value || exact) ? k_round_direct<T, true> : k_round_direct<T, false>;
-  k<<<blocks, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, e0, static_cast<int>(cols), in.rows, in.n_groups, v);
-  return check_launch("round direct kernel");
+  return with_bool(kIsI64<T> || exact, [&](auto ex) {
+    k_round_direct<T, decltype(ex)::value><<<blocks, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, e0, static_cast<int>(cols),
+                                                                  in.rows, in.n_groups, v);
+    return check_launch("round direct kernel");
+  });
 }
 
 // the direct kernel serves the call: few columns, out of place
@@ -1989,11 +1997,12 @@ int32_t launch_round_scalar(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
   const int64_t tiles = (n - e0 + tile - 1) / tile;
   if (tiles > 0x7fffffff) return fail(TAL_ERR_INVALID, "too many tiles");
   const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(in.n_groups));
-  auto k = (std::is_same<T, int64_t>::value || exact) ? k_round_tiled_scalar<T, true> : k_round_tiled_scalar<T, false>;
-  int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
-  if (rc) return rc;
-  k<<<grid, kBlock, lds, s>>>(pin, ld_in, pout, ld_out, e0, n, v, tile);
-  return check_launch("round scalar kernel");
+  return with_bool(kIsI64<T> || exact, [&](auto ex) {
+    auto k = k_round_tiled_scalar<T, decltype(ex)::value>;
+    if (int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds)) return rc;
+    k<<<grid, kBlock, lds, s>>>(pin, ld_in, pout, ld_out, e0, n, v, tile);
+    return check_launch("round scalar kernel");
+  });
 }
 
 // Threads per round workgroup: 16 wavefronts at c4 = 64 (a 64-source tile is 4 loads per lane),
@@ -2016,20 +2025,6 @@ constexpr int persistent_j(int c4, int64_t loads) {
 dim3 persistent_grid(int64_t tiles, int64_t per_cu, int32_t n_groups) {
   const int64_t gx = std::min<int64_t>(std::max<int64_t>(1, 256 * per_cu / n_groups), tiles);
   return dim3(static_cast<unsigned>(gx), static_cast<unsigned>(n_groups));
-}
-
-template <int C4, int J, bool EXACT, bool DENSE, typename T = float>
-int32_t launch_round_persistent(const T* pin, int64_t ld_in, T* pout, int64_t ld_out,
-                                int64_t n4, const PlanView& v, const tal_round_plan_info& in,
-                                size_t lds, hipStream_t s) {
-  constexpr int kRoundThreads = round_threads(C4);
-  auto k = k_round_f32_persistent<C4, kRoundThreads, J, EXACT, DENSE, T>;
-  int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
-  if (rc) return rc;
-  const int64_t tiles = (n4 + C4 - 1) / C4;
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / static_cast<int64_t>(lds)));
-  k<<<persistent_grid(tiles, per_cu, in.n_groups), kRoundThreads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
-  return check_launch("round kernel (persistent)");
 }
 
 constexpr int kNarrowThreads = 1024;
@@ -2077,6 +2072,30 @@ int resident_per_cu(const void* kernel, int threads, size_t lds) {
   return nb;
 }
 
+// The launch every persistent-grid round kernel shares: opt in to its LDS, count the column
+// tiles (c4 float4 each), size the grid and launch.  per_cu = 0: what the runtime says is
+// resident, asked once the LDS is opted in.
+template <typename K, typename T>
+int32_t launch_on_persistent_grid(K k, int threads, size_t lds, int64_t per_cu, int c4, const char* what,
+                                  const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n4,
+                                  const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
+  if (int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds)) return rc;
+  const int64_t tiles = (n4 + c4 - 1) / c4;
+  if (per_cu == 0) per_cu = resident_per_cu(reinterpret_cast<const void*>(k), threads, lds);
+  k<<<persistent_grid(tiles, per_cu, in.n_groups), threads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
+  return check_launch(what);
+}
+
+template <int C4, int J, bool EXACT, bool DENSE, typename T = float>
+int32_t launch_round_persistent(const T* pin, int64_t ld_in, T* pout, int64_t ld_out,
+                                int64_t n4, const PlanView& v, const tal_round_plan_info& in,
+                                size_t lds, hipStream_t s) {
+  constexpr int kRoundThreads = round_threads(C4);
+  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / static_cast<int64_t>(lds)));
+  return launch_on_persistent_grid(k_round_f32_persistent<C4, kRoundThreads, J, EXACT, DENSE, T>, kRoundThreads, lds,
+                                   per_cu, C4, "round kernel (persistent)", pin, ld_in, pout, ld_out, n4, v, in, s);
+}
+
 // 16-B staging lanes for bf16 pools (W16 in k_round_f32_narrow): on unless TAL_NARROW_W16=0 (A/B)
 bool narrow_w16_enabled() {
   static const bool on = [] {
@@ -2093,22 +2112,20 @@ int32_t launch_round_narrow_jr(const T* pin, int64_t ld_in, T* pout, int64_t ld_
   // two workgroups per CU when their LDS allows it (registers capped at 64), else one with the
   // row extents in registers
   constexpr int kNP = J >= 12 ? kNarrowPasses / 2 : kNarrowPasses;  // J = 12: VGPRs for the staging
-  auto k = k_round_f32_narrow<C4, kNarrowThreads, J, kNP, EXACT, T, ROWW>;
-  if constexpr (J <= 4)
-    if (2 * lds <= 160 * 1024) k = k_round_f32_narrow<C4, kNarrowThreads, J, 0, EXACT, T, ROWW>;
-  if constexpr (kIsBf16<T> && J >= 2 && J <= 4) {
-    // whole chunk pairs per row (an even chunk count and stride) from a 16-B aligned base: no
-    // pair reaches past a row's last chunk
-    if (narrow_w16_enabled() && n4 % 2 == 0 && (ld_in / 4) % 2 == 0 && (reinterpret_cast<uintptr_t>(pin) & 15) == 0)
-      k = 2 * lds <= 160 * 1024 ? k_round_f32_narrow<C4, kNarrowThreads, J, 0, EXACT, T, ROWW, true>
-                                : k_round_f32_narrow<C4, kNarrowThreads, J, kNP, EXACT, T, ROWW, true>;
-  }
-  int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
-  if (rc) return rc;
-  const int64_t tiles = (n4 + C4 - 1) / C4;
-  const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k), kNarrowThreads, lds);
-  k<<<persistent_grid(tiles, per_cu, in.n_groups), kNarrowThreads, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
-  return check_launch("round kernel (narrow tiles)");
+  constexpr bool kTwoForm = J <= 4;                                  // the forms that exist at this J:
+  constexpr bool kW16Form = kIsBf16<T> && J >= 2 && J <= 4;          // a constant-false choice adds none
+  // W16: whole chunk pairs per row (an even chunk count and stride) from a 16-B aligned base: no
+  // pair reaches past a row's last chunk
+  const bool w16 = kW16Form && narrow_w16_enabled() && n4 % 2 == 0 && (ld_in / 4) % 2 == 0 && aligned16(pin);
+  return with_bool(kTwoForm && 2 * lds <= 160 * 1024, [&](auto two) {
+    return with_bool(w16, [&](auto w) {
+      constexpr int kNp = kTwoForm && decltype(two)::value ? 0 : kNP;
+      constexpr bool kW16 = kW16Form && decltype(w)::value;
+      return launch_on_persistent_grid(k_round_f32_narrow<C4, kNarrowThreads, J, kNp, EXACT, T, ROWW, kW16>,
+                                       kNarrowThreads, lds, 0, C4, "round kernel (narrow tiles)", pin, ld_in, pout,
+                                       ld_out, n4, v, in, s);
+    });
+  });
 }
 
 // Broadcast form: NT = 64 x the plan's waves; J staging loads per lane cover the largest group.
@@ -2117,24 +2134,21 @@ int32_t launch_round_bcast_j(const T* pin, int64_t ld_in, T* pout, int64_t ld_ou
                              const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
   const size_t lds = static_cast<size_t>(in.lds_bytes);
   const bool one = in.bc_wg_per_cu == 1;  // one workgroup per CU: 128 VGPRs at 1024 threads
-  const bool w16 = kIsBf16<T> && J % 2 == 0 && narrow_w16_enabled() && n4 % 2 == 0 && (ld_in / 4) % 2 == 0 &&
-                   (reinterpret_cast<uintptr_t>(pin) & 15) == 0;
-  // J = 8 at 1024 threads (the two-chunk form's 128 KiB tile) only with one workgroup per CU
+  constexpr bool kW16Form = kIsBf16<T> && J % 2 == 0;
+  const bool w16 = kW16Form && narrow_w16_enabled() && n4 % 2 == 0 && (ld_in / 4) % 2 == 0 && aligned16(pin);
+  // J = 8 at 1024 threads (the two-chunk form's 128 KiB tile) only with one workgroup per CU:
+  // it has no NP = 0 instantiation
   constexpr bool kOneOnly = NT == 1024 && J == 8;
   if (kOneOnly && !one) return fail(TAL_ERR_CAPACITY, "broadcast-form round plan: this tile needs one workgroup per CU");
-  auto k = (one || kOneOnly) ? k_round_f32_narrow<C4, NT, J, 1, EXACT, T, false, false, true>
-                             : k_round_f32_narrow<C4, NT, J, kOneOnly ? 1 : 0, EXACT, T, false, false, true>;
-  if constexpr (kIsBf16<T> && J % 2 == 0) {
-    if (w16)
-      k = (one || kOneOnly) ? k_round_f32_narrow<C4, NT, J, 1, EXACT, T, false, true, true>
-                            : k_round_f32_narrow<C4, NT, J, kOneOnly ? 1 : 0, EXACT, T, false, true, true>;
-  }
-  int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
-  if (rc) return rc;
-  const int64_t tiles = (n4 + C4 - 1) / C4;
-  const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k), NT, lds);
-  k<<<persistent_grid(tiles, per_cu, in.n_groups), NT, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
-  return check_launch("round kernel (narrow tiles, broadcast form)");
+  return with_bool(one, [&](auto o) {
+    return with_bool(w16, [&](auto w) {
+      constexpr int kNp = kOneOnly || decltype(o)::value ? 1 : 0;
+      constexpr bool kW16 = kW16Form && decltype(w)::value;
+      return launch_on_persistent_grid(k_round_f32_narrow<C4, NT, J, kNp, EXACT, T, false, kW16, true>, NT, lds, 0, C4,
+                                       "round kernel (narrow tiles, broadcast form)", pin, ld_in, pout, ld_out, n4, v,
+                                       in, s);
+    });
+  });
 }
 
 template <int C4, int NT, bool EXACT, typename T>
@@ -2406,12 +2420,12 @@ __global__ __launch_bounds__(kBlock) void k_round_clique(const T* __restrict__ p
 }
 
 // The last column of an odd-width round: one thread per member row, its chain in reference
-// order (every other member ascending, then itself).
+// order (every other member ascending, then itself).  wtab as in k_round_clique.
 template <bool EXACT, typename T, bool WSRC>
-__device__ __forceinline__ void round_clique_tail_row(const T* __restrict__ pin, int64_t ld_in,
-                                                      T* __restrict__ pout, int64_t ld_out, int64_t e,
-                                                      const int32_t* __restrict__ table,
-                                                      const float* __restrict__ wtab) {
+__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const T* __restrict__ pin, int64_t ld_in,
+                                                                  T* __restrict__ pout, int64_t ld_out, int64_t e,
+                                                                  const int32_t* __restrict__ table,
+                                                                  const float* __restrict__ wtab) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
   const int m = t[0];
   const int i = threadIdx.x;
@@ -2429,27 +2443,12 @@ __device__ __forceinline__ void round_clique_tail_row(const T* __restrict__ pin,
   Io<T>::st1(pout, static_cast<int64_t>(orow) * ld_out + e, acc);
 }
 
-template <bool EXACT, typename T>
-__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail(const T* __restrict__ pin, int64_t ld_in,
-                                                                  T* __restrict__ pout, int64_t ld_out,
-                                                                  int64_t e, const int32_t* __restrict__ table) {
-  round_clique_tail_row<EXACT, T, false>(pin, ld_in, pout, ld_out, e, table, nullptr);
-}
-
-template <bool EXACT, typename T>
-__global__ __launch_bounds__(kCliqueMax) void k_round_clique_tail_w(const T* __restrict__ pin, int64_t ld_in,
-                                                                    T* __restrict__ pout, int64_t ld_out,
-                                                                    int64_t e, const int32_t* __restrict__ table,
-                                                                    const float* __restrict__ wtab) {
-  round_clique_tail_row<EXACT, T, true>(pin, ld_in, pout, ld_out, e, table, wtab);
-}
-
 // The last column for a block's attached rows: one thread per attached row.
 template <bool EXACT, typename T, bool WSRC>
-__device__ __forceinline__ void round_clique_tail_extra_row(const T* __restrict__ pin, int64_t ld_in,
-                                                            T* __restrict__ pout, int64_t ld_out, int64_t e,
-                                                            const int32_t* __restrict__ table,
-                                                            const float* __restrict__ wtab) {
+__global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const T* __restrict__ pin, int64_t ld_in,
+                                                                          T* __restrict__ pout, int64_t ld_out,
+                                                                          int64_t e, const int32_t* __restrict__ table,
+                                                                          const float* __restrict__ wtab) {
   const int32_t* t = table + static_cast<int64_t>(blockIdx.x) * TAL_CLIQUE_WORDS;
   const int q = threadIdx.x;
   if (q >= t[2]) return;
@@ -2472,29 +2471,6 @@ __device__ __forceinline__ void round_clique_tail_extra_row(const T* __restrict_
   Io<T>::st1(pout, static_cast<int64_t>(xr[0]) * ld_out + e, acc);
 }
 
-template <bool EXACT, typename T>
-__global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra(const T* __restrict__ pin,
-                                                                          int64_t ld_in, T* __restrict__ pout,
-                                                                          int64_t ld_out, int64_t e,
-                                                                          const int32_t* __restrict__ table) {
-  round_clique_tail_extra_row<EXACT, T, false>(pin, ld_in, pout, ld_out, e, table, nullptr);
-}
-
-template <bool EXACT, typename T>
-__global__ __launch_bounds__(kCliqueExtra) void k_round_clique_tail_extra_w(const T* __restrict__ pin,
-                                                                            int64_t ld_in, T* __restrict__ pout,
-                                                                            int64_t ld_out, int64_t e,
-                                                                            const int32_t* __restrict__ table,
-                                                                            const float* __restrict__ wtab) {
-  round_clique_tail_extra_row<EXACT, T, true>(pin, ld_in, pout, ld_out, e, table, wtab);
-}
-
-template <int MMAX, bool EXACT, typename T, bool WSRC>
-void launch_clique_block(dim3 grid, const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n2,
-                         const int32_t* table, const float* wtab, hipStream_t s) {
-  k_round_clique<MMAX, EXACT, T, WSRC><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table, wtab);
-}
-
 // wtab: the per-source weight table (WSRC), else unused
 template <bool EXACT, typename T, bool WSRC>
 int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
@@ -2508,30 +2484,18 @@ int32_t launch_round_clique(const T* pin, int64_t ld_in, T* pout, int64_t ld_out
     // the chains run over MMAX slots, the ones past the largest clique adding -0.0: MMAX close
     // to the clique size keeps those no-op adds few (a 60-member barbell clique under MMAX 64
     // spent 13 % of its adds on padding)
-    auto go = [&](auto M) {
-      launch_clique_block<decltype(M)::value, EXACT, T, WSRC>(grid, pin, ld_in, pout, ld_out, n2, table, wtab, s);
-    };
-    if (mmax <= 16) go(std::integral_constant<int, 16>{});
-    else if (mmax <= 32) go(std::integral_constant<int, 32>{});
-    else if (mmax <= 40) go(std::integral_constant<int, 40>{});
-    else if (mmax <= 48) go(std::integral_constant<int, 48>{});
-    else if (mmax <= 56) go(std::integral_constant<int, 56>{});
-    else if (mmax <= 60) go(std::integral_constant<int, 60>{});
-    else go(std::integral_constant<int, 64>{});
-    int32_t rc = check_launch("clique round kernel");
+    int32_t rc = with_ceil_int<16, 32, 40, 48, 56, 60, 64>(mmax, [&](auto M) {
+      k_round_clique<decltype(M)::value, EXACT, T, WSRC><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n2, table, wtab);
+      return check_launch("clique round kernel");
+    });
     if (rc) return rc;
   }
   if (n % 2) {
-    if constexpr (WSRC)
-      k_round_clique_tail_w<EXACT, T><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table, wtab);
-    else k_round_clique_tail<EXACT, T><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
+    k_round_clique_tail<EXACT, T, WSRC><<<n_cliques, kCliqueMax, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table, wtab);
     int32_t rc = check_launch("clique round tail kernel");
     if (rc) return rc;
-    if constexpr (WSRC)
-      k_round_clique_tail_extra_w<EXACT, T><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table,
-                                                                             wtab);
-    else
-      k_round_clique_tail_extra<EXACT, T><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table);
+    k_round_clique_tail_extra<EXACT, T, WSRC><<<n_cliques, kCliqueExtra, 0, s>>>(pin, ld_in, pout, ld_out, n - 1, table,
+                                                                                wtab);
     return check_launch("clique round tail kernel (attached rows)");
   }
   return TAL_OK;
@@ -2692,16 +2656,11 @@ int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld
   const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_cliques));
   // MMAX close to the block size keeps the -0.0 padding steps few: 68 for the reference's 66
   // clients, 100 for its 100
-  auto go = [&](auto M) {
+  return with_ceil_int<68, 84, 100, 116, 128>(mmax, [&](auto M) {
     k_round_clique_col<decltype(M)::value, EXACT, T, WSRC><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n, table,
                                                                                    wtab);
-  };
-  if (mmax <= 68) go(std::integral_constant<int, 68>{});
-  else if (mmax <= 84) go(std::integral_constant<int, 84>{});
-  else if (mmax <= 100) go(std::integral_constant<int, 100>{});
-  else if (mmax <= 116) go(std::integral_constant<int, 116>{});
-  else go(std::integral_constant<int, 128>{});
-  return check_launch("clique round kernel (one column per lane)");
+    return check_launch("clique round kernel (one column per lane)");
+  });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2896,14 +2855,8 @@ int32_t launch_round_seq(T* pool, int64_t ld, int64_t n, const int32_t* plan, co
 template <int NT, bool EXACT>
 int32_t launch_round_stream_nt(const float* pin, int64_t ld_in, float* pout, int64_t ld_out, int64_t n4,
                                const PlanView& v, const tal_round_plan_info& in, hipStream_t s) {
-  auto k = k_round_stream<NT, EXACT>;
-  const size_t lds = stream_lds_bytes(NT / 64 * kStreamPerWave);
-  int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
-  if (rc) return rc;
-  const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k), NT, lds);
-  const int64_t tiles = (n4 + 63) / 64;
-  k<<<persistent_grid(tiles, per_cu, in.n_groups), NT, lds, s>>>(pin, ld_in / 4, pout, ld_out / 4, n4, v, tiles);
-  return check_launch("round kernel (streamed)");
+  return launch_on_persistent_grid(k_round_stream<NT, EXACT>, NT, stream_lds_bytes(NT / 64 * kStreamPerWave), 0, 64,
+                                   "round kernel (streamed)", pin, ld_in, pout, ld_out, n4, v, in, s);
 }
 
 template <typename T>
@@ -2916,12 +2869,13 @@ int32_t launch_round_stream_scalar(const T* pin, int64_t ld_in, T* pout, int64_t
   const size_t lds = static_cast<size_t>(in.max_src) * tc * 4;
   const int64_t tiles = (n - e0 + tc - 1) / tc;
   if (tiles > 0x7fffffff) return fail(TAL_ERR_INVALID, "too many tiles");
-  auto k = (kIsI64<T> || exact) ? k_round_stream_scalar<T, true> : k_round_stream_scalar<T, false>;
-  int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds);
-  if (rc) return rc;
   const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>(in.n_groups));
-  k<<<grid, kBlock, lds, s>>>(pin, ld_in, pout, ld_out, e0, n, v, static_cast<int>(tc));
-  return check_launch("round scalar kernel (streamed plan)");
+  return with_bool(kIsI64<T> || exact, [&](auto ex) {
+    auto k = k_round_stream_scalar<T, decltype(ex)::value>;
+    if (int32_t rc = ensure_lds(reinterpret_cast<const void*>(k), lds)) return rc;
+    k<<<grid, kBlock, lds, s>>>(pin, ld_in, pout, ld_out, e0, n, v, static_cast<int>(tc));
+    return check_launch("round scalar kernel (streamed plan)");
+  });
 }
 
 template <int C4, bool EXACT, bool DENSE, typename T = float>

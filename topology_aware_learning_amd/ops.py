@@ -203,8 +203,19 @@ BCAST_CANDIDATES = ((16, 8, 2), (16, 16, 2), (32, 16, 1), (32, 8, 2))
 TUNE_DROP = 1.5  # a candidate whose first timed run exceeds the default's by this factor is dropped
 
 
+class _BlobPlan:
+    """What the plans that are one int32 blob (`host`) share: its copy on a device (`device`),
+    made by to() alone, which notes where it is (`on`, as a CliquePlan's)."""
+    on: Optional[torch.device] = None
+
+    def to(self, device):
+        self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
+        self.on = self.device.device
+        return self
+
+
 @dataclass
-class RoundPlan:
+class RoundPlan(_BlobPlan):
     info: RoundPlanInfo
     host: np.ndarray           # int32 blob
     device: Optional[torch.Tensor] = None
@@ -225,10 +236,6 @@ class RoundPlan:
         h, i = self.host, self.info
         return (int(h[i.off_src_row: i.off_src_row + i.total_src].max(initial=-1)),
                 int(h[i.off_out_row: i.off_out_row + i.rows].max(initial=-1)))
-
-    def to(self, device) -> "RoundPlan":
-        self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
-        return self
 
     def staged_rows(self) -> int:
         """Source rows read from HBM per column tile (sum over groups)."""
@@ -329,13 +336,8 @@ def build_plan(row_ptr, col, w, out_row, c4: int = 0, lds_bytes: int = 0, dense:
     by DPP row broadcasts, so per-operand weights cost no LDS reads (c4 16 / 32 only);
     bcast_wg = resident workgroups per CU it is compiled for (1: 128 VGPRs at 1024 threads and
     8 LDS reads in flight per wavefront; 2: 64 VGPRs, two groups' tiles per CU)."""
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
-    col = np.ascontiguousarray(col, dtype=np.int32)
-    w = np.ascontiguousarray(w, dtype=np.float64)
-    out_row = np.ascontiguousarray(out_row, dtype=np.int32)
+    (row_ptr, col, w, out_row), args = _csr_args(row_ptr, col, w, out_row)
     rows = len(out_row)
-    if len(row_ptr) != rows + 1 or row_ptr[-1] != len(col) or len(w) != len(col):
-        raise ValueError("inconsistent CSR arrays")
     L = _lib.load()
     cap = L.tal_round_plan_words(rows, len(col))
     best = None
@@ -344,29 +346,18 @@ def build_plan(row_ptr, col, w, out_row, c4: int = 0, lds_bytes: int = 0, dense:
     cands = [(c, b) for b in ([lds_bytes] if lds_bytes else LDS_BUDGETS) for c in widths]
     for cand, budget in cands:
         info = RoundPlanInfo()
-        P32 = ctypes.POINTER(ctypes.c_int32)
-        size = cap
-        for _ in range(2):  # the dense tables' size is known only after grouping: retry once
-            blob = np.zeros(size, dtype=np.int32)
-            args = (rows, row_ptr.ctypes.data_as(P32), col.ctypes.data_as(P32),
-                    w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out_row.ctypes.data_as(P32), cand, int(budget))
-            if bcast:
-                rc = L.tal_round_plan_build_bcast(*args, int(bcast), int(bcast_wg), blob.ctypes.data_as(P32), size,
-                                                  ctypes.byref(info))
-            else:
-                rc = L.tal_round_plan_build(*args, int(dense), blob.ctypes.data_as(P32), size, ctypes.byref(info))
-            if rc == _lib.TAL_ERR_CAPACITY and info.words > size:
-                size = int(info.words)
-                continue
-            break
-        if rc != _lib.TAL_OK:
-            last_err = _lib.TalError(rc, L.tal_last_error().decode())
+        fn, form = ((L.tal_round_plan_build_bcast, (int(bcast), int(bcast_wg))) if bcast
+                    else (L.tal_round_plan_build, (int(dense),)))
+        try:  # (the dense tables' size is known only after grouping: the capacity protocol)
+            blob = _build_blob(fn, args, (cand, int(budget), *form), cap, info)
+        except _lib.TalError as exc:
+            last_err = exc
             continue
         spec = dict(c4=int(cand), lds=int(budget), dense=int(dense))
         if bcast:
             spec["bcast"] = int(bcast)
             spec["bcwg"] = int(bcast_wg)
-        plan = RoundPlan(info=info, host=blob[: info.words].copy(), rows=rows, nnz=len(col), spec=spec)
+        plan = RoundPlan(info=info, host=blob, rows=rows, nnz=len(col), spec=spec)
         key = (_plan_cost(plan.info), -_blocks_per_cu(plan.info))
         if best is None or key < best[0]:
             best = (key, plan)
@@ -680,8 +671,6 @@ def _sub_csr(row_ptr, col, w, out_row, rows):
     return rp, col[sel], w[sel], np.asarray(out_row)[rows]
 
 
-
-
 def _csr(row_ptr, col, w, out_row):
     row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
     col = np.ascontiguousarray(col, dtype=np.int32)
@@ -692,30 +681,38 @@ def _csr(row_ptr, col, w, out_row):
     return row_ptr, col, w, out_row
 
 
+def _csr_args(row_ptr, col, w, out_row):
+    """The normalised CSR arrays and what every plan builder of the C-ABI takes first:
+    (rows, row_ptr, col, w, out_row)."""
+    arrays = _csr(row_ptr, col, w, out_row)
+    P32, PD = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+    return arrays, (len(arrays[3]), *(a.ctypes.data_as(PD if a.dtype == np.float64 else P32) for a in arrays))
+
+
+def _build_blob(fn, args, tail_args, size, info) -> np.ndarray:
+    """The plan blob of builder `fn` by the capacity protocol: a buffer of `size` int32 words and,
+    where the builder answers TAL_ERR_CAPACITY with the words it needs, one retry at that size."""
+    for _ in range(2):
+        blob = np.zeros(size, dtype=np.int32)
+        rc = fn(*args, *tail_args, blob.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), size, ctypes.byref(info))
+        if rc != _lib.TAL_ERR_CAPACITY or info.words <= size:
+            break
+        size = int(info.words)
+    check(rc)
+    return blob[: info.words].copy()
+
+
 def build_stream_plan(row_ptr, col, w, out_row, max_group_rows: int = 64, max_group_src: int = 0) -> RoundPlan:
     """Streamed-form plan (tal_round_plan_build_stream): groups of <= max_group_rows
     consecutive rows (and <= max_group_src distinct sources if > 0) whose sources stream through
     an LDS ring, so cliques and other dense neighborhoods of any size run without the LDS bound
     of build_plan.  Needs every row in reference order (sorted neighbors, then self)."""
-    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
-    rows = len(out_row)
+    (row_ptr, col, w, out_row), args = _csr_args(row_ptr, col, w, out_row)
     L = _lib.load()
-    P32 = ctypes.POINTER(ctypes.c_int32)
-    size = L.tal_round_plan_words(rows, len(col))
     info = RoundPlanInfo()
-    for _ in range(2):
-        blob = np.zeros(size, dtype=np.int32)
-        rc = L.tal_round_plan_build_stream(rows, row_ptr.ctypes.data_as(P32), col.ctypes.data_as(P32),
-                                           w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                           out_row.ctypes.data_as(P32), int(max_group_rows),
-                                           int(max_group_src), blob.ctypes.data_as(P32), size,
-                                           ctypes.byref(info))
-        if rc == _lib.TAL_ERR_CAPACITY and info.words > size:
-            size = int(info.words)
-            continue
-        break
-    check(rc)
-    return RoundPlan(info=info, host=blob[: info.words].copy(), rows=rows, nnz=len(col))
+    blob = _build_blob(L.tal_round_plan_build_stream, args, (int(max_group_rows), int(max_group_src)),
+                       L.tal_round_plan_words(len(out_row), len(col)), info)
+    return RoundPlan(info=info, host=blob, rows=len(out_row), nnz=len(col))
 
 
 def rows_uniform(row_ptr, w) -> bool:
@@ -1024,6 +1021,20 @@ def round_pool(pool_in: torch.Tensor, pool_out: torch.Tensor, plan, n: Optional[
     return globals()["round" + s.suffix](pool_in, pool_out, plan, n, *(mode,) * s.takes_mode, stream=stream)
 
 
+def _plan_on(plan, device) -> None:
+    """The plan's device copies are on `device`: moved there unless they are."""
+    if plan.on != device:
+        plan.to(device)
+
+
+def _check_plan_rows(plan, pool_in, pool_out) -> None:
+    reads, writes = plan.row_bounds
+    if reads >= pool_in.shape[0]:
+        raise ValueError("plan reads a pool row beyond pool_in")
+    if writes >= pool_out.shape[0]:
+        raise ValueError("plan writes a pool row beyond pool_out")
+
+
 def _round(seg: Segment, pool_in, pool_out, plan, n, mode, stream) -> torch.Tensor:
     """The round by the plan's kind: a CliquePlan runs K3c / K3c1 and its rest plan (on int64
     pools, which the clique kernels do not take, its `full` plan), a RowCallPlan one K1 call per
@@ -1044,14 +1055,9 @@ def _round(seg: Segment, pool_in, pool_out, plan, n, mode, stream) -> torch.Tens
     if isinstance(plan, RowCallPlan):
         return _round_rows(seg, pool_in, pool_out, plan, n, mode, stream)
     _check_pools(seg, pool_in, pool_out)
-    if plan.device is None or plan.device.device != pool_in.device:
-        plan.to(pool_in.device)
+    _plan_on(plan, pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
-    reads, writes = plan.row_bounds
-    if reads >= pool_in.shape[0]:
-        raise ValueError("plan reads a pool row beyond pool_in")
-    if writes >= pool_out.shape[0]:
-        raise ValueError("plan writes a pool row beyond pool_out")
+    _check_plan_rows(plan, pool_in, pool_out)
     _call("tal_agg_round", seg,
           (ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
            pool_out.stride(0), n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)),
@@ -1061,8 +1067,7 @@ def _round(seg: Segment, pool_in, pool_out, plan, n, mode, stream) -> torch.Tens
 
 def _round_clique(seg: Segment, pool_in, pool_out, plan: CliquePlan, n, mode, stream):
     _check_pools(seg, pool_in, pool_out, what="clique")
-    if plan.on != pool_in.device:
-        plan.to(pool_in.device)
+    _plan_on(plan, pool_in.device)
     n = pool_in.shape[1] if n is None else int(n)
     pair = 2 * seg.esize
     if plan.n_cliques > 0 and ((pool_in.stride(0) | pool_out.stride(0)) % 2
@@ -1070,11 +1075,7 @@ def _round_clique(seg: Segment, pool_in, pool_out, plan: CliquePlan, n, mode, st
         # K3c reads and writes column pairs (8 B fp32, 4 B bf16): rows not aligned to one take the full plan
         # (K3c1 has no such rule: a plan of 65..128-member blocks alone never gets here)
         return _round(seg, pool_in, pool_out, plan.full, n, mode, stream)
-    reads, writes = plan.row_bounds
-    if reads >= pool_in.shape[0]:
-        raise ValueError("plan reads a pool row beyond pool_in")
-    if writes >= pool_out.shape[0]:
-        raise ValueError("plan writes a pool row beyond pool_out")
+    _check_plan_rows(plan, pool_in, pool_out)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     # K3c for the blocks of <= 64 members, then K3c1 for those of 65..128, each with per-source
     # weights where the plan carries them
@@ -1111,7 +1112,7 @@ SEQ_DEFAULT = {(False, MODE_EXACT): False, (False, MODE_FMA): False,
 
 
 @dataclass
-class SeqPlan:
+class SeqPlan(_BlobPlan):
     """A sequential round (tal_agg.h K3q): rows in the caller's order, each reading the pool as
     the rows before it left it."""
     info: SeqPlanInfo
@@ -1120,10 +1121,6 @@ class SeqPlan:
     rows: int = 0
     nnz: int = 0
     spec: Optional[dict] = None
-
-    def to(self, device) -> "SeqPlan":
-        self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
-        return self
 
     def staged_rows(self) -> int:
         """Source rows read from HBM per column tile."""
@@ -1134,17 +1131,11 @@ def build_seq_plan(row_ptr, col, w, out_row) -> SeqPlan:
     """The plan of a sequential round given as CSR (row r: operands col[row_ptr[r]:row_ptr[r+1]]
     with float64 weights w, written to pool row out_row[r]; rows run in this order).  Raises
     TalError with TAL_ERR_CAPACITY for more than SEQ_MAX_SRC distinct source rows."""
-    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
-    rows = len(out_row)
+    (row_ptr, col, w, out_row), args = _csr_args(row_ptr, col, w, out_row)
     L = _lib.load()
-    P32 = ctypes.POINTER(ctypes.c_int32)
-    size = int(L.tal_seq_plan_words(rows, len(col)))
     info = SeqPlanInfo()
-    blob = np.zeros(size, dtype=np.int32)
-    check(L.tal_seq_plan_build(rows, row_ptr.ctypes.data_as(P32), col.ctypes.data_as(P32),
-                               w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out_row.ctypes.data_as(P32),
-                               blob.ctypes.data_as(P32), size, ctypes.byref(info)))
-    return SeqPlan(info=info, host=blob[: info.words].copy(), rows=rows, nnz=len(col), spec={"seq": 1})
+    blob = _build_blob(L.tal_seq_plan_build, args, (), int(L.tal_seq_plan_words(len(out_row), len(col))), info)
+    return SeqPlan(info=info, host=blob, rows=len(out_row), nnz=len(col), spec={"seq": 1})
 
 
 def round_seq(pool: torch.Tensor, plan: SeqPlan, n: Optional[int] = None, mode: int = MODE_EXACT,
@@ -1165,8 +1156,7 @@ def _round_seq(seg: Segment, pool, plan: SeqPlan, n, mode, stream) -> torch.Tens
         raise ValueError(f"n = {n} outside the pool's {pool.shape[1]} columns")
     if plan.info.max_row >= pool.shape[0]:
         raise ValueError("plan reads or writes a pool row beyond the pool")
-    if plan.device is None or plan.device.device != pool.device:
-        plan.to(pool.device)
+    _plan_on(plan, pool.device)
     _call("tal_agg_round_seq", seg,
           (ctypes.c_void_p(pool.data_ptr()), pool.stride(0), pool.shape[0], n,
            ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info)), mode, _stream(pool.device, stream))
@@ -1201,7 +1191,7 @@ MATRIX_PLAN_ONE_PASS = 1 << 24  # int32 words (64 MiB): build_matrix_plan's one-
 
 
 @dataclass
-class MatrixPlan:
+class MatrixPlan(_BlobPlan):
     """A snapshot round for the matrix cores (tal_agg.h K3m): OUT = W . X on bf16 pools, opt-in
     (MODE_MATRIX) and not bit-comparable to the other modes.  `full` is a regular plan over all
     rows for the int64 segment, as a CliquePlan's."""
@@ -1224,7 +1214,7 @@ class MatrixPlan:
         return int(self.info.n_src)
 
     def to(self, device) -> "MatrixPlan":
-        self.device = torch.from_numpy(self.host).to(device, non_blocking=False)
+        super().to(device)
         self.full.to(device)
         return self
 
@@ -1233,12 +1223,9 @@ def build_matrix_plan(row_ptr, col, w, out_row) -> MatrixPlan:
     """The K3m plan of a round given as CSR (row r: operands col[row_ptr[r]:row_ptr[r+1]] with
     float64 weights w, written to pool row out_row[r]).  Any operand count and order; neither
     the rows nor the sources of a round are bounded."""
-    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
+    (row_ptr, col, w, out_row), args = _csr_args(row_ptr, col, w, out_row)
     rows = len(out_row)
     L = _lib.load()
-    P32 = ctypes.POINTER(ctypes.c_int32)
-    args = (rows, row_ptr.ctypes.data_as(P32), col.ctypes.data_as(P32),
-            w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out_row.ctypes.data_as(P32))
     info = MatrixPlanInfo()
     # one planner pass into a buffer of tal_matrix_plan_words' upper bound where that is small (it
     # allows 3 k-blocks of 1 KiB per operand: 780 words each); past MATRIX_PLAN_ONE_PASS words the
@@ -1250,9 +1237,7 @@ def build_matrix_plan(row_ptr, col, w, out_row) -> MatrixPlan:
         if rc != _lib.TAL_ERR_CAPACITY or info.words <= 0:
             check(rc)
         size = int(info.words)
-    blob = np.zeros(size, dtype=np.int32)
-    check(L.tal_matrix_plan_build(*args, blob.ctypes.data_as(P32), size, ctypes.byref(info)))
-    blob = blob[: info.words].copy()
+    blob = _build_blob(L.tal_matrix_plan_build, args, (), size, info)
     full = default_plan(row_ptr, col, w, out_row, bf16=True)
     if isinstance(full, CliquePlan):
         full = full.full
@@ -1274,8 +1259,7 @@ def round_matrix_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: Matri
     pool_rows = min(pool_in.shape[0], pool_out.shape[0])
     if plan.info.max_row >= pool_rows:  # (the C entry refuses it too: TAL_ERR_INVALID, no launch)
         raise ValueError("plan reads or writes a pool row beyond the pools")
-    if plan.device is None or plan.device.device != pool_in.device:
-        plan.to(pool_in.device)
+    _plan_on(plan, pool_in.device)
     check(_lib.load().tal_agg_round_matrix_bf16(
         ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
         pool_out.stride(0), pool_rows, n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info),
