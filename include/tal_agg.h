@@ -62,7 +62,8 @@ const char* tal_last_error(void);
  * selected it.  ABI 34 added the column clique entries with per-source weights
  * (tal_agg_round_clique_col_w_*).  ABI 35 added the sequential round in one launch (K3q:
  * tal_seq_plan_*, tal_agg_round_seq_*).  ABI 36 added TAL_MODE_MATRIX: rounds on bf16 pools on the
- * matrix cores (K3m: tal_matrix_plan_*, tal_agg_round_matrix_bf16). */
+ * matrix cores (K3m: tal_matrix_plan_*, tal_agg_round_matrix_bf16).  ABI 37 added the clique
+ * entries for blocks of up to 256 members (K3c2: tal_agg_round_clique_half_*). */
 int32_t tal_abi_version(void);
 
 /* ---- K1: one aggregation call over M flattened operands --------------------------------
@@ -370,6 +371,33 @@ int32_t tal_agg_round_clique_col_w_bf16(const uint16_t* pool_in, int64_t ld_in, 
                                         int64_t ld_out, int64_t n, const int32_t* table_dev,
                                         int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
                                         const float* wtab_dev);
+
+/* Clique rounds for blocks of up to 256 members (K3c2, ABI 37): uniform-weight blocks as the
+ * column entries', two lanes per element column - a wavefront owns 32 columns, lanes l and l + 32
+ * keep one half of a column's products each and hand a row's chain across by
+ * v_permlane32_swap_b32 (`unweighted_fl` over 200 or 256 clients is one such block).  The
+ * arithmetic is the column entries' per column and per mode, each row its own in-order chain:
+ * the same bits.  table_dev: n_cliques records of TAL_CLIQUE_HALF_WORDS int32
+ *   {m, bits of w, 0, 0, src_row[256], out_row[256]}
+ * (out_row -1: member without an output row) copied to the device; no attached rows and no
+ * per-source weights.  Blocks of any m <= 256 are legal (m <= 128 gives the bits of
+ * tal_agg_round_clique_col_*).  Any ld >= n and element-aligned pools.  Out of place only.
+ * TAL_ERR_INVALID, with no launch, for a null pointer, pool_out == pool_in, mmax outside
+ * 1..TAL_CLIQUE_HALF_MAX, n_cliques outside 0..65535 or ld < n.  mmax = the largest m (kernels
+ * for 160, 192, 224 and 256 members: 80 to 128 product registers per lane). */
+#define TAL_CLIQUE_HALF_MAX 256
+#define TAL_CLIQUE_HALF_WORDS 516
+#if defined(__cplusplus)
+static_assert(TAL_CLIQUE_HALF_WORDS == 4 + 2 * TAL_CLIQUE_HALF_MAX, "two-lane-form record: header + 256 sources + 256 rows");
+#else
+_Static_assert(TAL_CLIQUE_HALF_WORDS == 4 + 2 * TAL_CLIQUE_HALF_MAX, "two-lane-form record: header + 256 sources + 256 rows");
+#endif
+int32_t tal_agg_round_clique_half_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                      int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                      int32_t mode, void* stream);
+int32_t tal_agg_round_clique_half_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out,
+                                       int64_t ld_out, int64_t n, const int32_t* table_dev,
+                                       int32_t n_cliques, int32_t mmax, int32_t mode, void* stream);
 
 /* ---- K3q: a sequential round in one launch (ABI 35) -----------------------------------------
  * The reference's round under one aggregation thread: its apps overwrite the client models that

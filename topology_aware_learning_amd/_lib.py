@@ -28,7 +28,7 @@ TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
 TAL_MODE_MATRIX = 2
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 EXPORTED = (
     "tal_last_error",
@@ -54,6 +54,8 @@ EXPORTED = (
     "tal_agg_round_clique_col_bf16",
     "tal_agg_round_clique_col_w_f32",
     "tal_agg_round_clique_col_w_bf16",
+    "tal_agg_round_clique_half_f32",
+    "tal_agg_round_clique_half_bf16",
     "tal_seq_plan_words",
     "tal_seq_plan_build",
     "tal_agg_round_seq_f32",
@@ -236,6 +238,8 @@ _SIGS = {
     "tal_agg_round_clique_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_agg_round_clique_col_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_clique_col_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
+    "tal_agg_round_clique_half_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
+    "tal_agg_round_clique_half_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P]),
     "tal_agg_round_clique_col_w_f32": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_agg_round_clique_col_w_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P]),
     "tal_seq_plan_words": (_I64, [_I32, _I64]),

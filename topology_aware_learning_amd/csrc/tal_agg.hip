@@ -29,6 +29,7 @@
 #include <thread>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -47,7 +48,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 36;
+constexpr int kAbiVersion = 37;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -2664,6 +2665,190 @@ int32_t launch_round_clique_col(const T* pin, int64_t ld_in, T* pout, int64_t ld
 }
 
 // ------------------------------------------------------------------------------------------
+// K3c2: K3c1 for uniform-weight blocks of 129..256 members, two lanes per column.  256 products
+// of a column do not fit one lane's registers beside the chains, so a wavefront owns 32 columns
+// and lanes l and l + 32 share column c0 + (l & 31): the low half keeps p_0 .. p_{H-1}, the high
+// half p_H .. p_{MMAX-1} (H = MMAX / 2), each K3c1's way (v2f pp[H / 2], packed steps whose second
+// source broadcasts one half of a pair).  The arithmetic is K3c's, chain for chain:
+// row i = ((S_i + p_{i+1}) + ... + p_{m-1}) + p_i, S_0 and the padding -0.0 (FMA: the zero whose
+// product with w is -0.0).
+// Rows i < H, four at a time: the low lane runs S_i + p_{i+1} .. p_{H-1}, hands the accumulator
+// and p_i to the lane 32 above (v_permlane32_swap_b32: vector ALU only, no LDS), and the high
+// lane adds p_H .. p_{MMAX-1}, then p_i, and stores.  The two halves are software-pipelined over
+// the row groups with no exec masking: in sweep g every lane runs `acc += pp[k]` over all of its
+// H slots - the high lanes for group g - 1, the low lanes for group g, whose slots of the groups
+// up to g hold the padding zero by then (a product is never needed in the low half again once
+// its group has been handed over, and x + -0.0 == x for every x).  One swap per product does
+// both: swap(padding, p_j) leaves {padding, p_j of the low lane} as the high lanes' own term
+// (the low lanes' own term is the padding: a no-op step) and {padding, the high lane's p} as the
+// new slot.  One more per chain hands the accumulators over: swap(next heads, swept chains)
+// leaves {low: the next group's heads, high: the low lanes' chains}.
+// Rows i >= H run on the high half alone, K3c1's loop on its H slots from S_H (handed over once);
+// the low lanes run the same steps on padding.  H / 4 + 1 sweeps of H steps and H^2 / 8 steps of
+// the second part: 3 MMAX^2 / 32 + MMAX / 2 four-chain steps per 32 columns.
+// Stores come from the 32 high lanes, one element each: any ld, element-aligned pools, no tail.
+// ------------------------------------------------------------------------------------------
+constexpr int kCliqueHalfMax = TAL_CLIQUE_HALF_MAX;
+static_assert(4 + 2 * kCliqueHalfMax == TAL_CLIQUE_HALF_WORDS, "two-lane-form table layout");
+constexpr int kHalfCols = kBlock / 2;  // columns per workgroup: 32 per wavefront
+
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>) in order: a loop unrolled by the
+// language (the row-group loops below are past the size at which `#pragma unroll` still unrolls,
+// and a loop left rolled would index the product registers dynamically)
+template <int... Is, class F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, Is...>, F&& f) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(std::make_integer_sequence<int, N>{}, f);
+}
+
+// v_permlane32_swap_b32 a, b: lanes 32..63 of a and lanes 0..31 of b change places, so
+// a = {a's low lanes, b's low lanes} and b = {a's high lanes, b's high lanes}.
+__device__ __forceinline__ void half_swap(float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+
+// Column e of every row of clique block `t` (TAL_CLIQUE_HALF_WORDS record).
+template <int MMAX, bool EXACT, typename T>
+__global__ __launch_bounds__(kBlock) void k_round_clique_half(const T* __restrict__ pin, int64_t ld_in,
+                                                              T* __restrict__ pout, int64_t ld_out, int64_t n,
+                                                              const int32_t* __restrict__ table) {
+  constexpr int H = MMAX / 2;
+  static_assert(H % 4 == 0 && MMAX <= kCliqueHalfMax, "each half takes its rows in fours");
+  const int32_t* t = table + static_cast<int64_t>(blockIdx.y) * TAL_CLIQUE_HALF_WORDS;
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * kHalfCols + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
+  if (e >= n) return;  // both lanes of a column leave: a swap never reads a lane that left
+  const bool hi = (threadIdx.x & 32) != 0;
+  const int m = t[0];
+  const float w = __int_as_float(t[1]);
+  const float pad = EXACT ? -0.f : (__float_as_uint(w) >> 31 ? 0.f : -0.f);
+  // as k_round_clique_col: every load issued unconditionally (a padding slot re-reads member 0,
+  // an L2 hit), all H of a lane in flight before the first use, in batches of 8.  A slot's row
+  // index differs between the halves, so a lane reads its own from the record (a vector load at
+  // the lane's half of src_row) and forms its address from it.
+  const int32_t* th = t + 4 + (hi ? H : 0);  // this half's src_row
+  const int mh = hi ? m - H : m;             // slots below mh hold a member
+  const int row0 = t[4];
+  v2f pp[H / 2];  // slot j = pp[j / 2][j % 2]: p_j in the low lanes, p_{H + j} in the high lanes
+  auto p = [&](int j) -> float { return pp[j >> 1][j & 1]; };
+#pragma unroll
+  for (int j = 0; j < H; ++j) {
+    const int slot_row = th[j];  // inside the record for every slot of either half
+    const int row = j < mh ? slot_row : row0;
+    pp[j >> 1][j & 1] = Io<T>::ld1(pin + static_cast<int64_t>(row) * ld_in, e);
+    if (j % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+  }
+#pragma unroll
+  for (int j = 0; j < H; ++j) {
+    if constexpr (kIsBf16<T> && EXACT) pp[j >> 1][j & 1] = round_bf16(__fmul_rn(w, p(j)));
+    else if constexpr (EXACT) pp[j >> 1][j & 1] = __fmul_rn(w, p(j));
+    if (j >= mh) pp[j >> 1][j & 1] = pad;
+  }
+  // A pair whose halves were written one by one is pinned to one aligned register pair again, so
+  // that the chain steps read it through op_sel (left alone the compiler keeps a broadcast pair
+  // per product: twice the registers and a move per step).
+  auto pin_pair = [&](int k) { asm volatile("" : "+v"(pp[k])); };
+#pragma unroll
+  for (int k = 0; k < H / 2; ++k) pin_pair(k);
+  // The head of a row group at slots i .. i+3: a[k] = (S_{i+k} + p(i+k+1)) + .. + p(i+3), and
+  // s moves on to S_{i+4}.
+  auto heads = [&](int i, float& s, float (&a)[4]) {
+    float sp[4];  // S_i .. S_{i+3}
+    sp[0] = s;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) sp[k] = clique_term<T, EXACT>(sp[k - 1], w, p(i + k - 1));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      a[k] = sp[k];
+#pragma unroll
+      for (int j = i + k + 1; j < i + 4; ++j) a[k] = clique_term<T, EXACT>(a[k], w, p(j));
+    }
+    s = clique_term<T, EXACT>(sp[3], w, p(i + 3));
+  };
+  // A low-half group leaves its slots: o = {padding, the low lanes' p(i + k)} is the own term of
+  // its rows on the high lanes, and the low lanes' slots take the padding.
+  auto hand_own = [&](int i, v4f& o) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float own = pad, slot = p(i + k);
+      half_swap(own, slot);
+      o[k] = own;
+      pp[(i + k) >> 1][(i + k) & 1] = slot;
+    }
+    pin_pair(i >> 1);
+    pin_pair((i >> 1) + 1);
+  };
+  auto store4 = [&](int row0, v4f q) {
+    int orow[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) orow[k] = row0 + k < m ? t[4 + kCliqueHalfMax + row0 + k + opaque_zero()] : -1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (hi && orow[k] >= 0) Io<T>::st1(pout + static_cast<int64_t>(orow[k]) * ld_out, e, q[k]);
+  };
+  // rows 0 .. H-1: sweep g carries group g on the low lanes and group g - 1 on the high lanes
+  float s = -0.f;
+  float a[4];
+  v4f own = {pad, pad, pad, pad}, own_next;
+  heads(0, s, a);
+  hand_own(0, own_next);
+  v4f q = {a[0], a[1], a[2], a[3]};
+  static_for<H / 4 + 1>([&](auto G) __attribute__((always_inline)) {
+    constexpr int g = decltype(G)::value;
+#pragma unroll
+    for (int j = 0; j < H; ++j) q = clique_term4<T, EXACT>(q, w, v4f{p(j), p(j), p(j), p(j)});
+    q = clique_term4<T, EXACT>(q, w, own);
+    if constexpr (g > 0) store4(4 * (g - 1), q);
+    own = own_next;
+    if constexpr (g + 1 < H / 4) {
+      heads(4 * (g + 1), s, a);
+      hand_own(4 * (g + 1), own_next);
+    }
+    if constexpr (g < H / 4) {
+      // {low: the next group's heads (after the last group: unused), high: the low lanes' chains}
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float low = a[k], chain = q[k];
+        half_swap(low, chain);
+        q[k] = low;
+      }
+    }
+  });
+  // rows H .. MMAX-1 on the high lanes: K3c1's loop over their slots, from the low lanes' S_H
+  float s_low = s;
+  half_swap(s, s_low);
+  static_for<H / 4>([&](auto G) __attribute__((always_inline)) {
+    constexpr int i = 4 * decltype(G)::value;
+    if (H + i < m) {  // wave-uniform: the groups past the last member are padding
+      heads(i, s, a);
+      q = v4f{a[0], a[1], a[2], a[3]};
+#pragma unroll
+      for (int j = i + 4; j < H; ++j) q = clique_term4<T, EXACT>(q, w, v4f{p(j), p(j), p(j), p(j)});
+      q = clique_term4<T, EXACT>(q, w, v4f{p(i), p(i + 1), p(i + 2), p(i + 3)});
+      store4(H + i, q);
+    }
+  });
+}
+
+template <bool EXACT, typename T>
+int32_t launch_round_clique_half(const T* pin, int64_t ld_in, T* pout, int64_t ld_out, int64_t n,
+                                 const int32_t* table, int32_t n_cliques, int32_t mmax, hipStream_t s) {
+  const int64_t blocks = (n + kHalfCols - 1) / kHalfCols;
+  if (blocks > 0x7fffffffLL) return fail(TAL_ERR_INVALID, "clique round (two lanes per column): grid too large");
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_cliques));
+  // MMAX close to the block size keeps the -0.0 padding steps few; 160 also takes the smaller
+  // blocks a hand-built table may carry
+  return with_ceil_int<160, 192, 224, 256>(mmax, [&](auto M) {
+    k_round_clique_half<decltype(M)::value, EXACT, T><<<grid, kBlock, 0, s>>>(pin, ld_in, pout, ld_out, n, table);
+    return check_launch("clique round kernel (two lanes per column)");
+  });
+}
+
+// ------------------------------------------------------------------------------------------
 // K3q: a sequential round in one launch, in place on one pool.  Rows run in plan order and row r
 // reads the pool as rows 0 .. r-1 of the call left it (the reference's round under one
 // aggregation thread: decentralized_client.py:413 overwrites the model later apps of the round
@@ -5047,8 +5232,9 @@ int32_t agg_round(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, 
 // tal_agg_round_clique_<T> / _w_<T> and, COL, tal_agg_round_clique_col_<T> / _col_w_<T> (WSRC:
 // per-source weights from wtab_dev).  K3c: a column pair is one 8-B (fp32) or 4-B (bf16) access,
 // which sets the alignment rule, and too many blocks are found at the launch.  K3c1, one column
-// per lane: any ld, element-aligned pools.
-template <typename T, bool COL, bool WSRC>
+// per lane: any ld, element-aligned pools.  FORM 2, tal_agg_round_clique_half_<T>: K3c2, two lanes
+// per column, K3c1's checks with blocks of up to 256 members (uniform weights only).
+template <typename T, int FORM, bool WSRC>
 int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* pool_out, int64_t ld_out, int64_t n,
                          const int32_t* table_dev, int32_t n_cliques, int32_t mmax, int32_t mode, void* stream,
                          const float* wtab_dev = nullptr) {
@@ -5056,9 +5242,10 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
   if (!pool_in || !pool_out || !table_dev || (WSRC && !wtab_dev)) return fail(TAL_ERR_INVALID, name + ": null pointer");
   if (pool_in == pool_out) return fail(TAL_ERR_INVALID, name + ": the clique round runs out of place");
   if (n < 0 || ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, name + ": bad n / ld");
-  if constexpr (COL) {
-    if (n_cliques < 0 || n_cliques > 65535 || mmax < 1 || mmax > kCliqueColMax)
-      return fail(TAL_ERR_INVALID, name + ": 0 <= n_cliques <= 65535, 1 <= mmax <= 128");
+  if constexpr (FORM != 0) {
+    constexpr int kCap = FORM == 2 ? kCliqueHalfMax : kCliqueColMax;
+    if (n_cliques < 0 || n_cliques > 65535 || mmax < 1 || mmax > kCap)
+      return fail(TAL_ERR_INVALID, name + ": 0 <= n_cliques <= 65535, 1 <= mmax <= " + std::to_string(kCap));
   } else {
     if (n_cliques < 0 || mmax < 1 || mmax > kCliqueMax)
       return fail(TAL_ERR_INVALID, name + ": n_cliques >= 0, 1 <= mmax <= 64");
@@ -5070,7 +5257,9 @@ int32_t agg_round_clique(const char* fn, const T* pool_in, int64_t ld_in, T* poo
   hipStream_t s = static_cast<hipStream_t>(stream);
   return with_bool(mode == TAL_MODE_EXACT, [&](auto ex) {
     constexpr bool kExact = decltype(ex)::value;
-    if constexpr (COL)
+    if constexpr (FORM == 2)
+      return launch_round_clique_half<kExact, T>(pool_in, ld_in, pool_out, ld_out, n, table_dev, n_cliques, mmax, s);
+    else if constexpr (FORM == 1)
       return launch_round_clique_col<kExact, T, WSRC>(pool_in, ld_in, pool_out, ld_out, n, table_dev, wtab_dev, n_cliques,
                                                       mmax, s);
     else
@@ -5273,56 +5462,70 @@ const char* tal_round_kernel_name(const tal_round_plan_info* info, int32_t bf16)
 int32_t tal_agg_round_clique_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                  int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                  int32_t mode, void* stream) {
-  return agg_round_clique<float, false, false>("tal_agg_round_clique_f32", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<float, 0, false>("tal_agg_round_clique_f32", pool_in, ld_in, pool_out, ld_out, n,
                                                table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                   int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                   int32_t mode, void* stream) {
-  return agg_round_clique<uint16_t, false, false>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<uint16_t, 0, false>("tal_agg_round_clique_bf16", pool_in, ld_in, pool_out, ld_out, n,
                                                   table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_col_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                      int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                      int32_t mode, void* stream) {
-  return agg_round_clique<float, true, false>("tal_agg_round_clique_col_f32", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<float, 1, false>("tal_agg_round_clique_col_f32", pool_in, ld_in, pool_out, ld_out, n,
                                               table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_col_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                       int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                       int32_t mode, void* stream) {
-  return agg_round_clique<uint16_t, true, false>("tal_agg_round_clique_col_bf16", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<uint16_t, 1, false>("tal_agg_round_clique_col_bf16", pool_in, ld_in, pool_out, ld_out, n,
                                                  table_dev, n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_half_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
+                                      int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                      int32_t mode, void* stream) {
+  return agg_round_clique<float, 2, false>("tal_agg_round_clique_half_f32", pool_in, ld_in, pool_out, ld_out, n,
+                                           table_dev, n_cliques, mmax, mode, stream);
+}
+
+int32_t tal_agg_round_clique_half_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                       int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
+                                       int32_t mode, void* stream) {
+  return agg_round_clique<uint16_t, 2, false>("tal_agg_round_clique_half_bf16", pool_in, ld_in, pool_out, ld_out, n,
+                                              table_dev, n_cliques, mmax, mode, stream);
 }
 
 int32_t tal_agg_round_clique_col_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                        int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                        int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique<float, true, true>("tal_agg_round_clique_col_w_f32", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<float, 1, true>("tal_agg_round_clique_col_w_f32", pool_in, ld_in, pool_out, ld_out, n,
                                              table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_col_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                         int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                         int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique<uint16_t, true, true>("tal_agg_round_clique_col_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<uint16_t, 1, true>("tal_agg_round_clique_col_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
                                                 table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_w_f32(const float* pool_in, int64_t ld_in, float* pool_out, int64_t ld_out,
                                    int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                    int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique<float, false, true>("tal_agg_round_clique_w_f32", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<float, 0, true>("tal_agg_round_clique_w_f32", pool_in, ld_in, pool_out, ld_out, n,
                                               table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 
 int32_t tal_agg_round_clique_w_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                     int64_t n, const int32_t* table_dev, int32_t n_cliques, int32_t mmax,
                                     int32_t mode, void* stream, const float* wtab_dev) {
-  return agg_round_clique<uint16_t, false, true>("tal_agg_round_clique_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
+  return agg_round_clique<uint16_t, 0, true>("tal_agg_round_clique_w_bf16", pool_in, ld_in, pool_out, ld_out, n,
                                                  table_dev, n_cliques, mmax, mode, stream, wtab_dev);
 }
 

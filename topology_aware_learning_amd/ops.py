@@ -399,6 +399,14 @@ CLIQUE_COL_WWORDS = CLIQUE_COL_MAX  # TAL_CLIQUE_COL_WWORDS (128): one weight pe
 # - all four, by 2.0x to 5.2x, the forms agreeing bit for bit
 WCLIQUE_COL_DEFAULT = {(False, MODE_EXACT): True, (False, MODE_FMA): True,
                        (True, MODE_EXACT): True, (True, MODE_FMA): True}
+CLIQUE_HALF_MAX = 256     # TAL_CLIQUE_HALF_MAX: members of a block of the two-lanes-per-column form (K3c2)
+CLIQUE_HALF_WORDS = 4 + 2 * CLIQUE_HALF_MAX  # TAL_CLIQUE_HALF_WORDS (516)
+# (bf16, mode): whether default_plan admits uniform-weight blocks of 129..256 members (K3c2, spec
+# {"clique": 1, "members": 256}).  All off: the form is reached by build_clique_plan(max_members=256),
+# plan_from_spec and the tuner's opt-in candidate; a line is switched on with measurements against
+# the default of the same round (tools/clique_half_rate.py), as the tables above were
+CLIQUE_HALF_DEFAULT = {(False, MODE_EXACT): False, (False, MODE_FMA): False,
+                       (True, MODE_EXACT): False, (True, MODE_FMA): False}
 
 
 def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_source: bool = False,
@@ -424,9 +432,15 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_
 
     wide_per_source: with per_source, lifts the per-source limit from 64 to 128 members too
     (K3c1 with per-source weights, tal_agg_round_clique_col_w_*); without it per_source with
-    max_members > 64 is a ValueError, as it was before that form existed."""
-    if max_members > CLIQUE_COL_MAX:
+    max_members > 64 is a ValueError, as it was before that form existed.
+
+    max_members=256 (that one value past 128) admits uniform-weight blocks of 129..256 sources
+    too: the two-lanes-per-column form (K3c2, tal_agg_round_clique_half_*), which like K3c1 has no
+    attached rows.  It has no per-source weights: with per_source it is a ValueError."""
+    if max_members > CLIQUE_COL_MAX and max_members != CLIQUE_HALF_MAX:
         raise ValueError(f"clique blocks have at most {CLIQUE_COL_MAX} members")
+    if per_source and max_members == CLIQUE_HALF_MAX:
+        raise ValueError(f"per-source clique blocks have at most {CLIQUE_COL_MAX} members")
     if per_source and max_members > CLIQUE_MAX and not wide_per_source:
         raise ValueError(f"per-source clique blocks have at most {CLIQUE_MAX} members")
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
@@ -514,7 +528,9 @@ class CliquePlan:
     rule), launched after the K3c blocks of `table`; clique_sources and clique_rows count both.
     A plan is per-source as a whole: built with wide_per_source, its blocks of 65..128 members
     carry `col_wtable` (CLIQUE_COL_WWORDS float32 per block beside `col_table`, whose weight word
-    is then 0) and run tal_agg_round_clique_col_w_*."""
+    is then 0) and run tal_agg_round_clique_col_w_*.  Uniform-weight blocks of 129..256 members
+    (build_clique_plan(max_members=256)) are `half_table`: n_half records of CLIQUE_HALF_WORDS for
+    K3c2 (tal_agg_round_clique_half_*, two lanes per column), launched after K3c1's."""
     table: np.ndarray
     n_cliques: int
     mmax: int
@@ -536,6 +552,10 @@ class CliquePlan:
     col_device: Optional[torch.Tensor] = None
     col_wtable: Optional[np.ndarray] = None
     col_wdevice: Optional[torch.Tensor] = None
+    half_table: Optional[np.ndarray] = None
+    n_half: int = 0
+    half_mmax: int = 0
+    half_device: Optional[torch.Tensor] = None
     on: Optional[torch.device] = None  # where the device copies are (to)
 
     @property
@@ -557,13 +577,14 @@ class CliquePlan:
 
     def make_spec(self) -> dict:
         """The spec plan_from_spec rebuilds this plan from: its name, "members": 128 when it has
-        blocks of 65..128 members, and its rest plan's spec."""
-        return {self.spec_key: 1, **({"members": CLIQUE_COL_MAX} if self.n_col else {}),
+        blocks of 65..128 members (256: of 129..256), and its rest plan's spec."""
+        members = CLIQUE_HALF_MAX if self.n_half else CLIQUE_COL_MAX if self.n_col else None
+        return {self.spec_key: 1, **({"members": members} if members else {}),
                 "rest": self.rest.spec if self.rest is not None else None}
 
     def to(self, device) -> "CliquePlan":
         for host, attr in ((self.table, "device"), (self.wtable, "wdevice"), (self.col_table, "col_device"),
-                           (self.col_wtable, "col_wdevice")):
+                           (self.col_wtable, "col_wdevice"), (self.half_table, "half_device")):
             if host is not None:
                 setattr(self, attr, torch.from_numpy(host).to(device))
         self.on = self.device.device
@@ -580,14 +601,15 @@ class CliquePlan:
         att = t[:, 4 + 2 * CLIQUE_MAX:].reshape(self.n_cliques, CLIQUE_EXTRA, CLIQUE_EXTRA_WORDS)
         att = att[np.arange(CLIQUE_EXTRA)[None, :] < t[:, 2:3]]  # attached records in use
         ct = (self.col_table if self.col_table is not None else np.zeros(0, np.int32)).reshape(self.n_col, CLIQUE_COL_WORDS)
+        ht = (self.half_table if self.half_table is not None else np.zeros(0, np.int32)).reshape(self.n_half, CLIQUE_HALF_WORDS)
         return (max(t[:, 4: 4 + CLIQUE_MAX].max(initial=-1), att[:, [5, 7, 8]].max(initial=-1),
-                    ct[:, 4: 4 + CLIQUE_COL_MAX].max(initial=-1)),
+                    ct[:, 4: 4 + CLIQUE_COL_MAX].max(initial=-1), ht[:, 4: 4 + CLIQUE_HALF_MAX].max(initial=-1)),
                 max(t[:, 4 + CLIQUE_MAX: 4 + 2 * CLIQUE_MAX].max(initial=-1), att[:, 0].max(initial=-1),
-                    ct[:, 4 + CLIQUE_COL_MAX:].max(initial=-1)))
+                    ct[:, 4 + CLIQUE_COL_MAX:].max(initial=-1), ht[:, 4 + CLIQUE_HALF_MAX:].max(initial=-1)))
 
 
 def _clique_head(rec, wrec, cap, srcs, w32, outs):
-    """A block's head in a record of either layout (cap = CLIQUE_MAX or CLIQUE_COL_MAX members):
+    """A block's head in a record of any layout (cap = CLIQUE_MAX, CLIQUE_COL_MAX or CLIQUE_HALF_MAX members):
     member count, weight - per source into wrec where the plan has a weight table, else the
     record's weight word - sources, and output rows (-1: none)."""
     rec[0] = len(srcs)
@@ -613,14 +635,20 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
     max_members (find_cliques): up to 128 admits uniform-weight blocks of 65..128 sources, which
     go to `col_table` (K3c1); blocks of <= 64 stay in `table` with their attached rows.
     wide_per_source (find_cliques): per-source blocks of 65..128 sources too; they go to
-    `col_table` + `col_wtable` (no attached rows: rows beside them go to the rest plan)."""
+    `col_table` + `col_wtable` (no attached rows: rows beside them go to the rest plan).
+    max_members=256: uniform-weight blocks of 129..256 sources go to `half_table` (K3c2); the
+    smaller blocks land where they land under 128."""
     row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
     cliques, rest = find_cliques(row_ptr, col, w, out_row, min_rows, per_source=per_source,
                                  max_members=max_members, wide_per_source=wide_per_source)
     if not cliques:
         return None
-    wide = [c for c in cliques if len(c[0]) > CLIQUE_MAX]
+    half = [c for c in cliques if len(c[0]) > CLIQUE_COL_MAX]
+    wide = [c for c in cliques if CLIQUE_MAX < len(c[0]) <= CLIQUE_COL_MAX]
     cliques = [c for c in cliques if len(c[0]) <= CLIQUE_MAX]
+    half_table = np.zeros((len(half), CLIQUE_HALF_WORDS), np.int32) if half else None
+    for k, (srcs, w32, outs, _) in enumerate(half):
+        _clique_head(half_table[k], None, CLIQUE_HALF_MAX, srcs, w32, outs)
     col_table = np.zeros((len(wide), CLIQUE_COL_WORDS), np.int32) if wide else None
     col_wtable = np.ones((len(wide), CLIQUE_COL_WWORDS), np.float32) if wide and per_source else None
     for k, (srcs, w32, outs, _) in enumerate(wide):
@@ -655,13 +683,15 @@ def build_clique_plan(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS,
             raise ValueError("a bf16 clique plan's other rows take a sparse or narrow plan (dense_rb 0, stream_cs 0)")
     mmax = max((len(c[0]) for c in cliques), default=0)
     return CliquePlan(table=table.reshape(-1), n_cliques=len(cliques), mmax=mmax,
-                      clique_sources=sum(len(c[0]) for c in cliques + wide) + n_ext_loads,
-                      clique_rows=sum(len(c[2]) + len(c[3]) for c in cliques + wide), rest=rest_plan,
+                      clique_sources=sum(len(c[0]) for c in cliques + wide + half) + n_ext_loads,
+                      clique_rows=sum(len(c[2]) + len(c[3]) for c in cliques + wide + half), rest=rest_plan,
                       full=build_plan(row_ptr, col, w, out_row, dense=0), rows=len(out_row), rest_rows=rest,
                       wtable=wtable.reshape(-1) if per_source else None,
                       col_table=col_table.reshape(-1) if wide else None, n_col=len(wide),
                       col_mmax=max((len(c[0]) for c in wide), default=0),
-                      col_wtable=col_wtable.reshape(-1) if col_wtable is not None else None)
+                      col_wtable=col_wtable.reshape(-1) if col_wtable is not None else None,
+                      half_table=half_table.reshape(-1) if half else None, n_half=len(half),
+                      half_mmax=max((len(c[0]) for c in half), default=0))
 
 
 def _sub_csr(row_ptr, col, w, out_row, rows):
@@ -732,6 +762,7 @@ _CLIQUE_VARIANTS = {
     "clique128": (dict(max_members=CLIQUE_COL_MAX), CLIQUE_COL_DEFAULT, lambda p: p.n_col > 0),
     "wclique128": (dict(per_source=True, max_members=CLIQUE_COL_MAX, wide_per_source=True), WCLIQUE_COL_DEFAULT,
                    lambda p: p.col_wtable is not None),
+    "clique256": (dict(max_members=CLIQUE_HALF_MAX), CLIQUE_HALF_DEFAULT, lambda p: p.n_half > 0),
 }
 
 
@@ -745,8 +776,11 @@ def _clique_variant(name, row_ptr, col, w, out_row, bf16) -> Optional[CliquePlan
     return p
 
 
-def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT):
-    """tune_plan's candidates [(key, plan)], the default plan first (host-side plans)."""
+def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT, clique_half: bool = False):
+    """tune_plan's candidates [(key, plan)], the default plan first (host-side plans).
+    clique_half: also offer the plan with blocks of 129..256 members (K3c2, key "clique256") where
+    the round has such a block; on request only while CLIQUE_HALF_DEFAULT is off, so the candidate
+    lists of rounds past 128 members stay what they were."""
     base = default_plan(row_ptr, col, w, out_row, bf16=bf16, mode=mode)
     if base.spec is None:
         base.spec = {}
@@ -779,8 +813,12 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
         # takes; per-source plans (weighted / centrality apps on cliques) do not count against a
         # uniform-weight variant
         have = [c for _, c in cands if isinstance(c, CliquePlan)]
-        per, wide = kw.get("per_source", False), "max_members" in kw
-        if any((c.wtable is not None or not per) and (c.n_col > 0 or not wide) for c in have):
+        per, members = kw.get("per_source", False), kw.get("max_members", CLIQUE_MAX)
+        wide, half = members == CLIQUE_COL_MAX, members == CLIQUE_HALF_MAX
+        if half and not clique_half:
+            continue
+        if any((c.wtable is not None or not per) and (c.n_col > 0 or not wide) and (c.n_half > 0 or not half)
+               for c in have):
             continue
         p = _clique_variant(name, row_ptr, col, w, out_row, bf16)
         if p is not None and p.clique_rows > max((c.clique_rows for c in have if per or c.wtable is None), default=0):
@@ -790,7 +828,7 @@ def tune_candidates(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MO
 
 def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.Tensor,
               n: Optional[int] = None, reps: int = 5, mode: int = MODE_EXACT,
-              margin: float = 0.01) -> RoundPlan:
+              margin: float = 0.01, clique_half: bool = False) -> RoundPlan:
     """Pick the plan by measurement, anchored on the untimed default (default_plan).
 
     Candidates are the forms that have won a measured round on some BASELINE config (DESIGN §4
@@ -808,12 +846,13 @@ def tune_plan(row_ptr, col, w, out_row, pool_in: torch.Tensor, pool_out: torch.T
     again (its median comes from that run).  A candidate replaces the default only when its
     median beats the default's by more than `margin` (round 4: the tuner's single short timings
     once kept a plan slower than the default - 23.74 vs 22.89 ms).  pool_out must not alias
-    pool_in."""
+    pool_in.  clique_half: time the K3c2 plan too where the round has a block of 129..256 members
+    (tune_candidates)."""
     if pool_in.data_ptr() == pool_out.data_ptr():
         raise ValueError("tune_plan needs distinct input / output pools")
     bf16 = pool_in.dtype == torch.bfloat16  # bf16 rounds: sparse, narrow and clique plans
     run = round_bf16 if bf16 else round_f32  # (not round_pool: an int64 pool is refused)
-    cands = tune_candidates(row_ptr, col, w, out_row, bf16=bf16, mode=mode)
+    cands = tune_candidates(row_ptr, col, w, out_row, bf16=bf16, mode=mode, clique_half=clique_half)
     base = cands[0][1]
     if isinstance(base, CliquePlan) and base.rest is not None:  # the rows outside the cliques: tuned too
         r_rp, r_col, r_w, r_out = _sub_csr(row_ptr, col, w, out_row, base.rest_rows)
@@ -881,6 +920,9 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     """The plan the round components build when they do not time candidates (tune=False).
     A round with clique blocks takes the first clique variant (_CLIQUE_VARIANTS) that finds
     blocks of its kind, in this order of preference:
+      clique256   a uniform-weight block of 129..256 members (`unweighted_fl` over 200 or 256
+                  clients): K3c2, spec {"clique": 1, "members": 256}; gated by CLIQUE_HALF_DEFAULT,
+                  which is off for every dtype and mode
       clique128   a uniform-weight block of 65..128 members (`unweighted_fl` over 66 or 100
                   clients): K3c1, spec {"clique": 1, "members": 128}; gated by CLIQUE_COL_DEFAULT
       clique      uniform-weight blocks of <= 64 members: K3c, spec {"clique": 1}; never gated
@@ -918,7 +960,7 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
             raise ValueError("MODE_MATRIX runs bf16 pools only (tal_agg.h K3m)")
         return build_matrix_plan(row_ptr, col, w, out_row)
     try:
-        for name in ("clique128", "clique", "wclique128", "wclique"):
+        for name in ("clique256", "clique128", "clique", "wclique128", "wclique"):
             gate = _CLIQUE_VARIANTS[name][1]
             if gate is None or gate[bool(bf16), int(mode)]:
                 cp = _clique_variant(name, row_ptr, col, w, out_row, bf16)
@@ -964,7 +1006,7 @@ def round_kernel_name(plan, bf16: bool = False) -> str:
     info, asked from the library (tal_round_kernel_name: the function its launch dispatches on);
     clique plans name the K3c kernel (their rest rows run a second one)."""
     if isinstance(plan, CliquePlan):
-        return "k_round_clique" if plan.n_cliques > 0 else "k_round_clique_col"
+        return "k_round_clique" if plan.n_cliques > 0 else "k_round_clique_col" if plan.n_col > 0 else "k_round_clique_half"
     if isinstance(plan, RowCallPlan):
         return "k_agg (one call per row)"
     info = plan.info if isinstance(plan, RoundPlan) else plan
@@ -1078,12 +1120,13 @@ def _round_clique(seg: Segment, pool_in, pool_out, plan: CliquePlan, n, mode, st
     _check_plan_rows(plan, pool_in, pool_out)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     # K3c for the blocks of <= 64 members, then K3c1 for those of 65..128, each with per-source
-    # weights where the plan carries them
-    for col_form, table, blocks, mmax, wtab in (
-            (False, plan.device, plan.n_cliques, plan.mmax, plan.wdevice if plan.wtable is not None else None),
-            (True, plan.col_device, plan.n_col, plan.col_mmax, plan.col_wdevice if plan.col_wtable is not None else None)):
+    # weights where the plan carries them, then K3c2 for those of 129..256
+    for form, table, blocks, mmax, wtab in (
+            ("", plan.device, plan.n_cliques, plan.mmax, plan.wdevice if plan.wtable is not None else None),
+            ("_col", plan.col_device, plan.n_col, plan.col_mmax, plan.col_wdevice if plan.col_wtable is not None else None),
+            ("_half", plan.half_device, plan.n_half, plan.half_mmax, None)):
         if blocks > 0:
-            _call("tal_agg_round_clique" + "_col" * col_form + "_w" * (wtab is not None), seg,
+            _call("tal_agg_round_clique" + form + "_w" * (wtab is not None), seg,
                   (ptr(pool_in), pool_in.stride(0), ptr(pool_out), pool_out.stride(0), n, ptr(table), blocks, mmax),
                   mode, _stream(pool_in.device, stream), *((ptr(wtab),) if wtab is not None else ()))
     if plan.rest is not None:
