@@ -63,7 +63,8 @@ const char* tal_last_error(void);
  * (tal_agg_round_clique_col_w_*).  ABI 35 added the sequential round in one launch (K3q:
  * tal_seq_plan_*, tal_agg_round_seq_*).  ABI 36 added TAL_MODE_MATRIX: rounds on bf16 pools on the
  * matrix cores (K3m: tal_matrix_plan_*, tal_agg_round_matrix_bf16).  ABI 37 added the clique
- * entries for blocks of up to 256 members (K3c2: tal_agg_round_clique_half_*). */
+ * entries for blocks of up to 256 members (K3c2: tal_agg_round_clique_half_*).  ABI 38 added the
+ * shared sum of matrix-mode rows with identical operands (K3ms: tal_agg_round_shared_bf16). */
 int32_t tal_abi_version(void);
 
 /* ---- K1: one aggregation call over M flattened operands --------------------------------
@@ -585,6 +586,70 @@ int32_t tal_matrix_plan_build(int32_t rows, const int32_t* row_ptr_host, const i
 int32_t tal_agg_round_matrix_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
                                   int64_t pool_rows, int64_t n, const int32_t* plan_dev,
                                   const tal_matrix_plan_info* info, void* stream);
+
+/* ---- K3ms: one shared sum for matrix-mode rows with identical operands (ABI 38) -------------
+ * Opt-in inside TAL_MODE_MATRIX, bf16 pools, out of place.  A CLASS is a set of >= 2 rows of the
+ * round whose operand multisets {(pool_in row, bits of fp32(w))} are equal: the operands' order
+ * does not matter, a source listed twice counts twice, and a row with a non-finite fp32 weight
+ * joins no class.  (`unweighted_fl`, a barbell's cliques, the weighted apps on complete graphs:
+ * every row of a block lists the same sources with the same weights.)  The class's operands
+ * sorted by (pool row, weight bits) are its canonical order, and every member row is written
+ *
+ *   acc = fl(w_0 x_0);  acc = fma(w_k, x_k, acc)  (k = 1 .. M-1, canonical order, fp32,
+ *   subnormals kept);  pool_out[out_row][e] = bf16(acc)  (nearest even, NaN stored as 0xFFFF)
+ *
+ * - one chain per class and column, read once per source and stored to each member row, so all
+ * rows of a class are bit-identical.  An fp32 FMA chain of M terms and one bf16 rounding:
+ *
+ *   |out - ref| <= 2^-8 |ref| + M 2^-24 sum_k |w_k x_k| (1 + small)
+ *
+ * which lies inside K3m's bound above; that bound stays the mode's single contract.
+ *
+ * Non-finite values: K3m's rule.  An element whose accumulator is not finite after the chain is
+ * recomputed, for every member row, as that row's own TAL_MODE_FMA chain over its operands in
+ * the caller's order (the table carries the members' CSR): a non-finite output is exactly FMA
+ * mode's.
+ *
+ * Rows outside the classes are not this entry's: in a shared plan they run the regular
+ * TAL_MODE_FMA plan of their sub-round (tal_agg_round_bf16) and CARRY FMA MODE'S BITS - within
+ * 2^-8 |ref| + M 2^-24 sum |w x| of the reference, inside the matrix bound, so the mode's promise
+ * holds for every row of the round.
+ *
+ * Lanes.  A lane owns 8 columns (16-B loads and stores) where both pools are 16-B aligned with
+ * ld % 8 == 0, 4 columns where they are 8-B aligned with ld % 4 == 0, one column otherwise and
+ * for the n % 8 (n % 4) tail.  No pool is refused for its alignment.
+ *
+ * Table (int32 words, built by the caller, copied to the device, 8-B aligned; offsets in
+ * tal_shared_plan_info):
+ *   cls[n_classes][4]   {first source record, sources, first member, members (>= 2)}
+ *   src[n_src][2]       (off_src even) {pool_in row, bits of the fp32 weight}, a class's records
+ *                       consecutive and in canonical order
+ *   out_row[n_out]      pool_out row of each member, a class's members consecutive
+ *   row_ptr[n_out+1], col[nnz], w[nnz] (fp32 bits)   the members' rows as the caller gave them
+ *
+ * tal_agg_round_shared_bf16: pool_rows = rows of the smaller of the two pools.  TAL_ERR_INVALID,
+ * with no launch, for a null pointer, pool_out == pool_in, n < 0, ld < n, an info that is not a
+ * shared plan's, a table_dev that is not 8-B aligned or a table row >= pool_rows (info->max_row,
+ * the largest row read or written); n == 0 returns TAL_OK without a launch. */
+typedef struct tal_shared_plan_info {
+  int32_t n_classes;
+  int32_t n_src;         /* source records over all classes */
+  int32_t n_out;         /* member rows over all classes */
+  int32_t nnz;           /* operands of the member rows (= sum over classes of sources x members) */
+  int32_t max_src;       /* sources of the widest class */
+  int32_t max_row;       /* largest pool row read or written */
+  /* offsets (int32 words) of the arrays inside the table */
+  int32_t off_cls;
+  int32_t off_src;
+  int32_t off_out_row;
+  int32_t off_row_ptr;
+  int32_t off_col;
+  int32_t off_w;
+  int64_t words;         /* total int32 words of the table */
+} tal_shared_plan_info;
+int32_t tal_agg_round_shared_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                  int64_t pool_rows, int64_t n, const int32_t* table_dev,
+                                  const tal_shared_plan_info* info, void* stream);
 
 /* tal_agg_round_f32's round on bf16 pools (arithmetic as tal_agg_bf16, per mode).  Takes sparse plans
  * (c4 64 / 128, dense_rb 0) and narrow plans (c4 16 / 32); TAL_ERR_INVALID for dense or

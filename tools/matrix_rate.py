@@ -5,7 +5,10 @@ same round on bf16 pools (not part of the product).  Five rounds:
   (c) config 4: barbell(60, 8) at ResNet-50's width (23,573,962 elements), unweighted
   (d) complete 100 at ResNet-50's width, unweighted (`unweighted_fl` over 100 clients)
   (e) complete 700 at the CIFAR-CNN width (5,851,338 elements), unweighted (`unweighted_fl`, 700 clients)
-Both forms run ops.round_pool out of place between the same two pools; each is warmed, then timed
+A third form where the round has rows with identical operands: the matrix mode's shared plan
+(K3ms, default_plan(mode=MODE_MATRIX, shared=True): one sum per row class, the other rows in FMA
+mode); a round without a class has no such plan and prints no "shared" figures.
+All forms run ops.round_pool out of place between the same two pools; each is warmed, then timed
 `--reps` times (default 10) with HIP events, the forms alternating repetition by repetition.  One
 JSON line per round: median / min / max per form, the algorithmic bytes (every distinct source
 read once, every row written once) and each form's share of 8 TB/s at its median, the FMA form's
@@ -53,7 +56,10 @@ def measure(dev, name, spec, n, reps) -> None:
     out = np.arange(m, dtype=np.int32)
     plans = {"fma": ops.default_plan(rp, col, w, out, bf16=True, mode=ops.MODE_FMA).to(dev),
              "matrix": ops.default_plan(rp, col, w, out, bf16=True, mode=ops.MODE_MATRIX).to(dev)}
-    modes = {"fma": ops.MODE_FMA, "matrix": ops.MODE_MATRIX}
+    modes = {"fma": ops.MODE_FMA, "matrix": ops.MODE_MATRIX, "shared": ops.MODE_MATRIX}
+    sp = ops.default_plan(rp, col, w, out, bf16=True, mode=ops.MODE_MATRIX, shared=True)
+    if isinstance(sp, ops.SharedPlan):  # a round without a class: the same MatrixPlan, not timed twice
+        plans["shared"] = sp.to(dev)
     ld = -(-n // 64) * 64
     pin = torch.empty((m, ld), dtype=torch.bfloat16, device=dev).normal_()
     pout = torch.empty_like(pin)
@@ -61,9 +67,14 @@ def measure(dev, name, spec, n, reps) -> None:
     res = dict(round=name, rows=m, operands=len(col), sources=len(set(col.tolist())), elements=n, reps=reps,
                fma_kernel=ops.round_kernel_name(plans["fma"], bf16=True),
                matrix_kblocks=int(plans["matrix"].info.n_kblocks), matrix_groups=int(plans["matrix"].info.n_groups))
+    if "shared" in plans:
+        i = plans["shared"].info
+        res.update(shared_classes=int(i.n_classes), shared_class_rows=int(i.n_out), shared_class_sources=int(i.n_src),
+                   shared_rest_rows=len(plans["shared"].rest_index))
     nbytes = 2 * n * (res["sources"] + m)
     ref = None
-    for k in ("fma", "matrix"):  # warm (code load) and compare
+    for k in plans:  # warm (code load) and compare with the FMA form
+        pout.zero_()
         ops.round_pool(pin, pout, plans[k], n, modes[k])
         torch.cuda.synchronize()
         head = pout[:, : min(n, 1 << 20)].float()
@@ -72,7 +83,8 @@ def measure(dev, name, spec, n, reps) -> None:
         else:
             step = ref.abs() * 2.0 ** -8
             ok = step > 0
-            res["max_diff_in_rounding_steps"] = round(float(((head - ref).abs()[ok] / step[ok]).max()), 3)
+            key = "max_diff_in_rounding_steps" + "_shared" * (k == "shared")
+            res[key] = round(float(((head - ref).abs()[ok] / step[ok]).max()), 3)
     del ref, head
     ts = {k: [] for k in plans}
     for _ in range(reps):  # forms alternate rep by rep: a clock drift does not favour one
@@ -88,6 +100,8 @@ def measure(dev, name, spec, n, reps) -> None:
                       hbm_share=round(nbytes / (med * 1e-3) / HBM_PEAK, 4))
     res["algorithmic_bytes"] = nbytes
     res["fma_vs_matrix"] = round(res["fma"]["median_ms"] / res["matrix"]["median_ms"], 3)
+    if "shared" in plans:
+        res["fma_vs_shared"] = round(res["fma"]["median_ms"] / res["shared"]["median_ms"], 3)
     print(json.dumps(res), flush=True)
 
 

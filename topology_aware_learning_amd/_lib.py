@@ -28,7 +28,7 @@ TAL_COMM_ID_BYTES = 128
 TAL_MODE_FMA = 0
 TAL_MODE_EXACT = 1
 TAL_MODE_MATRIX = 2
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 EXPORTED = (
     "tal_last_error",
@@ -64,6 +64,7 @@ EXPORTED = (
     "tal_matrix_plan_words",
     "tal_matrix_plan_build",
     "tal_agg_round_matrix_bf16",
+    "tal_agg_round_shared_bf16",
     "tal_cosine_plan_words",
     "tal_cosine_plan_build",
     "tal_cosine_plan_set_threads",
@@ -183,6 +184,14 @@ class MatrixPlanInfo(ctypes.Structure):
         "off_w", "off_out_row")] + [("words", ctypes.c_int64)]
 
 
+class SharedPlanInfo(ctypes.Structure):
+    """tal_shared_plan_info (tal_agg.h K3ms)."""
+
+    _fields_ = [(f, ctypes.c_int32) for f in (
+        "n_classes", "n_src", "n_out", "nnz", "max_src", "max_row", "off_cls", "off_src", "off_out_row",
+        "off_row_ptr", "off_col", "off_w")] + [("words", ctypes.c_int64)]
+
+
 class CosineRoundInfo(ctypes.Structure):
     """tal_cosine_round_info (tal_agg.h K2r)."""
 
@@ -250,6 +259,7 @@ _SIGS = {
     "tal_matrix_plan_words": (_I64, [_I32, _I64]),
     "tal_matrix_plan_build": (_I32, [_I32, _PI32, _PI32, _PD, _PI32, _PI32, _I64, ctypes.POINTER(MatrixPlanInfo)]),
     "tal_agg_round_matrix_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _I64, _P, ctypes.POINTER(MatrixPlanInfo), _P]),
+    "tal_agg_round_shared_bf16": (_I32, [_P, _I64, _P, _I64, _I64, _I64, _P, ctypes.POINTER(SharedPlanInfo), _P]),
     "tal_cosine_plan_words": (_I64, [_PI64, _I32]),
     "tal_cosine_plan_build": (_I32, [_PI64, _I32, _PI64, _I64, _PI32]),
     "tal_cosine_plan_set_threads": (_I32, [_PI64, _I32]),

@@ -48,7 +48,7 @@
 
 namespace {
 
-constexpr int kAbiVersion = 37;
+constexpr int kAbiVersion = 38;
 constexpr int kMaxOps = 256;     // operands per K1 launch (kernel-argument table, 3 KiB)
 constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr uint32_t kMaskUniform = 0x80000000u;  // dense table mask flag: one weight for all rows
@@ -5736,12 +5736,18 @@ struct MxPlan {
 
 // One output element as tal_agg_bf16's TAL_MODE_FMA chain over operands q0 .. q1-1 of the CSR:
 // the columns no strip takes and every element the matrix cores left non-finite.
-__device__ __noinline__ TAL_MX_DEVICE float mx_chain(const uint16_t* pin, int64_t ld_in, const int32_t* col, const float* w,
-                                       int q0, int q1, int64_t e) {
+// (mx_chain_steps: the chain itself, inlined where a call would cost a stack frame - K3ms)
+__device__ __forceinline__ TAL_MX_DEVICE float mx_chain_steps(const uint16_t* pin, int64_t ld_in, const int32_t* col,
+                                                              const float* w, int q0, int q1, int64_t e) {
   float acc = first1t<uint16_t, false>(w[q0], Io<uint16_t>::ld1(pin + static_cast<int64_t>(col[q0]) * ld_in, e));
   for (int q = q0 + 1; q < q1; ++q)
     acc = next1t<uint16_t, false>(acc, w[q], Io<uint16_t>::ld1(pin + static_cast<int64_t>(col[q]) * ld_in, e));
   return acc;
+}
+
+__device__ __noinline__ TAL_MX_DEVICE float mx_chain(const uint16_t* pin, int64_t ld_in, const int32_t* col, const float* w,
+                                       int q0, int q1, int64_t e) {
+  return mx_chain_steps(pin, ld_in, col, w, q0, q1, e);
 }
 
 __device__ __forceinline__ bool mx_finite(float v) { return __builtin_fabsf(v) <= 3.402823466e38f; }  // false for NaN
@@ -5903,6 +5909,210 @@ int32_t launch_round_matrix(const uint16_t* pin, int64_t ld_in, uint16_t* pout, 
     return check_launch("matrix round kernel (chain columns)");
   }
   return TAL_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// K3ms: the rows of a matrix-mode round whose operand multisets are equal, as ONE sum written to
+// every one of them (contract and table in tal_agg.h).  A class of R rows over S sources is read
+// S times and written R times per column: no chain per row, nothing to share between lanes, so
+// no LDS - the kernel is a stream of loads into registers and of stores out of them.
+//
+// Work split: a work item is (class, column strip), a strip being kShThreads lanes x LW columns;
+// a persistent grid (persistent_grid at what resident_per_cu answers) walks the items, class by
+// class, so neighbouring workgroups read neighbouring strips of the same sources.  A lane owns LW
+// consecutive columns - 8 (one 16-B load per source), 4 (8 B) or 1 by the pools' alignment - and
+// LW fp32 accumulators.  The class's (pool row, weight) records are wave-uniform: read through
+// the constant address space they are scalar loads, kShBatch records and then kShBatch data loads
+// in flight with no branch between them; the remainder of a class runs as batches of 4, 2 and 1.
+// acc starts at -0.0, so fma(w_0, x_0, acc) is fl(w_0 x_0) with its sign of zero, and every
+// further term is one fma: the canonical chain.  The accumulators are rounded and packed once
+// (Io<uint16_t>) and the packed registers stored to each of the class's output rows.
+//
+// Non-finite accumulators: a lane that holds one stores its finite elements one by one and then,
+// with the accumulators dead, recomputes the others per member row as that row's own FMA chain
+// (mx_chain's steps over the members' CSR, one inlined loop: a call to mx_chain itself made the
+// kernel reserve 96-112 B of scratch per lane for the callee's frame), so no dispatch reserves
+// scratch.
+// ------------------------------------------------------------------------------------------
+constexpr int kShThreads = 256;
+constexpr int kShBatch = 8;
+
+struct ShPlan {
+  const int32_t* cls;      // [n_classes][4]: first source record, sources, first member, members
+  const int32_t* src;      // [n_src][2]: pool_in row, fp32 weight bits (canonical order)
+  const int32_t* out_row;  // [n_out]: pool_out row of each member
+  const int32_t* row_ptr;  // [n_out + 1], col, w: the members' own CSR, for the chain
+  const int32_t* col;
+  const float* w;
+};
+
+typedef int32_t i32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(4))) const i32x2* ConstI32x2;
+
+// LW columns of one pool row as loaded / as stored, and their fp32 values
+template <int LW>
+struct ShLane;
+
+template <>
+struct ShLane<8> {
+  typedef u32x4 raw_t;
+  static __device__ __forceinline__ raw_t ld(const uint16_t* row, int64_t e) {
+    return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + e));
+  }
+  static __device__ __forceinline__ void widen(raw_t q, float* x) {
+    const float4 a = Io<uint16_t>::f4(u32x2{q.x, q.y}), b = Io<uint16_t>::f4(u32x2{q.z, q.w});
+    x[0] = a.x, x[1] = a.y, x[2] = a.z, x[3] = a.w, x[4] = b.x, x[5] = b.y, x[6] = b.z, x[7] = b.w;
+  }
+  static __device__ __forceinline__ raw_t pack(const float* a) {
+    const u32x2 lo = Io<uint16_t>::pack(make_float4(a[0], a[1], a[2], a[3]));
+    const u32x2 hi = Io<uint16_t>::pack(make_float4(a[4], a[5], a[6], a[7]));
+    return u32x4{lo.x, lo.y, hi.x, hi.y};
+  }
+  static __device__ __forceinline__ void st(uint16_t* row, int64_t e, raw_t q) {
+    __builtin_nontemporal_store(q, reinterpret_cast<u32x4*>(row + e));
+  }
+};
+
+template <>
+struct ShLane<4> {
+  typedef u32x2 raw_t;
+  static __device__ __forceinline__ raw_t ld(const uint16_t* row, int64_t e) { return Io<uint16_t>::ld_raw(row, e >> 2); }
+  static __device__ __forceinline__ void widen(raw_t q, float* x) {
+    const float4 a = Io<uint16_t>::f4(q);
+    x[0] = a.x, x[1] = a.y, x[2] = a.z, x[3] = a.w;
+  }
+  static __device__ __forceinline__ raw_t pack(const float* a) {
+    return Io<uint16_t>::pack(make_float4(a[0], a[1], a[2], a[3]));
+  }
+  static __device__ __forceinline__ void st(uint16_t* row, int64_t e, raw_t q) {
+    __builtin_nontemporal_store(q, reinterpret_cast<u32x2*>(row) + (e >> 2));
+  }
+};
+
+template <>
+struct ShLane<1> {
+  typedef float raw_t;  // the element widened: Io's st1 rounds it at each store
+  static __device__ __forceinline__ raw_t ld(const uint16_t* row, int64_t e) { return Io<uint16_t>::ld1(row, e); }
+  static __device__ __forceinline__ void widen(raw_t q, float* x) { x[0] = q; }
+  static __device__ __forceinline__ raw_t pack(const float* a) { return a[0]; }
+  static __device__ __forceinline__ void st(uint16_t* row, int64_t e, raw_t q) { Io<uint16_t>::st1(row, e, q); }
+};
+
+// B sources of a class from record s on, into the lane's accumulators: the records, then the
+// loads, then the fmas - no branch inside
+template <int LW, int B>
+__device__ __forceinline__ TAL_MX_DEVICE void sh_batch(const uint16_t* pin, int64_t ld_in, ConstI32x2 src, int s, int64_t e,
+                                                       float* acc) {
+  typedef ShLane<LW> L;
+  i32x2 rec[B];
+#pragma unroll
+  for (int k = 0; k < B; ++k) rec[k] = src[s + k];
+  typename L::raw_t v[B];
+#pragma unroll
+  for (int k = 0; k < B; ++k) v[k] = L::ld(pin + static_cast<int64_t>(rec[k].x) * ld_in, e);
+#pragma unroll
+  for (int k = 0; k < B; ++k) {
+    float x[LW];
+    L::widen(v[k], x);
+    // a builtin, so there is nothing to call under TAL_MX_DEVICE; from a scalar copy: applied to the
+    // vector element itself the cast read element 0, the row
+    const int32_t wbits = rec[k].y;
+    const float w = __builtin_bit_cast(float, wbits);
+#pragma unroll
+    for (int j = 0; j < LW; ++j) acc[j] = __fmaf_rn(w, x[j], acc[j]);
+  }
+}
+
+// Columns e0 .. e1-1 of every class, (e1 - e0) a multiple of LW; rows of both pools aligned to LW
+// elements from column e0 on (the launcher's ladder).
+template <int LW>
+__global__ __launch_bounds__(kShThreads) TAL_MX_DEVICE void k_round_shared(const uint16_t* pin, int64_t ld_in, uint16_t* pout,
+                                                                           int64_t ld_out, int64_t e0, int64_t e1, ShPlan p,
+                                                                           int64_t strips, int64_t items) {
+  typedef ShLane<LW> L;
+  const ConstI32 cls = (ConstI32)p.cls, out_row = (ConstI32)p.out_row;
+  const ConstI32x2 src = (ConstI32x2)p.src;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int c = static_cast<int>(item / strips);
+    const int64_t e = e0 + ((item % strips) * kShThreads + threadIdx.x) * LW;
+    if (e >= e1) continue;  // lanes past the columns (the last strip): no barrier in this kernel
+    const int s0 = cls[4 * c], s1 = s0 + cls[4 * c + 1], m0 = cls[4 * c + 2], m1 = m0 + cls[4 * c + 3];
+    float acc[LW];
+#pragma unroll
+    for (int j = 0; j < LW; ++j) acc[j] = -0.f;
+    int s = s0;
+    for (; s + kShBatch <= s1; s += kShBatch) sh_batch<LW, kShBatch>(pin, ld_in, src, s, e, acc);
+    if (s + 4 <= s1) { sh_batch<LW, 4>(pin, ld_in, src, s, e, acc); s += 4; }
+    if (s + 2 <= s1) { sh_batch<LW, 2>(pin, ld_in, src, s, e, acc); s += 2; }
+    if (s < s1) sh_batch<LW, 1>(pin, ld_in, src, s, e, acc);
+
+    uint32_t bad = 0;
+#pragma unroll
+    for (int j = 0; j < LW; ++j) bad |= mx_finite(acc[j]) ? 0u : 1u << j;
+    if (bad == 0) {
+      const typename L::raw_t q = L::pack(acc);
+      int m = m0;
+      for (; m + kShBatch <= m1; m += kShBatch) {
+        int32_t row[kShBatch];
+#pragma unroll
+        for (int k = 0; k < kShBatch; ++k) row[k] = out_row[m + k];
+#pragma unroll
+        for (int k = 0; k < kShBatch; ++k) L::st(pout + static_cast<int64_t>(row[k]) * ld_out, e, q);
+      }
+      for (; m < m1; ++m) L::st(pout + static_cast<int64_t>(out_row[m]) * ld_out, e, q);
+      continue;
+    }
+    // rare and divergent (an inf or NaN source, an overflow): the finite elements first ...
+    for (int m = m0; m < m1; ++m)
+#pragma unroll
+      for (int j = 0; j < LW; ++j)
+        if (!(bad >> j & 1u)) Io<uint16_t>::st1(pout + static_cast<int64_t>(p.out_row[m]) * ld_out, e + j, acc[j]);
+    // ... then, the accumulators dead, the others as each member row's own FMA-mode chain
+    for (int m = m0; m < m1; ++m) {
+      const int q0 = p.row_ptr[m], q1 = p.row_ptr[m + 1];
+      for (int j = 0; j < LW; ++j)
+        if (bad >> j & 1u)
+          Io<uint16_t>::st1(pout + static_cast<int64_t>(p.out_row[m]) * ld_out, e + j,
+                            mx_chain_steps(pin, ld_in, p.col, p.w, q0, q1, e + j));
+    }
+  }
+}
+
+ShPlan sh_view(const int32_t* table, const tal_shared_plan_info& in) {
+  ShPlan v;
+  v.cls = table + in.off_cls;
+  v.src = table + in.off_src;
+  v.out_row = table + in.off_out_row;
+  v.row_ptr = table + in.off_row_ptr;
+  v.col = table + in.off_col;
+  v.w = reinterpret_cast<const float*>(table + in.off_w);
+  return v;
+}
+
+template <int LW>
+int32_t launch_shared_lanes(const uint16_t* pin, int64_t ld_in, uint16_t* pout, int64_t ld_out, int64_t e0, int64_t e1,
+                            const ShPlan& v, const tal_shared_plan_info& in, hipStream_t s) {
+  if (e1 <= e0) return TAL_OK;
+  const int64_t strips = ((e1 - e0) / LW + kShThreads - 1) / kShThreads, items = strips * in.n_classes;
+  const int per_cu = resident_per_cu(reinterpret_cast<const void*>(k_round_shared<LW>), kShThreads, 0);
+  k_round_shared<LW><<<persistent_grid(items, per_cu, 1), kShThreads, 0, s>>>(pin, ld_in, pout, ld_out, e0, e1, v, strips, items);
+  return check_launch("shared round kernel");
+}
+
+// The alignment ladder: 16-B lanes, 8-B lanes, element lanes; the columns past the last whole
+// lane always by element lanes.
+int32_t launch_round_shared(const uint16_t* pin, int64_t ld_in, uint16_t* pout, int64_t ld_out, int64_t n,
+                            const int32_t* table, const tal_shared_plan_info& in, hipStream_t s) {
+  const ShPlan v = sh_view(table, in);
+  const uintptr_t base = reinterpret_cast<uintptr_t>(pin) | reinterpret_cast<uintptr_t>(pout);
+  const int lw = (base & 15u) == 0 && ld_in % 8 == 0 && ld_out % 8 == 0 ? 8
+               : (base & 7u) == 0 && ld_in % 4 == 0 && ld_out % 4 == 0 ? 4 : 1;
+  const int64_t body = n / lw * lw;
+  int32_t rc = lw == 8 ? launch_shared_lanes<8>(pin, ld_in, pout, ld_out, 0, body, v, in, s)
+             : lw == 4 ? launch_shared_lanes<4>(pin, ld_in, pout, ld_out, 0, body, v, in, s)
+                       : launch_shared_lanes<1>(pin, ld_in, pout, ld_out, 0, body, v, in, s);
+  if (rc == TAL_OK && body < n) rc = launch_shared_lanes<1>(pin, ld_in, pout, ld_out, body, n, v, in, s);
+  return rc;
 }
 
 // fp32 -> bf16 bits, nearest even (host; NaN keeps a quiet payload)
@@ -6152,6 +6362,28 @@ int32_t tal_agg_round_matrix_bf16(const uint16_t* pool_in, int64_t ld_in, uint16
     return fail(TAL_ERR_INVALID, fn + ": plan row " + std::to_string(info->max_row) + " >= pool_rows");
   if (n == 0) { g_err.clear(); return TAL_OK; }
   return launch_round_matrix(pool_in, ld_in, pool_out, ld_out, n, plan_dev, *info, static_cast<hipStream_t>(stream));
+}
+
+int32_t tal_agg_round_shared_bf16(const uint16_t* pool_in, int64_t ld_in, uint16_t* pool_out, int64_t ld_out,
+                                  int64_t pool_rows, int64_t n, const int32_t* table_dev,
+                                  const tal_shared_plan_info* info, void* stream) {
+  const std::string fn("tal_agg_round_shared_bf16");
+  if (!pool_in || !pool_out) return fail(TAL_ERR_INVALID, fn + ": null pool");
+  if (!table_dev) return fail(TAL_ERR_INVALID, fn + ": null table_dev");
+  if (!info) return fail(TAL_ERR_INVALID, fn + ": null info");
+  if (pool_out == pool_in) return fail(TAL_ERR_INVALID, fn + ": pool_out == pool_in (the round is a snapshot, out of place)");
+  if (info->n_classes <= 0 || info->n_src < info->n_classes || info->n_out < 2 * static_cast<int64_t>(info->n_classes) ||
+      info->nnz < info->n_out || info->max_row < 0 || info->off_cls < 0 || info->off_src < info->off_cls ||
+      info->off_src % 2 != 0 || info->off_out_row < info->off_src || info->off_row_ptr < info->off_out_row ||
+      info->off_col < info->off_row_ptr || info->off_w < info->off_col || info->words < info->off_w + info->nnz)
+    return fail(TAL_ERR_INVALID, fn + ": info is not a shared plan's");
+  if (reinterpret_cast<uintptr_t>(table_dev) & 7u) return fail(TAL_ERR_INVALID, fn + ": table_dev is not 8-B aligned");
+  if (n < 0) return fail(TAL_ERR_INVALID, fn + ": n < 0");
+  if (ld_in < n || ld_out < n) return fail(TAL_ERR_INVALID, fn + ": ld < n");
+  if (info->max_row >= pool_rows)
+    return fail(TAL_ERR_INVALID, fn + ": table row " + std::to_string(info->max_row) + " >= pool_rows");
+  if (n == 0) { g_err.clear(); return TAL_OK; }
+  return launch_round_shared(pool_in, ld_in, pool_out, ld_out, n, table_dev, *info, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

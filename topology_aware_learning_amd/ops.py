@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MatrixPlanInfo, RoundPlanInfo, SeqPlanInfo, check
+from ._lib import MatrixPlanInfo, RoundPlanInfo, SeqPlanInfo, SharedPlanInfo, check
 from .arena import SEG, SEGMENTS, Segment, segment_of
 
 MODE_EXACT = _lib.TAL_MODE_EXACT
@@ -512,6 +512,27 @@ def find_cliques(row_ptr, col, w, out_row, min_rows: int = CLIQUE_MIN_ROWS, per_
     return cliques, [r for r in range(len(out_row)) if r not in used]
 
 
+def find_row_classes(row_ptr, col, w, out_row):
+    """Row classes of a round (the K3ms kernel's rows, tal_agg.h): sets of >= 2 rows whose operand
+    multisets {(pool row, bits of fp32(w))} are equal - operands in any order, a source listed
+    twice counting twice, the own model anywhere or absent, any number of members; a row with a
+    non-finite fp32 weight joins none.  Returns (classes, rest): classes = [(pool rows, fp32
+    weights, row indices)], the operands in canonical order (sorted by pool row, then weight
+    bits), classes by their first row; rest = the other row indices."""
+    row_ptr, col, w, out_row = _csr(row_ptr, col, w, out_row)
+    w32 = w.astype(np.float32)
+    keys = col.astype(np.int64) << 32 | w32.view(np.uint32)
+    groups: dict = {}
+    for r in range(len(out_row)):
+        a, b = row_ptr[r], row_ptr[r + 1]
+        if b > a and np.all(np.isfinite(w32[a:b])):
+            groups.setdefault(np.sort(keys[a:b]).tobytes(), []).append(r)
+    classes = [(np.frombuffer(k, np.int64), rows) for k, rows in groups.items() if len(rows) >= 2]
+    member = {r for _, rows in classes for r in rows}
+    return ([((k >> 32).astype(np.int32), (k & 0xFFFFFFFF).astype(np.uint32).view(np.float32), rows) for k, rows in classes],
+            [r for r in range(len(out_row)) if r not in member])
+
+
 CLIQUE_EXTRA_W = CLIQUE_MAX + 3                            # an attached row's weights: 64 member positions, 2 ext, self
 CLIQUE_WWORDS = CLIQUE_MAX + CLIQUE_EXTRA * CLIQUE_EXTRA_W  # TAL_CLIQUE_WWORDS (332)
 
@@ -916,7 +937,7 @@ def plan_from_spec(row_ptr, col, w, out_row, spec: dict) -> RoundPlan:
     return p
 
 
-def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT):
+def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_EXACT, shared: bool = False):
     """The plan the round components build when they do not time candidates (tune=False).
     A round with clique blocks takes the first clique variant (_CLIQUE_VARIANTS) that finds
     blocks of its kind, in this order of preference:
@@ -954,11 +975,14 @@ def default_plan(row_ptr, col, w, out_row, bf16: bool = False, mode: int = MODE_
     `unweighted_fl` over > ~620 clients) gets a streamed plan - the fp32 streamed kernel, or for
     bf16 pools the wide-row kernel - or, rows out of reference order, one K1 call per row
     (RowCallPlan).  mode=MODE_MATRIX (opt-in, bf16 pools only: ValueError otherwise) is none of
-    this: the round's MatrixPlan (build_matrix_plan), whatever its graph."""
+    this: the round's MatrixPlan (build_matrix_plan), whatever its graph - with shared=True
+    (opt-in, MODE_MATRIX only: ValueError otherwise) its SharedPlan where rows share their operands."""
+    if shared and mode != MODE_MATRIX:
+        raise ValueError("shared=True is an option of MODE_MATRIX (tal_agg.h K3ms)")
     if mode == MODE_MATRIX:
         if not bf16:
             raise ValueError("MODE_MATRIX runs bf16 pools only (tal_agg.h K3m)")
-        return build_matrix_plan(row_ptr, col, w, out_row)
+        return build_matrix_plan(row_ptr, col, w, out_row, shared=shared)
     try:
         for name in ("clique256", "clique128", "clique", "wclique128", "wclique"):
             gate = _CLIQUE_VARIANTS[name][1]
@@ -1081,12 +1105,14 @@ def _round(seg: Segment, pool_in, pool_out, plan, n, mode, stream) -> torch.Tens
     """The round by the plan's kind: a CliquePlan runs K3c / K3c1 and its rest plan (on int64
     pools, which the clique kernels do not take, its `full` plan), a RowCallPlan one K1 call per
     row, any other plan the round kernel.  A MatrixPlan runs K3m on bf16 pools and its `full` plan
-    on int64 ones; MODE_MATRIX with any other plan is refused (there is no quiet FMA round)."""
-    if isinstance(plan, MatrixPlan):
+    on int64 ones, a SharedPlan likewise with K3ms and its rest plan; MODE_MATRIX with any other
+    plan is refused (there is no quiet FMA round)."""
+    if isinstance(plan, (MatrixPlan, SharedPlan)):
         if seg is _B16:
-            return round_matrix_bf16(pool_in, pool_out, plan, n, stream)
+            run = round_shared_bf16 if isinstance(plan, SharedPlan) else round_matrix_bf16
+            return run(pool_in, pool_out, plan, n, stream)
         if seg is not _I64:
-            raise ValueError("a MatrixPlan runs bf16 pools (int64 ones through its full plan), not fp32")
+            raise ValueError(f"a {type(plan).__name__} runs bf16 pools (int64 ones through its full plan), not fp32")
         plan = plan.full
     elif mode == MODE_MATRIX and seg.takes_mode:
         raise ValueError("MODE_MATRIX takes a MatrixPlan (build_matrix_plan)")
@@ -1262,11 +1288,17 @@ class MatrixPlan(_BlobPlan):
         return self
 
 
-def build_matrix_plan(row_ptr, col, w, out_row) -> MatrixPlan:
+def build_matrix_plan(row_ptr, col, w, out_row, shared: bool = False):
     """The K3m plan of a round given as CSR (row r: operands col[row_ptr[r]:row_ptr[r+1]] with
     float64 weights w, written to pool row out_row[r]).  Any operand count and order; neither
-    the rows nor the sources of a round are bounded."""
+    the rows nor the sources of a round are bounded.  shared=True (opt-in): where the round has
+    rows with identical operands (find_row_classes) a SharedPlan instead - one sum per class (K3ms),
+    the other rows through their FMA-mode plan; a round without a class gets the MatrixPlan."""
     (row_ptr, col, w, out_row), args = _csr_args(row_ptr, col, w, out_row)
+    if shared:
+        sp = _build_shared_plan(row_ptr, col, w, out_row)
+        if sp is not None:
+            return sp
     rows = len(out_row)
     L = _lib.load()
     info = MatrixPlanInfo()
@@ -1307,6 +1339,104 @@ def round_matrix_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: Matri
         ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
         pool_out.stride(0), pool_rows, n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info),
         _stream(pool_in.device, stream)))
+    return pool_out
+
+
+# ------------------------------------------------------------------------------------------
+# K3ms: one shared sum for matrix-mode rows with identical operands (opt-in inside MODE_MATRIX)
+# ------------------------------------------------------------------------------------------
+@dataclass
+class SharedPlan(_BlobPlan):
+    """A matrix-mode round split into row classes (tal_agg.h K3ms: one sum per class and column,
+    written to every member) and the remaining rows, which run `rest`, the regular FMA-mode plan
+    of their sub-round, and carry FMA mode's bits (None if there are none).  `full` is a regular
+    plan over all rows for the int64 segment, as a MatrixPlan's.  `class_index` / `rest_index`:
+    the round's row indices per class and of the rest."""
+    info: SharedPlanInfo
+    host: np.ndarray           # int32 table
+    rest: object
+    full: object
+    class_index: list
+    rest_index: list
+    device: Optional[torch.Tensor] = None
+    rows: int = 0
+    nnz: int = 0
+    tuned_ms: Optional[float] = None
+    candidates: Optional[list] = None
+    spec: Optional[dict] = None
+
+    @property
+    def single_group(self) -> bool:
+        return False  # out of place always
+
+    def staged_rows(self) -> int:
+        """Source rows read from HBM per column: every class's sources + the rest plan's."""
+        return int(self.info.n_src) + (self.rest.staged_rows() if self.rest is not None else 0)
+
+    def to(self, device) -> "SharedPlan":
+        super().to(device)
+        if self.rest is not None:
+            self.rest.to(device)
+        self.full.to(device)
+        return self
+
+
+def _build_shared_plan(row_ptr, col, w, out_row) -> Optional[SharedPlan]:
+    """The SharedPlan of a round (normalised CSR), or None when no two rows share their operands."""
+    classes, rest = find_row_classes(row_ptr, col, w, out_row)
+    if not classes:
+        return None
+    members = [r for _, _, rows in classes for r in rows]
+    m_rp, m_col, m_w, m_out = _sub_csr(row_ptr, col, w, out_row, members)
+    n_src, n_out, nnz = sum(len(s) for s, _, _ in classes), len(members), len(m_col)
+    info = SharedPlanInfo(n_classes=len(classes), n_src=n_src, n_out=n_out, nnz=nnz,
+                          max_src=max(len(s) for s, _, _ in classes), max_row=int(max(m_col.max(), m_out.max())))
+    info.off_cls, info.off_src = 0, 4 * len(classes)  # (even: the records are read as 8-B pairs)
+    info.off_out_row = info.off_src + 2 * n_src
+    info.off_row_ptr = info.off_out_row + n_out
+    info.off_col = info.off_row_ptr + n_out + 1
+    info.off_w = info.off_col + nnz
+    info.words = info.off_w + nnz
+    cls, s0, m0 = np.zeros((len(classes), 4), np.int32), 0, 0
+    for k, (srcs, _, rows) in enumerate(classes):
+        cls[k] = s0, len(srcs), m0, len(rows)
+        s0, m0 = s0 + len(srcs), m0 + len(rows)
+    src = np.stack([np.concatenate([s for s, _, _ in classes]),
+                    np.concatenate([ws for _, ws, _ in classes]).view(np.int32)], axis=1)
+    blob = np.concatenate([cls.reshape(-1), src.reshape(-1), m_out, m_rp, m_col,
+                           m_w.astype(np.float32).view(np.int32)]).astype(np.int32)
+    rest_plan = None
+    if rest:
+        rest_plan = default_plan(*_sub_csr(row_ptr, col, w, out_row, rest), bf16=True, mode=MODE_FMA)
+    full = default_plan(row_ptr, col, w, out_row, bf16=True)
+    if isinstance(full, CliquePlan):
+        full = full.full
+    return SharedPlan(info=info, host=blob, rest=rest_plan, full=full, class_index=[rows for _, _, rows in classes],
+                      rest_index=rest, rows=len(out_row), nnz=len(col), spec={"matrix": 1, "shared": 1})
+
+
+def round_shared_bf16(pool_in: torch.Tensor, pool_out: torch.Tensor, plan: SharedPlan, n: Optional[int] = None,
+                      stream=None) -> torch.Tensor:
+    """K3ms on [models, ld] bf16 pools, out of place: every row of a class = the class's one fp32
+    FMA chain in canonical order, rounded once (bound and non-finite rule in tal_agg.h); then the
+    rows outside the classes through the plan's FMA-mode rest plan.  Any pool alignment: 16-B, 8-B
+    or element lanes."""
+    if not isinstance(plan, SharedPlan):
+        raise TypeError("a shared round takes a SharedPlan (build_matrix_plan(shared=True))")
+    _check_pools(_B16, pool_in, pool_out, what="shared")
+    n = pool_in.shape[1] if n is None else int(n)
+    if not 0 <= n <= min(pool_in.shape[1], pool_out.shape[1]):
+        raise ValueError(f"n = {n} outside the pools' columns")
+    pool_rows = min(pool_in.shape[0], pool_out.shape[0])
+    if plan.info.max_row >= pool_rows:  # (the C entry refuses it too: TAL_ERR_INVALID, no launch)
+        raise ValueError("plan reads or writes a pool row beyond the pools")
+    _plan_on(plan, pool_in.device)
+    check(_lib.load().tal_agg_round_shared_bf16(
+        ctypes.c_void_p(pool_in.data_ptr()), pool_in.stride(0), ctypes.c_void_p(pool_out.data_ptr()),
+        pool_out.stride(0), pool_rows, n, ctypes.c_void_p(plan.device.data_ptr()), ctypes.byref(plan.info),
+        _stream(pool_in.device, stream)))
+    if plan.rest is not None:
+        _round(_B16, pool_in, pool_out, plan.rest, n, MODE_FMA, stream)
     return pool_out
 
 

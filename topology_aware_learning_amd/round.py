@@ -19,7 +19,8 @@ always).
 ``mode=ops.MODE_MATRIX`` (opt-in, bf16 pools without an fp32 segment) runs the b16 segment on
 the matrix cores (K3m, ``ops.MatrixPlan``; a tolerance, not the other modes' bits: tal_agg.h)
 and the int64 segment through the plan's ``full`` regular plan; always out of place (the spare
-or the scratch pool), snapshot rounds only.
+or the scratch pool), snapshot rounds only.  ``shared=True`` (opt-in inside that mode) gives rows
+with identical operands one sum (K3ms, ``ops.SharedPlan``) and runs the other rows in FMA mode.
 """
 from __future__ import annotations
 
@@ -99,13 +100,16 @@ class RoundExecutor:
 
     def __init__(self, pool: ModelPool, scratch: Optional[ModelPool] = None, mode: int = ops.MODE_EXACT,
                  placement_trials: int = 4, double_buffer: Optional[bool] = None,
-                 carried_rows: Optional[int] = None):
+                 carried_rows: Optional[int] = None, shared: bool = False):
         if mode == ops.MODE_MATRIX and (pool.layout.n_f32 or not pool.layout.n_b16):
             raise ValueError("MODE_MATRIX runs bf16 pools: this pool has an fp32 segment or no bf16 one "
                              "(the matrix round, K3m, exists for bf16 alone)")
+        if shared and mode != ops.MODE_MATRIX:
+            raise ValueError("shared=True is an option of MODE_MATRIX (one sum for rows with identical operands, K3ms)")
         self.pool = pool
         self.scratch = scratch
         self.mode = mode
+        self.shared = bool(shared)
         self.placement_trials = placement_trials
         self.placement: Optional[dict] = None
         self._plans: Dict[Tuple, ops.RoundPlan] = {}
@@ -143,12 +147,12 @@ class RoundExecutor:
         return keep
 
     def plan(self, orders, weights, out_rows) -> ops.RoundPlan:
-        key = _plan_key(orders, weights, out_rows)
+        key = _plan_key(orders, weights, out_rows) + (self.shared,)
         p = self._plans.get(key)
         if p is None:
             row_ptr, col, w = csr_from_lists(orders, weights)
-            p = ops.default_plan(row_ptr, col, w, np.asarray(out_rows, np.int32),
-                                 bf16=bool(self.pool.layout.n_b16), mode=self.mode).to(self.pool.device)
+            p = ops.default_plan(row_ptr, col, w, np.asarray(out_rows, np.int32), bf16=bool(self.pool.layout.n_b16),
+                                 mode=self.mode, shared=self.shared).to(self.pool.device)
             rest = sorted(set(range(self.carried_rows)) - set(int(r) for r in out_rows))
             # rows a double-buffered round does not aggregate: copied into the spare before the swap
             p.rest_rows = torch.as_tensor(rest, dtype=torch.long, device=self.pool.device) if rest else None
